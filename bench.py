@@ -10,13 +10,20 @@ ranks is reported by rank 0 as ONE JSON line.
 the GPU) runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same args>` as a
 child process and relays rank 0's line.  Launched under torch.distributed.run it is a rank.
 
-For N > 1 the line also carries `strong` (the BASELINE metric's global batch of 16 split over the ranks, per-rank BatchNorm) and
-`sync_bn` (the weak run with cross-rank BatchNorm statistics): SURVEY.md section 8(d).
-
 `--config K` selects one of BASELINE.json's five configurations (1: 2x64x64; 2: 16x256x256 - the default; 3: 4x512x512 per GPU in
 bf16; 4: DeepLabV3+ 16x256x256; 5: 1x1024x1024 per GPU, fp16 operands + loss scaling, hipGraph-captured step incl. the RCCL all-reduces for N > 1).
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` then also writes what the last timed step
+handed its caller as float32 .npy files (see dump_outputs), so that two builds can be compared output for output: the inputs, the
+initial weights and the dropout draws are seeded, identical from run to run with the same arguments.
+
+`--full` adds the secondary measurements, which a plain run skips:
+  roofline     - see below; with one rank its per-launch HIP events run inside the timed region (about 0.2 ms per step).
+  cpu_baseline - the oracle's train step on the host cores (about 25 s).
+  strong / sync_bn (N > 1) - the BASELINE metric's global batch of 16 split over the ranks (per-rank BatchNorm), and the weak run with
+                 cross-rank BatchNorm statistics: SURVEY.md section 8(d).
+
+Extra objects on the line with --full:
   roofline     - the dominant matrix-core kernel of the step (largest accumulated launch time).  `frac` = EXECUTED multiply-add FLOPs
                  per launch / average launch duration / dense MFMA peak of the arithmetic's type (fp32 157.3 TFLOP/s; bf16 2500; the
                  split-operand "x3" kernels do fp32 arithmetic with six bf16 MFMAs per product: `bf16_matrix_pipe` has that view), the
@@ -97,11 +104,15 @@ def parse_args(argv=None):
     ap.add_argument("--graph", action="store_true", help="hipGraph-captured step (with N > 1 the RCCL gradient all-reduces are captured with it)")
     ap.add_argument("--loss-scale", type=float, default=1024.0, help="static loss scale of the fp16 mode (ignored otherwise)")
     ap.add_argument("--sync-bn", action="store_true", help="primary run with cross-rank BatchNorm statistics (results equal the global-batch step)")
-    ap.add_argument("--no-extra-runs", action="store_true", help="N > 1: skip the `strong` and `sync_bn` sub-runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline, the CPU baseline and (N > 1) the `strong` / `sync_bn` sub-runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-extra-runs", action="store_true", help="with --full, N > 1: skip the `strong` and `sync_bn` sub-runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)   # CPU test of the self-launcher (gloo, no GPU)
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config or 2]
     for k in ("model", "batch", "size", "dtype"):
         if getattr(args, k) is None:
@@ -179,6 +190,34 @@ def cpu_baseline(batch, size, seed):
     return {"value": round(n * steps / dt, 3), "unit": "images/s", "cores": torch.get_num_threads(), "kind": "port",
             "spread": {"steps": steps, "images_per_s_min": round(n / max(times), 3), "images_per_s_max": round(n / min(times), 3)},
             "sample": f"{steps} train steps of {n} images {size}x{size} (fwd+BCE+bwd+Adam, fp32, torch CPU ops; the benchmarked batch is {batch}) after 1 warm-up step"}
+
+
+# ------------------------------------------------------------------------------------------------ outputs of the last timed step
+DUMP_SAMPLE = 1 << 22     # values kept of each flattened parameter / gradient vector (16 MB of float32; 40.9 M each at base 64)
+
+
+def dump_outputs(outdir, model, final_loss):
+    """Write what a caller of the train step holds after the last timed step, float32: loss.npy [1]; params.npy and grads.npy, the
+    parameters after the Adam update and the gradients of that step, flattened in named_parameters() order and cut to a fixed seeded
+    sample of DUMP_SAMPLE positions (the same positions for every build of the same model; a parameter without a gradient counts as
+    zeros); buffers.npy, all BatchNorm running statistics and step counters in named_buffers() order.  About 32 MB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    flat = {"params": torch.cat([p.detach().reshape(-1).float() for p in params]),
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])}
+    n = flat["params"].numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))).to(flat["params"].device)
+    out = {"loss": np.array([final_loss], dtype=np.float32)}
+    for k, v in flat.items():
+        out[k] = (v if idx is None else v.index_select(0, idx)).cpu().numpy()
+    out["buffers"] = torch.cat([b.detach().reshape(-1).float() for _, b in model.named_buffers()]).cpu().numpy()
+    for k, v in out.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
+    log(f"outputs of the last timed step written to {outdir}: " + ", ".join(f"{k}{list(v.shape)}" for k, v in out.items()))
 
 
 # ------------------------------------------------------------------------------------------------ one rank
@@ -291,7 +330,7 @@ def run_rank(args):
     if rank == 0:
         log(f"{args.model} on {dev}, {args.warmup} warm-up + {args.steps} timed steps of {args.batch} x {args.size}x{args.size} per GPU, "
             f"{args.dtype}" + (", hipGraph step" if graph else ""))
-    want_roof = not args.no_roofline and args.model == "runet" and not graph
+    want_roof = args.full and not args.no_roofline and args.model == "runet" and not graph
     # One rank: the per-launch HIP events of the roofline run inside the timed region (0.2 ms of a 33 ms step).  Under a process group they
     # cost the step 5 % (35.4 against 33.5 ms with one RCCL rank, tools/ddp_overhead.py: 33.4 without them), which would be charged to
     # every rank of a scaling run: there the timed region runs clean and the roofline comes from a pass of its own right after it.
@@ -300,6 +339,8 @@ def run_rank(args):
     enqueue_ms = host_ms[0]
     if rank == 0:
         log(f"timed region {dt:.3f} s")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, model, final_loss)     # before any further pass moves the weights on
     roof_steps, roof_dt = args.steps, dt
     if want_roof and not roof_in_region:
         roof_steps = max(3, min(args.steps, 10))
@@ -315,7 +356,7 @@ def run_rank(args):
         ops.USE_WGRAD_STREAM = True
 
     extra = {}
-    if world > 1 and not args.no_extra_runs and not strong:
+    if world > 1 and args.full and not args.no_extra_runs and not strong:
         # secondary measurements: a failure here must not cost the primary line (every rank takes the same branch: the exceptions these
         # calls can raise - allocation, launch errors - are raised on all ranks alike or abort the job)
         try:
@@ -405,7 +446,7 @@ def run_rank(args):
                 r["by_kernel_columns"] = r["by_kernel_columns"] + ["algorithmic GB/s"]
                 if alone is not None and len(alone) > 4:
                     r["standalone"] = {"achieved": alone[4], "frac": round(alone[4] / HBM_PEAK_GBS, 4), "avg_launch_us": round(1e3 * alone[1] / alone[0], 2)}
-        if world == 1 and not args.no_cpu_baseline and args.model == "runet":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.model == "runet":
             out["cpu_baseline"] = cpu_baseline(args.batch, args.size, 1234)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

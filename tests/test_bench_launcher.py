@@ -34,3 +34,27 @@ def test_config_presets_follow_baseline_json():
     assert a.model == "deeplab"
     a = bench.parse_args(["--config", "1", "--batch", "8"])
     assert (a.batch, a.size) == (8, 64)
+
+
+def test_plain_run_options_and_output_dump(tmp_path):
+    """A plain run leaves the secondary measurements to --full; --dump-outputs writes float32 arrays, at most 64 MB, at fixed positions."""
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert bench.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full
+    model = importlib.import_module("eusipco-2026-robust-unet_amd").RobustUNet(3, 1, 64)      # 40.9 M parameters: sampled
+    for i, p in enumerate(model.parameters()):
+        p.grad = torch.full_like(p, float(i))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), model, 0.5)
+    total = 0
+    for name in ("loss", "params", "grads", "buffers"):
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [0.5]
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    assert np.isin(np.load(tmp_path / "a" / "params.npy"), flat).all()

@@ -6,16 +6,16 @@ set -e
 TAG=${1:-round3}
 O=gpurun_out/${TAG}p
 mkdir -p $O
-python bench.py > $O/${TAG}_bench_n1.json 2> $O/bench_n1.err
-python bench.py --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_n1_bf16.json 2>/dev/null
+python bench.py --full > $O/${TAG}_bench_n1.json 2> $O/bench_n1.err
+python bench.py --full --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_n1_bf16.json 2>/dev/null
 python bench.py --batch 2 --no-roofline --no-cpu-baseline > $O/${TAG}_bench_b2.json 2>/dev/null
 python bench.py --batch 2 --graph --no-cpu-baseline > $O/${TAG}_bench_b2_graph.json 2>/dev/null
-python bench.py --config 1 --no-cpu-baseline > $O/${TAG}_bench_config1.json 2>/dev/null
+python bench.py --full --config 1 --no-cpu-baseline > $O/${TAG}_bench_config1.json 2>/dev/null
 python bench.py --config 1 --graph --no-cpu-baseline > $O/${TAG}_bench_config1_graph.json 2>/dev/null
-python bench.py --config 3 --no-cpu-baseline > $O/${TAG}_bench_config3.json 2>/dev/null
+python bench.py --full --config 3 --no-cpu-baseline > $O/${TAG}_bench_config3.json 2>/dev/null
 python bench.py --config 4 --no-cpu-baseline > $O/${TAG}_bench_config4.json 2>/dev/null
 python bench.py --config 5 --no-cpu-baseline > $O/${TAG}_bench_config5.json 2>/dev/null
-RUNET_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline > $O/${TAG}_bench_n1_rccl_one_rank.json 2>/dev/null
+RUNET_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline > $O/${TAG}_bench_n1_rccl_one_rank.json 2>/dev/null
 RUNET_BENCH_FORCE_DIST=1 python bench.py --config 5 --no-cpu-baseline > $O/${TAG}_bench_config5_rccl_one_rank.json 2>/dev/null
 echo benches done
 bash tools/collect_profiles.sh $O ${TAG}
