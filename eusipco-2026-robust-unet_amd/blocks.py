@@ -765,6 +765,44 @@ def maxpool_backward(dy, idx, dx=None):
     return dx
 
 
+def bn_relu_maxpool_forward(t, scale, shift):
+    """maxpool2(relu(t * scale + shift)) in one pass: -> (pooled, idx); the full-resolution activation is not written (SegNet's encoder ends)."""
+    n, h, w, c = t.shape
+    y = ops.empty_nhwc(n, h // 2, w // 2, c, t)
+    idx = torch.empty((n, h // 2, w // 2, c), device=t.device, dtype=torch.uint8)
+    check(lib.runet_bn_relu_maxpool2_fwd(t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), ops.ld(y), idx.data_ptr(), n, h, w,
+                                         c, ops.stream()))
+    return y, idx
+
+
+def bn_backward_pooled(dpool, idx, x, mean, invstd, scale, sums, relu_shift, training=True):
+    """bn_backward(maxpool_backward(dpool, idx), x, ..., relu_shift=...) without the full-resolution gradient: the two pooled-gradient kernels
+    scatter it in registers.  -> dx (full resolution)"""
+    n, h, w, c = x.shape
+    st = ops.stream()
+    check(lib.runet_bn_bwd_reduce_pooled(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), n, h, w, c, mean.data_ptr(),
+                                         invstd.data_ptr(), _ws(n, h * w, c, x.device).data_ptr(), sums.data_ptr(), scale.data_ptr(),
+                                         relu_shift.data_ptr(), st))
+    use = sums if training else zeros(2 * c, x.device)
+    dx = ops.empty_nhwc(n, h, w, c, x)
+    check(lib.runet_bn_bwd_apply_pooled(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), dx.data_ptr(), ops.ld(dx), n, h, w, c,
+                                        mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), use.data_ptr(), 0, relu_shift.data_ptr(), st))
+    return dx
+
+
+def maxunpool_forward(x, idx):
+    """nn.MaxUnpool2d(2, 2) by a 2x2 pool's winner bytes: zeros, each value at its index (= runet_maxpool2_bwd without accumulation)."""
+    return maxpool_backward(x, idx)
+
+
+def maxunpool_backward(du, idx):
+    """Gradient of maxunpool_forward: the gather du[2ho + k/2, 2wo + k%2] at each pooled position."""
+    n, h, w, c = du.shape
+    dp = ops.empty_nhwc(n, h // 2, w // 2, c, du)
+    check(lib.runet_maxunpool2_bwd(du.data_ptr(), ops.ld(du), idx.data_ptr(), dp.data_ptr(), ops.ld(dp), n, h, w, c, ops.stream()))
+    return dp
+
+
 def to_nhwc_pad(x_nchw, c_pad):
     n, c, h, w = x_nchw.shape
     y = torch.empty((n, h, w, c_pad), device=x_nchw.device, dtype=torch.float32)

@@ -73,6 +73,75 @@ __global__ __launch_bounds__(TPB) void maxpool2_bwd_kernel(const float* __restri
     }
 }
 
+// ---- BatchNorm (per-channel affine) + ReLU + 2x2 max pool in one pass (SegNet encoder ends): t is read once, only the pooled values and
+// the winner bytes are written.  The window compares the post-affine, post-ReLU values with bn_apply_kernel's own expressions (bn_pre, then
+// fmaxf with 0, then the unit dropout factor), so values and bytes equal runet_bn_apply(relu=1) followed by runet_maxpool2_fwd.
+__global__ __launch_bounds__(TPB) void bn_relu_maxpool2_fwd_kernel(const float* __restrict__ t, int ldt, const float* __restrict__ scale,
+                                                                   const float* __restrict__ shift, float* __restrict__ y, int ldy,
+                                                                   unsigned char* __restrict__ idx, int N, int Ho, int Wo, int C,
+                                                                   float unit) {
+    const int cvec = C / 4;
+    const long total = (long)N * Ho * Wo * cvec;
+    const int W = Wo * 2;
+    for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
+        const long op = i / cvec;
+        const int c = (int)(i - op * cvec) * 4;
+        const int wo = (int)(op % Wo);
+        const long tt = op / Wo;
+        const int ho = (int)(tt % Ho);
+        const long n = tt / Ho;
+        const long ip = (n * (Ho * 2) + ho * 2) * W + wo * 2;
+        float sc[4], sh[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { sc[e] = scale[c + e]; sh[e] = shift[c + e]; }
+        auto act = [&](long q) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(t + q * ldt + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaxf(bn_pre(v[e], sc[e], sh[e]), 0.f) * unit;
+            return v;
+        };
+        f32x4 m = act(ip);
+        unsigned int sel[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 1; k < 4; ++k) {
+            const f32x4 v = act(ip + (k >> 1) * W + (k & 1));
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (v[e] > m[e] || v[e] != v[e]) { m[e] = v[e]; sel[e] = k; }
+        }
+        *reinterpret_cast<f32x4*>(y + op * ldy + c) = m;
+        *reinterpret_cast<unsigned int*>(idx + op * C + c) = sel[0] | (sel[1] << 8) | (sel[2] << 16) | (sel[3] << 24);
+    }
+}
+// ---- MaxUnpool2d(2, 2) backward: the gather dpool[n, ho, wo, c] = dU[n, 2ho + k/2, 2wo + k%2, c], k = the pool's winner byte.  All four window
+// vectors are loaded (the neighbouring lanes need the other channels of the same lines anyway) and selected per element.
+__global__ __launch_bounds__(TPB) void maxunpool2_bwd_kernel(const float* __restrict__ du, int lddu, const unsigned char* __restrict__ idx,
+                                                             float* __restrict__ dp, int ldp, int N, int Ho, int Wo, int C) {
+    const int cvec = C / 4;
+    const long total = (long)N * Ho * Wo * cvec;
+    const int W = Wo * 2;
+    for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
+        const long op = i / cvec;
+        const int c = (int)(i - op * cvec) * 4;
+        const int wo = (int)(op % Wo);
+        const long tt = op / Wo;
+        const int ho = (int)(tt % Ho);
+        const long n = tt / Ho;
+        const long ip = (n * (Ho * 2) + ho * 2) * W + wo * 2;
+        const unsigned int s = *reinterpret_cast<const unsigned int*>(idx + op * C + c);
+        f32x4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const f32x4*>(du + (ip + (k >> 1) * W + (k & 1)) * lddu + c);
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned int k = (s >> (8 * e)) & 3;
+            o[e] = k == 0 ? v[0][e] : k == 1 ? v[1][e] : k == 2 ? v[2][e] : v[3][e];
+        }
+        *reinterpret_cast<f32x4*>(dp + op * ldp + c) = o;
+    }
+}
+
 // ---- strided [N,C,H,W] (any strides) -> NHWC with channels zero-padded to Cp
 __global__ __launch_bounds__(TPB) void to_nhwc_pad_kernel(const float* __restrict__ x, long sn, long sc, long sh, long sw,
                                                           float* __restrict__ y, int N, int C, int H, int W, int Cp) {
@@ -195,6 +264,29 @@ extern "C" int runet_maxpool2_bwd(const float* dy, int lddy, const unsigned char
     RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, n_img, h / 2, w / 2, c, accumulate);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_relu_maxpool2_fwd(const float* t, int ldt, const float* scale, const float* shift, float* y, int ldy, unsigned char* idx,
+                                          int n_img, int h, int w, int c, void* stream) {
+    RUNET_REQUIRE(t && scale && shift && y && idx, "null pointer");
+    RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ldt >= c && ldy >= c && ldt % 4 == 0 && ldy % 4 == 0, "bad shape");
+    const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
+    // unit: the dropout factor bn_apply_kernel multiplies by when no mask is given, passed at run time so the product stays in the code
+    hipLaunchKernelGGL(bn_relu_maxpool2_fwd_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
+                       n_img, h / 2, w / 2, c, 1.0f);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_maxunpool2_bwd(const float* du, int lddu, const unsigned char* idx, float* dpool, int ldp, int n_img, int h, int w, int c,
+                                    void* stream) {
+    RUNET_REQUIRE(du && idx && dpool, "null pointer");
+    RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && lddu >= c && ldp >= c && lddu % 4 == 0 && ldp % 4 == 0, "bad shape");
+    const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
+    hipLaunchKernelGGL(maxunpool2_bwd_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, du, lddu, idx, dpool, ldp, n_img, h / 2,
+                       w / 2, c);
     RUNET_CHECK_LAUNCH();
 }
 

@@ -334,8 +334,25 @@ __global__ __launch_bounds__(TPB) void bn_apply_kernel(const float* __restrict__
     }
 }
 
+// The incoming gradient of a 2x2 max-pool (POOL): dy is the POOLED gradient [n, H/2, W/2] (pixel stride lddy) and pidx its winner bytes
+// (dense, C per pooled pixel); the full-resolution g is rebuilt in registers exactly as runet_maxpool2_bwd(accumulate=0) would write it:
+// g(h, w) = pidx[h/2, w/2] == (h&1)*2 + (w&1) ? dy[h/2, w/2] : 0.  W is the full-resolution width.  The POOL instances below take pidx / W
+// in the act / ldact argument slots (they have no saved activation: ReLU from x), so the other instances keep their argument list and code.
+__device__ __forceinline__ f32x4 pooled_grad4(const float* __restrict__ dy, int lddy, const unsigned char* __restrict__ pidx, int W, int C,
+                                              int n, int HW, int p, int c) {
+    const int hh = p / W, ww = p - hh * W;
+    const long q = (long)n * (HW >> 2) + (long)(hh >> 1) * (W >> 1) + (ww >> 1);
+    const f32x4 t = *reinterpret_cast<const f32x4*>(dy + q * lddy + c);
+    const unsigned int s = *reinterpret_cast<const unsigned int*>(pidx + q * C + c);
+    const unsigned int k = (unsigned)((hh & 1) * 2 + (ww & 1));
+    f32x4 g;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[e] = (((s >> (8 * e)) & 0xff) == k) ? t[e] : 0.f;
+    return g;
+}
+
 // partial sums of g and g*xhat per channel; g = dy [* mask[n,c] * (act > 0)]
-template <int VEC>
+template <int VEC, bool POOL = false>
 __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __restrict__ dy, int lddy, const float* __restrict__ x,
                                                              int ldx, const float* __restrict__ act, int ldact, int HW, int C,
                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -347,6 +364,9 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
     const int col = tid % cvec, row = tid / cvec;
     const int n = blockIdx.y, chunk = blockIdx.x;
     const int p0 = chunk * pix_per_chunk, p1 = min(HW, p0 + pix_per_chunk);
+    const unsigned char* pidx = POOL ? reinterpret_cast<const unsigned char*>(act) : nullptr;
+    const int W = POOL ? ldact : 0;
+    if constexpr (POOL) act = nullptr;
     // ReLU(+Dropout2d) backward: either from the saved activation (act > 0) or, when rscale/rshift are given, recomputed from x with
     // the forward's own expression x*scale + shift > 0 - one tensor less to read
     const bool recompute = rscale != nullptr;
@@ -364,7 +384,9 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
         const long ib = (long)n * HW;
         auto fetch = [&](int p, float (&g)[VEC], float (&xv)[VEC], float (&av)[VEC]) {
             if constexpr (VEC == 4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(dy + (ib + p) * lddy + col * 4);
+                f32x4 t;
+                if constexpr (POOL) t = pooled_grad4(dy, lddy, pidx, W, C, n, HW, p, col * 4);
+                else t = *reinterpret_cast<const f32x4*>(dy + (ib + p) * lddy + col * 4);
                 const f32x4 u = *reinterpret_cast<const f32x4*>(x + (ib + p) * ldx + col * 4);
                 g[0] = t[0]; g[1] = t[1]; g[2] = t[2]; g[3] = t[3];
                 xv[0] = u[0]; xv[1] = u[1]; xv[2] = u[2]; xv[3] = u[3];
@@ -431,7 +453,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_final(const float* __restri
     }
 }
 
-template <int VEC>
+template <int VEC, bool POOL = false>
 __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x,
                                                            int ldx, const float* __restrict__ act, int ldact, float* __restrict__ dx,
                                                            int lddx, int HW, int C, int pix_per_chunk, const float* __restrict__ mean,
@@ -443,6 +465,9 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
     if (row >= rows) return;
     const int n = blockIdx.y;
     const int p0 = blockIdx.x * pix_per_chunk, p1 = min(HW, p0 + pix_per_chunk);
+    const unsigned char* pidx = POOL ? reinterpret_cast<const unsigned char*>(act) : nullptr;
+    const int W = POOL ? ldact : 0;
+    if constexpr (POOL) act = nullptr;
     // dx = sc*(g - k1 - xhat*k2) = g*sc + x*a + b  with a = -sc*k2*invstd, b = sc*(mean*invstd*k2 - k1)
     const bool recompute = rshift != nullptr;        // ReLU mask from x*scale + shift > 0 (scale IS the forward scale) instead of act > 0
     float sc[VEC], ca[VEC], cb[VEC], mk[VEC], fh[VEC];
@@ -458,7 +483,9 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
     for (int p = p0 + row; p < p1; p += rows) {
         float g[VEC], xv[VEC], av[VEC];
         if constexpr (VEC == 4) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(dy + (ib + p) * lddy + col * 4);
+            f32x4 t;
+            if constexpr (POOL) t = pooled_grad4(dy, lddy, pidx, W, C, n, HW, p, col * 4);
+            else t = *reinterpret_cast<const f32x4*>(dy + (ib + p) * lddy + col * 4);
             const f32x4 u = *reinterpret_cast<const f32x4*>(x + (ib + p) * ldx + col * 4);
             g[0] = t[0]; g[1] = t[1]; g[2] = t[2]; g[3] = t[3];
             xv[0] = u[0]; xv[1] = u[1]; xv[2] = u[2]; xv[3] = u[3];
@@ -711,5 +738,46 @@ extern "C" int runet_chan_sum(const float* x, int ld, long pixels, int c, float*
     else hipLaunchKernelGGL((chan_sum_partial<1>), dim3((int)chunks), dim3(TPB), lds, st, x, ld, pixels, c, ppc, workspace);
     const int cw = final_cw(c, chunks);
     hipLaunchKernelGGL(chan_sum_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, (int)chunks, c, cw, out, accumulate);
+    RUNET_CHECK_LAUNCH();
+}
+
+// runet_bn_bwd_reduce / runet_bn_bwd_apply for a BatchNorm + ReLU whose output fed ONLY a 2x2 max-pool: the gradient arrives at pooled
+// resolution with the pool's winner bytes and is scattered in registers (POOL instances above); ReLU mask from x (relu_shift form).
+// Same chunking and summation order as the two-launch path, hence the same bits as runet_maxpool2_bwd(accumulate=0) + the plain calls.
+#define REQ_POOLED(h, w, c) RUNET_REQUIRE((h) > 0 && (w) > 0 && (h) % 2 == 0 && (w) % 2 == 0 && (c) % 4 == 0 && (c) >= 4 && (c) <= 1024, \
+                                          "h, w must be even and c a multiple of 4 (at most 1024)")
+
+extern "C" int runet_bn_bwd_reduce_pooled(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, int n_img, int h,
+                                          int w, int c, const float* mean, const float* invstd, float* workspace, float* sums,
+                                          const float* relu_scale, const float* relu_shift, void* stream) {
+    RUNET_REQUIRE(dpool && idx && x && mean && invstd && workspace && sums && relu_scale && relu_shift, "null pointer");
+    REQ_POOLED(h, w, c);
+    RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && ldp % 4 == 0 && ldx % 4 == 0, "bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    const int hw = h * w, rows = TPB / (c / 4);
+    const int chunks = pick_chunks(n_img, hw, c, rows);
+    const int ppc = (hw + chunks - 1) / chunks;
+    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
+    hipLaunchKernelGGL((bn_bwd_reduce_partial<4, true>), dim3(chunks, n_img), dim3(TPB), lds, st, dpool, ldp, x, ldx,
+                       reinterpret_cast<const float*>(idx), w, hw, c, mean, invstd, nullptr, ppc, workspace, relu_scale, relu_shift);
+    const int cw = final_cw(c, (long)chunks * n_img);
+    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_bwd_apply_pooled(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, float* dx, int lddx,
+                                         int n_img, int h, int w, int c, const float* mean, const float* invstd, const float* scale,
+                                         const float* sums, long m_total, const float* relu_shift, void* stream) {
+    RUNET_REQUIRE(dpool && idx && x && dx && mean && invstd && scale && sums && relu_shift, "null pointer");
+    REQ_POOLED(h, w, c);
+    RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && lddx >= c && ldp % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, "bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    const long pixels = (long)n_img * h * w;
+    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
+    const int hw = h * w;
+    int ppc;
+    const int chunks = stream_chunks(n_img, hw, c, TPB / (c / 4), ppc);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true>), dim3(chunks, n_img), dim3(TPB), 0, st, dpool, ldp, x, ldx,
+                       reinterpret_cast<const float*>(idx), w, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, nullptr, inv_m, relu_shift);
     RUNET_CHECK_LAUNCH();
 }

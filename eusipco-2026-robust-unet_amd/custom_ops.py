@@ -7,6 +7,8 @@ hand-written data-gradient / weight-gradient kernels.
     torch.ops.runet.conv2d_nhwc_dgrad / conv2d_nhwc_wgrad        its two gradients (ops in their own right)
     torch.ops.runet.convt2x2s2_nhwc(x, w_hwio, bias)             ConvTranspose2d(k2, s2)  (+ _dgrad / _wgrad)
     torch.ops.runet.maxpool2_nhwc(x) -> (y, idx)                 MaxPool2d(2) with the argmax byte  (+ maxpool2_nhwc_bwd)
+    torch.ops.runet.maxunpool2_nhwc(x, idx)                      MaxUnpool2d(2, 2) by those bytes (comne.py:177-211); backward = the gather
+    torch.ops.runet.bn_relu_maxpool2_nhwc(t, scale, shift)       maxpool2(relu(t * scale + shift)) in one pass -> (y, idx); forward only
     torch.ops.runet.bce_loss(prob, target)                       nn.BCELoss() mean, ATen clamp semantics (Main_Final.py:551)
     torch.ops.runet.cross_entropy(logits, target)                nn.CrossEntropyLoss() mean (train_water_segmentation.py:304)
     torch.ops.runet.seg_counts(pred, target, threshold)          per-image tp / predicted / target / agreement counts (Main_Final.py:519-547)
@@ -179,6 +181,56 @@ def _pool_bwd(ctx, dy, _didx):
 register_autograd("runet::maxpool2_nhwc", _pool_bwd, setup_context=_pool_setup)
 
 
+@custom_op("runet::maxunpool2_nhwc", mutates_args=(), device_types=_DEV)
+def maxunpool2_nhwc(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    _chk_nhwc(x)
+    from . import blocks
+    return blocks.maxunpool_forward(x.contiguous(), idx.contiguous())
+
+
+@maxunpool2_nhwc.register_fake
+def _(x, idx):
+    n, h, w, c = x.shape
+    return x.new_empty((n, 2 * h, 2 * w, c))
+
+
+@custom_op("runet::maxunpool2_nhwc_bwd", mutates_args=(), device_types=_DEV)
+def maxunpool2_nhwc_bwd(dy: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    from . import blocks
+    return blocks.maxunpool_backward(dy.contiguous(), idx.contiguous())
+
+
+@maxunpool2_nhwc_bwd.register_fake
+def _(dy, idx):
+    n, h, w, c = dy.shape
+    return dy.new_empty((n, h // 2, w // 2, c))
+
+
+def _unpool_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+
+
+def _unpool_bwd(ctx, dy):
+    (idx,) = ctx.saved_tensors
+    return torch.ops.runet.maxunpool2_nhwc_bwd(dy.contiguous(), idx), None
+
+
+register_autograd("runet::maxunpool2_nhwc", _unpool_bwd, setup_context=_unpool_setup)
+
+
+@custom_op("runet::bn_relu_maxpool2_nhwc", mutates_args=(), device_types=_DEV)
+def bn_relu_maxpool2_nhwc(t: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    _chk_nhwc(t)
+    from . import blocks
+    return blocks.bn_relu_maxpool_forward(t.contiguous(), scale.contiguous(), shift.contiguous())
+
+
+@bn_relu_maxpool2_nhwc.register_fake
+def _(t, scale, shift):
+    n, h, w, c = t.shape
+    return t.new_empty((n, h // 2, w // 2, c)), t.new_empty((n, h // 2, w // 2, c), dtype=torch.uint8)
+
+
 # ------------------------------------------------------------------------------------------------ losses / metrics / resize
 @custom_op("runet::bce_loss", mutates_args=(), device_types=_DEV)
 def bce_loss(prob: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -294,4 +346,4 @@ register_autograd("runet::bilinear_resize", _bil_bwd, setup_context=_bil_setup)
 
 OPS = ("conv2d_nhwc", "conv2d_nhwc_dgrad", "conv2d_nhwc_wgrad", "convt2x2s2_nhwc", "convt2x2s2_nhwc_dgrad", "convt2x2s2_nhwc_wgrad",
        "maxpool2_nhwc", "maxpool2_nhwc_bwd", "bce_loss", "bce_loss_bwd", "cross_entropy", "cross_entropy_bwd", "seg_counts",
-       "bilinear_resize", "bilinear_resize_bwd")
+       "bilinear_resize", "bilinear_resize_bwd", "maxunpool2_nhwc", "maxunpool2_nhwc_bwd", "bn_relu_maxpool2_nhwc")

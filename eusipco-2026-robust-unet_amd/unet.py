@@ -88,42 +88,68 @@ class UNet(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------------ blocks
-def _block_forward(x, seq, training, sm, out=None, save=True):
-    c1, bn1, c2, bn2 = seq[0], seq[1], seq[3], seq[4]
-    w1, w2 = ops.hwio(c1.weight), ops.hwio(c2.weight)
-    t1 = ops.conv_fwd(x, w1, c1.bias)
-    s1, h1, mean1, invstd1, _ = B.bn_coeff(t1, bn1.state(), training, sm)
-    a1 = B.bn_apply(t1, s1, h1, None, relu=True)
-    t2 = ops.conv_fwd(a1, w2, c2.bias)
-    s2, h2, mean2, invstd2, _ = B.bn_coeff(t2, bn2.state(), training, sm)
-    a2 = B.bn_apply(t2, s2, h2, None, relu=True, out=out)
-    ctx = None
-    if save:
-        ctx = dict(x=x, w1=w1, w2=w2, t1=t1, a1=a1, t2=t2, s1=s1, h1=h1, mean1=mean1, invstd1=invstd1, s2=s2, h2=h2, mean2=mean2, invstd2=invstd2,
-                   training=training, cin_w=w1.shape[2])
-    return a2, ctx
+def _triples(seq):
+    """(conv, bn) of each Conv2d(3x3) -> BatchNorm2d -> ReLU triple at the start of a Sequential (a trailing conv without BatchNorm is
+    the caller's)."""
+    k = sum(isinstance(m, BatchNorm2d) for m in seq)
+    return [(seq[3 * i], seq[3 * i + 1]) for i in range(k)]
 
 
-def _block_backward(c, dout, G, pre, need_dx=True):
+def _block_forward(x, seq, training, sm, out=None, save=True, tail=None):
+    """Any number of Conv3x3 -> BatchNorm -> ReLU triples.  The last BatchNorm + ReLU is bn_apply into `out`, or tail(t, scale, shift) when
+    given (a fused consumer: SegNet's encoder ends pool there).  ctx keys: x, w1.., t1.., a1.. (all but the last activation), s/h/mean/invstd1.."""
+    layers = _triples(seq)
+    k = len(layers)
+    ctx = dict(x=x, training=training, k=k) if save else None
+    cur = x
+    for i, (conv, bn) in enumerate(layers, 1):
+        w = ops.hwio(conv.weight)
+        t = ops.conv_fwd(cur, w, conv.bias)
+        s, h, mean, invstd, _ = B.bn_coeff(t, bn.state(), training, sm)
+        if i < k:
+            cur = B.bn_apply(t, s, h, None, relu=True)
+        elif tail is not None:
+            cur = tail(t, s, h)
+        else:
+            cur = B.bn_apply(t, s, h, None, relu=True, out=out)
+        if save:
+            ctx.update({f"w{i}": w, f"t{i}": t, f"s{i}": s, f"h{i}": h, f"mean{i}": mean, f"invstd{i}": invstd})
+            if i == 1:
+                ctx["cin_w"] = w.shape[2]
+            if i < k:
+                ctx[f"a{i}"] = cur
+    return cur, ctx
+
+
+def _block_backward(c, dout, G, pre, need_dx=True, tail_bwd=None):
+    """Backward of _block_forward: parameter gradients (physical layouts) into G under `pre`.  tail_bwd(dout, t, mean, invstd, scale, sums,
+    shift, training) -> dt replaces the last BatchNorm + ReLU backward when the forward fused its consumer."""
     dev = dout.device
-    cout = c["w2"].shape[3]
 
     def vec(n):
         return torch.empty(n, device=dev, dtype=torch.float32)
 
-    sums2 = vec(2 * cout)
-    dt2 = B.bn_backward(dout, c["t2"], c["mean2"], c["invstd2"], c["s2"], sums2, relu_shift=c["h2"], training=c["training"])
-    G[pre + ".4.weight"], G[pre + ".4.bias"] = sums2[:cout], sums2[cout:]
-    G[pre + ".3.weight"] = ops.conv_wgrad(c["a1"], dt2, 3, 3)
-    G[pre + ".3.bias"] = B.chan_sum(dt2, vec(cout))
-    da1 = ops.conv_dgrad(dt2, c["w2"])
-    del dt2
-    sums1 = vec(2 * cout)
-    dt1 = B.bn_backward(da1, c["t1"], c["mean1"], c["invstd1"], c["s1"], sums1, relu_shift=c["h1"], out=da1, training=c["training"])
-    G[pre + ".1.weight"], G[pre + ".1.bias"] = sums1[:cout], sums1[cout:]
-    G[pre + ".0.weight"] = ops.conv_wgrad(c["x"], dt1, 3, 3, cin_w=c["cin_w"], on_side=need_dx)
-    G[pre + ".0.bias"] = B.chan_sum(dt1, vec(cout))
-    return ops.conv_dgrad(dt1, c["w1"]) if need_dx else None
+    k = c["k"]
+    d = dout
+    for i in range(k, 0, -1):
+        cout = c[f"w{i}"].shape[3]
+        sums = vec(2 * cout)
+        if i == k and tail_bwd is not None:
+            dt = tail_bwd(d, c[f"t{i}"], c[f"mean{i}"], c[f"invstd{i}"], c[f"s{i}"], sums, c[f"h{i}"], c["training"])
+        elif i == k:
+            dt = B.bn_backward(d, c[f"t{i}"], c[f"mean{i}"], c[f"invstd{i}"], c[f"s{i}"], sums, relu_shift=c[f"h{i}"], training=c["training"])
+        else:
+            dt = B.bn_backward(d, c[f"t{i}"], c[f"mean{i}"], c[f"invstd{i}"], c[f"s{i}"], sums, relu_shift=c[f"h{i}"], out=d, training=c["training"])
+        G[f"{pre}.{3 * i - 2}.weight"], G[f"{pre}.{3 * i - 2}.bias"] = sums[:cout], sums[cout:]
+        if i > 1:
+            G[f"{pre}.{3 * i - 3}.weight"] = ops.conv_wgrad(c[f"a{i - 1}"], dt, 3, 3)
+            G[f"{pre}.{3 * i - 3}.bias"] = B.chan_sum(dt, vec(cout))
+            d = ops.conv_dgrad(dt, c[f"w{i}"])
+            del dt
+        else:
+            G[f"{pre}.0.weight"] = ops.conv_wgrad(c["x"], dt, 3, 3, cin_w=c["cin_w"], on_side=need_dx)
+            G[f"{pre}.0.bias"] = B.chan_sum(dt, vec(cout))
+            return ops.conv_dgrad(dt, c["w1"]) if need_dx else None
 
 
 def _head_weights(net):

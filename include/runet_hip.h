@@ -431,6 +431,32 @@ int runet_ce_fwd(const float* logits_nchw, const long long* target, int n_img, i
 int runet_ce_bwd(const float* logits_nchw, const long long* target, const float* gout, float* dlogits_nchw, int n_img, int classes, long hw,
                  void* stream);
 
+/* ---- SegNet baseline of the reference's second comparison script (comne.py:84-211): 3x3 conv + BatchNorm2d + ReLU stacks joined by
+ *      nn.MaxPool2d(2, 2, return_indices=True) and nn.MaxUnpool2d(2, 2) (comne.py:174-175, 177-211); Conv2d(64, 1, 3) + sigmoid head =
+ *      runet_head3x3_fwd / _bwd above.  Pool index = the runet_maxpool2_fwd byte k = dy*2 + dx in the window (first maximum, NaN wins).
+ * Unpool FORWARD (comne.py:197,200,203,206 self.unpool(x, idx, output_size)) is runet_maxpool2_bwd(accumulate=0): zeros, the value at
+ *   its index - exactly nn.MaxUnpool2d's scatter (h, w = the unpooled size).
+ * runet_bn_relu_maxpool2_fwd: y, idx = maxpool2(relu(t * scale + shift)) - an encoder block's last BatchNorm + ReLU and the pool that is its
+ *   only consumer (comne.py:96-97 + 181, and :105-106 + 185, :117-118 + 189, :129-130 + 193); t is read once, the full-resolution
+ *   activation is never written.  Same values and bytes as runet_bn_apply(relu=1) followed by runet_maxpool2_fwd.  h, w: t's size.
+ * runet_bn_bwd_reduce_pooled / runet_bn_bwd_apply_pooled: runet_bn_bwd_reduce / runet_bn_bwd_apply (ReLU mask from x: relu_scale / relu_shift
+ *   are the forward's scale / shift) whose incoming gradient is the POOLED gradient dpool [n, h/2, w/2, c] with the pool's bytes idx:
+ *   g(n, y, x, c) = idx[n, y/2, x/2, c] == (y&1)*2 + (x&1) ? dpool[n, y/2, x/2, c] : 0 (autograd of :181 etc. into :96-97 etc.).
+ *   Same bits as runet_maxpool2_bwd(accumulate=0) followed by the two plain calls.  h, w: x's size; workspace as runet_bn_bwd_reduce.
+ * runet_maxunpool2_bwd: autograd of nn.MaxUnpool2d (comne.py:197,200,203,206), the gather dpool[n, ho, wo, c] = dU[n, 2ho + k/2, 2wo + k%2, c].
+ *   h, w: dU's (unpooled) size.
+ * All four: c a multiple of 4, h and w even, pixel strides multiples of 4. */
+int runet_bn_relu_maxpool2_fwd(const float* t, int ldt, const float* scale, const float* shift, float* y, int ldy, unsigned char* idx,
+                               int n_img, int h, int w, int c, void* stream);
+int runet_bn_bwd_reduce_pooled(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, int n_img, int h, int w, int c,
+                               const float* mean, const float* invstd, float* workspace, float* sums, const float* relu_scale,
+                               const float* relu_shift, void* stream);
+int runet_bn_bwd_apply_pooled(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, float* dx, int lddx, int n_img,
+                              int h, int w, int c, const float* mean, const float* invstd, const float* scale, const float* sums, long m_total,
+                              const float* relu_shift, void* stream);
+int runet_maxunpool2_bwd(const float* du, int lddu, const unsigned char* idx, float* dpool, int ldp, int n_img, int h, int w, int c,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
