@@ -790,6 +790,67 @@ def bn_backward_pooled(dpool, idx, x, mean, invstd, scale, sums, relu_shift, tra
     return dx
 
 
+# ---- LeakyReLU forms (YOLOSeg, Main_Final.py:436-510: every BatchNorm2d is followed by nn.LeakyReLU(0.1))
+# RUNET_NO_FUSED_LEAKY_POOL=1: a stage end runs runet_bn_apply_leaky + runet_maxpool2_fwd (and the full-resolution backward) instead of the
+# fused pool kernels - the A/B partner; both give the same bits.
+FUSED_LEAKY_POOL = os.environ.get("RUNET_NO_FUSED_LEAKY_POOL", "0") != "1"
+
+
+def bn_apply_leaky(x, scale, shift, slope, out=None):
+    """leaky_relu(x * scale + shift, slope) in one pass."""
+    n, h, w, c = x.shape
+    if out is None:
+        out = ops.empty_nhwc(n, h, w, c, x)
+    check(lib.runet_bn_apply_leaky(x.data_ptr(), ops.ld(x), out.data_ptr(), ops.ld(out), n * h * w, h * w, c, scale.data_ptr(), shift.data_ptr(),
+                                   float(slope), ops.stream()))
+    return out
+
+
+def bn_backward_leaky(dy, x, mean, invstd, scale, sums, shift, slope, training=True, out=None):
+    """bn_backward(relu_shift=shift) with the LeakyReLU factor (dy * slope where x * scale + shift <= 0).  sums: [2c] (dgamma | dbeta). -> dx"""
+    n, h, w, c = x.shape
+    hw = h * w
+    st = ops.stream()
+    check(lib.runet_bn_bwd_reduce_leaky(dy.data_ptr(), ops.ld(dy), x.data_ptr(), ops.ld(x), n, hw, c, mean.data_ptr(), invstd.data_ptr(),
+                                        _ws(n, hw, c, x.device).data_ptr(), sums.data_ptr(), scale.data_ptr(), shift.data_ptr(), float(slope), st))
+    use = sums if training else zeros(2 * c, x.device)
+    if out is None:
+        out = ops.empty_nhwc(n, h, w, c, x)
+    check(lib.runet_bn_bwd_apply_leaky(dy.data_ptr(), ops.ld(dy), x.data_ptr(), ops.ld(x), out.data_ptr(), ops.ld(out), n * hw, hw, c,
+                                       mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), use.data_ptr(), 0, shift.data_ptr(), float(slope), st))
+    return out
+
+
+def bn_leaky_maxpool_forward(t, scale, shift, slope):
+    """maxpool2(leaky_relu(t * scale + shift, slope)) -> (pooled, idx).  Fused: one pass, the full-resolution activation is not written."""
+    n, h, w, c = t.shape
+    if not FUSED_LEAKY_POOL:
+        return maxpool_forward(bn_apply_leaky(t, scale, shift, slope))
+    y = ops.empty_nhwc(n, h // 2, w // 2, c, t)
+    idx = torch.empty((n, h // 2, w // 2, c), device=t.device, dtype=torch.uint8)
+    check(lib.runet_bn_leaky_maxpool2_fwd(t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), float(slope), y.data_ptr(), ops.ld(y),
+                                          idx.data_ptr(), n, h, w, c, ops.stream()))
+    return y, idx
+
+
+def bn_backward_pooled_leaky(dpool, idx, x, mean, invstd, scale, sums, shift, slope, training=True):
+    """bn_backward_leaky(maxpool_backward(dpool, idx), x, ...) without the full-resolution gradient (fused), or with it
+    (RUNET_NO_FUSED_LEAKY_POOL=1).  -> dx (full resolution)"""
+    if not FUSED_LEAKY_POOL:
+        return bn_backward_leaky(maxpool_backward(dpool, idx), x, mean, invstd, scale, sums, shift, slope, training=training)
+    n, h, w, c = x.shape
+    st = ops.stream()
+    check(lib.runet_bn_bwd_reduce_pooled_leaky(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), n, h, w, c, mean.data_ptr(),
+                                               invstd.data_ptr(), _ws(n, h * w, c, x.device).data_ptr(), sums.data_ptr(), scale.data_ptr(),
+                                               shift.data_ptr(), float(slope), st))
+    use = sums if training else zeros(2 * c, x.device)
+    dx = ops.empty_nhwc(n, h, w, c, x)
+    check(lib.runet_bn_bwd_apply_pooled_leaky(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), dx.data_ptr(), ops.ld(dx), n,
+                                              h, w, c, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), use.data_ptr(), 0, shift.data_ptr(),
+                                              float(slope), st))
+    return dx
+
+
 def maxunpool_forward(x, idx):
     """nn.MaxUnpool2d(2, 2) by a 2x2 pool's winner bytes: zeros, each value at its index (= runet_maxpool2_bwd without accumulation)."""
     return maxpool_backward(x, idx)

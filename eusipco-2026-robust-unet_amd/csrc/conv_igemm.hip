@@ -50,8 +50,12 @@ struct IGemmArgs {
 // to valid addresses: their products land in output rows / columns that are never stored).  The general loader recomputes tap geometry,
 // bounds and 64-bit addresses every k-step: ~220 VALU instructions (20 of them quarter-rate integer multiplies) per 32 MFMAs, and fp32
 // MFMAs share SIMD cycles with VALU work (conv_winograd.hip) - the 1x1 forward / data-gradient launches ran at 52-69 TFLOP/s with it.
-template <int BM, int BN, int WM, int WN, bool KCONTIG, bool SIMPLE = false>
-__global__ __launch_bounds__(256, 2) void igemm_kernel(IGemmArgs g) {
+// Stats = float* (runet_convt4_igemm_stats, the k4 transposed forward of YOLOSeg's decoder): after the stores, the BatchNorm statistics
+// partials of the stored tile, stats[blockIdx.z * gridDim.x + blockIdx.x][Ncols][3] = (count, mean, M2) per column over the tile's rows.
+// The main loop and the stores are the same code either way, so y has the same bits.  Without it (the empty pack) the argument list, the
+// code and the demangled name are the kernel's as they were.
+template <int BM, int BN, int WM, int WN, bool KCONTIG, bool SIMPLE = false, typename... Stats>
+__global__ __launch_bounds__(256, 2) void igemm_kernel(IGemmArgs g, Stats... stats_arg) {
     constexpr int LDA = 20;
     constexpr int LDB = BN + 4;
     constexpr int A_ELEMS = BM * LDA;
@@ -325,7 +329,64 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IGemmArgs g) {
             }
         }
     }
+    if constexpr (sizeof...(Stats) > 0) {
+        float* const stats = (stats_arg, ...);
+        // as conv_x3_kernel's statistics epilogue: a lane holds TM * 16 rows of each of its columns -> two-pass (mean, M2) in registers,
+        // Chan-combined with the other lane half (xor 32), then through LDS over the BM / WM waves of the column in wave order.  Fixed
+        // order: bitwise reproducible.  (accumulate is 0 here: the stored value is acc + bias.)
+        constexpr int WAVES_M = BM / WM;
+        float* xch = smem;                                            // [WAVES_M][BN][3]: the stages are dead by now
+        lds_barrier();
+#pragma unroll
+        for (int b = 0; b < TN; ++b) {
+            float cnt = 0.f, s1 = 0.f;
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool ok = m0 + wm0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh < P;
+                    cnt += ok ? 1.f : 0.f;
+                    s1 += ok ? acc[a][b][r] + bv[b] : 0.f;
+                }
+            float mean = cnt > 0.f ? s1 / cnt : 0.f, m2 = 0.f;
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool ok = m0 + wm0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh < P;
+                    const float d = acc[a][b][r] + bv[b] - mean;
+                    m2 += ok ? d * d : 0.f;
+                }
+            const float cnt_o = __shfl_xor(cnt, 32, 64), mean_o = __shfl_xor(mean, 32, 64), m2_o = __shfl_xor(m2, 32, 64);
+            {
+                const float nt = cnt + cnt_o, dlt = mean_o - mean;
+                if (nt > 0.f) { m2 = m2 + m2_o + dlt * dlt * (cnt * cnt_o / nt); mean = mean + dlt * (cnt_o / nt); }
+                cnt = nt;
+            }
+            if (lh == 0) {
+                float* o = xch + ((wid / WAVES_N) * BN + wn0 + b * 32 + li) * 3;
+                o[0] = cnt; o[1] = mean; o[2] = m2;
+            }
+        }
+        lds_barrier();
+        for (int cl = tid; cl < BN; cl += 256) {
+            const int col = n0 + cl;
+            if (col < g.Ncols) {
+                float cnt = xch[cl * 3], mean = xch[cl * 3 + 1], m2 = xch[cl * 3 + 2];
+#pragma unroll
+                for (int wv = 1; wv < WAVES_M; ++wv) {
+                    const float* e = xch + (wv * BN + cl) * 3;
+                    const float nt = cnt + e[0], dlt = e[1] - mean;
+                    if (nt > 0.f) { m2 = m2 + e[2] + dlt * dlt * (cnt * e[0] / nt); mean = mean + dlt * (e[0] / nt); }
+                    cnt = nt;
+                }
+                float* o = stats + (((long)blockIdx.z * gridDim.x + blockIdx.x) * g.Ncols + col) * 3;
+                o[0] = cnt; o[1] = mean; o[2] = m2;
+            }
+        }
+    }
 }
+
 
 // ------------------------------------------------------------------------------------------ wgrad
 struct WGradArgs {
@@ -798,6 +859,19 @@ void dispatch_igemm(const IGemmArgs& a, int gz, hipStream_t st) {
     }
 }
 
+// the k4 transposed forward with the statistics epilogue: the tile variant dispatch_igemm<false> would pick (same grid, same y)
+template <int BM, int BN, int WM, int WN>
+void launch_igemm_stats(const IGemmArgs& a, int gz, float* stats, hipStream_t st) {
+    const long P = (long)a.Nimg * a.H * a.W;
+    dim3 grid(cdiv(P, BM), cdiv(a.Ncols, BN), gz);
+    const size_t lds = 2 * (BM * 20 + 16 * (BN + 4)) * sizeof(float);
+    static_assert((BM / WM) * BN * 3 <= 2 * (BM * 20 + 16 * (BN + 4)), "statistics exchange fits the stages");
+    hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, false, false, float*>), grid, dim3(256), lds, st, a, stats);
+}
+
+IGemmVariant convt4_fwd_variant(long P, int cout) { return pick_variant(P, cout, 0, false, false); }
+int variant_bm(IGemmVariant v) { return v == V_256x64 ? 256 : v == V_64x64 ? 64 : 128; }
+
 }  // namespace
 
 namespace {
@@ -1201,6 +1275,37 @@ extern "C" int runet_convt4_igemm(const float* x, int ldx, const float* w, const
         dispatch_igemm<true>(a, 1, st);
     } else {
         RUNET_REQUIRE(false, "mode must be RUNET_CONVT_FWD or RUNET_CONVT_DGRAD");
+    }
+    RUNET_CHECK_LAUNCH();
+}
+
+// runet_convt4_igemm(RUNET_CONVT_FWD) + the BatchNorm statistics partials of y for runet_bn_stats_finalize: one part per tile and parity
+// class (the tile's output pixels of one (ph, pw) class), stats [runet_convt4_igemm_stats_parts(...)][cout][3] = (count, mean, M2).
+extern "C" int runet_convt4_igemm_stats_parts(int n_img, int h, int w_, int cout) {
+    if (n_img <= 0 || h <= 0 || w_ <= 0 || cout <= 0) return 0;
+    const long P = (long)n_img * h * w_;
+    return 4 * cdiv(P, variant_bm(convt4_fwd_variant(P, cout)));
+}
+
+extern "C" int runet_convt4_igemm_stats(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int h, int w_,
+                                        int cin, int cout, float* stats, void* stream) {
+    RUNET_REQUIRE(x && w && y && stats, "null pointer");
+    RUNET_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && cin > 0 && cout > 0, "cin and cout must be positive multiples of 4");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0 && ldx >= cin && ldy >= cout, "bad shape");
+    RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
+    hipStream_t st = (hipStream_t)stream;
+    IGemmArgs a{};      // exactly runet_convt4_igemm's RUNET_CONVT_FWD arguments
+    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = 0; a.a_div = 1;
+    a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout; a.H = h; a.W = w_;
+    a.w_tap_stride = (long)cin * cout; a.w_sk = cout; a.w_sn = 1;
+    a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = 2; a.KW = 2; a.zmode4 = 1;
+    a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2;
+    switch (convt4_fwd_variant((long)n_img * h * w_, cout)) {
+    case V_128x32: launch_igemm_stats<128, 32, 32, 32>(a, 4, stats, st); break;
+    case V_256x64: launch_igemm_stats<256, 64, 64, 64>(a, 4, stats, st); break;
+    case V_128x64: launch_igemm_stats<128, 64, 64, 32>(a, 4, stats, st); break;
+    case V_128x128: launch_igemm_stats<128, 128, 64, 64>(a, 4, stats, st); break;
+    case V_64x64: launch_igemm_stats<64, 64, 32, 32>(a, 4, stats, st); break;
     }
     RUNET_CHECK_LAUNCH();
 }

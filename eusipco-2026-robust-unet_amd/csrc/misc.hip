@@ -76,7 +76,11 @@ __global__ __launch_bounds__(TPB) void maxpool2_bwd_kernel(const float* __restri
 // ---- BatchNorm (per-channel affine) + ReLU + 2x2 max pool in one pass (SegNet encoder ends): t is read once, only the pooled values and
 // the winner bytes are written.  The window compares the post-affine, post-ReLU values with bn_apply_kernel's own expressions (bn_pre, then
 // fmaxf with 0, then the unit dropout factor), so values and bytes equal runet_bn_apply(relu=1) followed by runet_maxpool2_fwd.
-__global__ __launch_bounds__(TPB) void bn_relu_maxpool2_fwd_kernel(const float* __restrict__ t, int ldt, const float* __restrict__ scale,
+// ACT_LEAKY (YOLOSeg's BatchNorm + LeakyReLU + pool): the window compares z > 0 ? z : z * slope (runet_bn_apply_leaky's expression) and
+// `unit` carries the slope.  The ACT_RELU instance is the kernel as it was.
+enum { ACT_RELU = 0, ACT_LEAKY = 1 };
+template <int ACT = ACT_RELU>
+__global__ __launch_bounds__(TPB) void bn_act_maxpool2_fwd_kernel(const float* __restrict__ t, int ldt, const float* __restrict__ scale,
                                                                    const float* __restrict__ shift, float* __restrict__ y, int ldy,
                                                                    unsigned char* __restrict__ idx, int N, int Ho, int Wo, int C,
                                                                    float unit) {
@@ -97,7 +101,14 @@ __global__ __launch_bounds__(TPB) void bn_relu_maxpool2_fwd_kernel(const float* 
         auto act = [&](long q) {
             f32x4 v = *reinterpret_cast<const f32x4*>(t + q * ldt + c);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(bn_pre(v[e], sc[e], sh[e]), 0.f) * unit;
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (ACT == ACT_LEAKY) {
+                    const float z = bn_pre(v[e], sc[e], sh[e]);
+                    v[e] = z > 0.f ? z : z * unit;
+                } else {
+                    v[e] = fmaxf(bn_pre(v[e], sc[e], sh[e]), 0.f) * unit;
+                }
+            }
             return v;
         };
         f32x4 m = act(ip);
@@ -274,8 +285,20 @@ extern "C" int runet_bn_relu_maxpool2_fwd(const float* t, int ldt, const float* 
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ldt >= c && ldy >= c && ldt % 4 == 0 && ldy % 4 == 0, "bad shape");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
     // unit: the dropout factor bn_apply_kernel multiplies by when no mask is given, passed at run time so the product stays in the code
-    hipLaunchKernelGGL(bn_relu_maxpool2_fwd_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
+    hipLaunchKernelGGL(bn_act_maxpool2_fwd_kernel<ACT_RELU>, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
                        n_img, h / 2, w / 2, c, 1.0f);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_leaky_maxpool2_fwd(const float* t, int ldt, const float* scale, const float* shift, float slope, float* y, int ldy,
+                                           unsigned char* idx, int n_img, int h, int w, int c, void* stream) {
+    RUNET_REQUIRE(t && scale && shift && y && idx, "null pointer");
+    RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ldt >= c && ldy >= c && ldt % 4 == 0 && ldy % 4 == 0, "bad shape");
+    RUNET_REQUIRE(((uintptr_t)t % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
+    const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
+    hipLaunchKernelGGL(bn_act_maxpool2_fwd_kernel<ACT_LEAKY>, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
+                       n_img, h / 2, w / 2, c, slope);
     RUNET_CHECK_LAUNCH();
 }
 

@@ -299,10 +299,21 @@ __global__ __launch_bounds__(TPB) void chan_stats_finalize_kernel(const float* _
 
 // Streaming kernels use a division-free layout: grid (chunks, images); a thread owns VEC consecutive channels (its per-channel
 // coefficients live in registers) and every `rows`-th pixel of its chunk, so the inner loop is loads, FMAs and one pointer add.
-template <int VEC>
-__global__ __launch_bounds__(TPB) void bn_apply_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
-                                                       int HW, int C, int pix_per_chunk, const float* __restrict__ scale,
-                                                       const float* __restrict__ shift, const float* __restrict__ mask, int relu) {
+// The activation behind a BatchNorm is a compile-time choice: ACT_RELU (the U-Net family: ReLU, optionally times a Dropout2d factor) or
+// ACT_LEAKY (YOLOSeg: LeakyReLU with a run-time slope).  The ACT_RELU forms are the kernels as they were (same code).  LeakyReLU is NOT ReLU
+// with slope 0 (that gives -0.0 for negative inputs): leaky_act is aten's expression z > 0 ? z : z * slope (the product in fp32, the slope
+// a float) and leaky_grad its backward g * (z > 0 ? 1 : slope), z always bn_pre's, so the backward's decision is the forward's.
+enum { ACT_RELU = 0, ACT_LEAKY = 1 };
+__device__ __forceinline__ float leaky_act(const float z, const float slope) { return z > 0.f ? z : z * slope; }
+__device__ __forceinline__ float leaky_grad(const float g, const float z, const float slope) { return z > 0.f ? g : g * slope; }
+// the ACT_LEAKY instances of the backward kernels have no Dropout2d mask and take the slope in its argument slot
+template <int ACT> struct MaskArg { typedef const float* __restrict__ type; };
+template <> struct MaskArg<ACT_LEAKY> { typedef float type; };
+
+template <int VEC, int ACT>
+__device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, int HW, int C,
+                                              int pix_per_chunk, const float* __restrict__ scale, const float* __restrict__ shift,
+                                              const float* __restrict__ mask, int relu, float slope) {
     const int cvec = C / VEC, rows = TPB / cvec, tid = threadIdx.x;
     const int col = tid % cvec, row = tid / cvec;
     if (row >= rows) return;
@@ -324,14 +335,31 @@ __global__ __launch_bounds__(TPB) void bn_apply_kernel(const float* __restrict__
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
             float r = bn_pre(v[q], sc[q], sh[q]);
-            if (relu) r = fmaxf(r, 0.f);
-            v[q] = r * mk[q];
+            if constexpr (ACT == ACT_LEAKY) {
+                v[q] = leaky_act(r, slope);
+            } else {
+                if (relu) r = fmaxf(r, 0.f);
+                v[q] = r * mk[q];
+            }
         }
         if constexpr (VEC == 4) {
             f32x4 t = {v[0], v[1], v[2], v[3]};
             *reinterpret_cast<f32x4*>(y + (ib + p) * ldy + col * 4) = t;
         } else y[(ib + p) * ldy + col] = v[0];
     }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(TPB) void bn_apply_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
+                                                       int HW, int C, int pix_per_chunk, const float* __restrict__ scale,
+                                                       const float* __restrict__ shift, const float* __restrict__ mask, int relu) {
+    bn_apply_body<VEC, ACT_RELU>(x, ldx, y, ldy, HW, C, pix_per_chunk, scale, shift, mask, relu, 0.f);
+}
+template <int VEC>
+__global__ __launch_bounds__(TPB) void bn_apply_leaky_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
+                                                             int HW, int C, int pix_per_chunk, const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, float slope) {
+    bn_apply_body<VEC, ACT_LEAKY>(x, ldx, y, ldy, HW, C, pix_per_chunk, scale, shift, nullptr, 1, slope);
 }
 
 // The incoming gradient of a 2x2 max-pool (POOL): dy is the POOLED gradient [n, H/2, W/2] (pixel stride lddy) and pidx its winner bytes
@@ -351,12 +379,12 @@ __device__ __forceinline__ f32x4 pooled_grad4(const float* __restrict__ dy, int 
     return g;
 }
 
-// partial sums of g and g*xhat per channel; g = dy [* mask[n,c] * (act > 0)]
-template <int VEC, bool POOL = false>
+// partial sums of g and g*xhat per channel; g = dy [* mask[n,c] * (act > 0)]   (ACT_LEAKY: leaky_grad(dy, x * rscale + rshift, slope))
+template <int VEC, bool POOL = false, int ACT = ACT_RELU>
 __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __restrict__ dy, int lddy, const float* __restrict__ x,
                                                              int ldx, const float* __restrict__ act, int ldact, int HW, int C,
                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                             const float* __restrict__ mask, int pix_per_chunk,
+                                                             typename MaskArg<ACT>::type mask, int pix_per_chunk,
                                                              float* __restrict__ part, const float* __restrict__ rscale,
                                                              const float* __restrict__ rshift) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -366,7 +394,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
     const int p0 = chunk * pix_per_chunk, p1 = min(HW, p0 + pix_per_chunk);
     const unsigned char* pidx = POOL ? reinterpret_cast<const unsigned char*>(act) : nullptr;
     const int W = POOL ? ldact : 0;
-    if constexpr (POOL) act = nullptr;
+    if constexpr (POOL || ACT == ACT_LEAKY) act = nullptr;
     // ReLU(+Dropout2d) backward: either from the saved activation (act > 0) or, when rscale/rshift are given, recomputed from x with
     // the forward's own expression x*scale + shift > 0 - one tensor less to read
     const bool recompute = rscale != nullptr;
@@ -377,7 +405,8 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
         const int c = col * VEC + q;
         const bool ok = row < rows;
         mu[q] = ok ? mean[c] : 0.f; is[q] = ok ? invstd[c] : 0.f;
-        mk[q] = (ok && mask) ? mask[(long)n * C + c] : 1.f;
+        if constexpr (ACT == ACT_LEAKY) mk[q] = 1.f;
+        else mk[q] = (ok && mask) ? mask[(long)n * C + c] : 1.f;
         fs[q] = (ok && recompute) ? rscale[c] : 0.f; fh[q] = (ok && recompute) ? rshift[c] : 0.f;
     }
     if (row < rows) {
@@ -403,7 +432,8 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
 #pragma unroll
             for (int q = 0; q < VEC; ++q) {
                 float gg = g[q];
-                if (act) gg = (av[q] > 0.f) ? gg * mk[q] : 0.f;
+                if constexpr (ACT == ACT_LEAKY) gg = leaky_grad(gg, bn_pre(xv[q], fs[q], fh[q]), mask);
+                else if (act) gg = (av[q] > 0.f) ? gg * mk[q] : 0.f;
                 else if (recompute) gg = (bn_pre(xv[q], fs[q], fh[q]) > 0.f) ? gg * mk[q] : 0.f;
                 sg[q] += gg;
                 sgx[q] += gg * (xv[q] - mu[q]) * is[q];
@@ -453,12 +483,12 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_final(const float* __restri
     }
 }
 
-template <int VEC, bool POOL = false>
+template <int VEC, bool POOL = false, int ACT = ACT_RELU>
 __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x,
                                                            int ldx, const float* __restrict__ act, int ldact, float* __restrict__ dx,
                                                            int lddx, int HW, int C, int pix_per_chunk, const float* __restrict__ mean,
                                                            const float* __restrict__ invstd, const float* __restrict__ scale,
-                                                           const float* __restrict__ sums, const float* __restrict__ mask, float inv_m,
+                                                           const float* __restrict__ sums, typename MaskArg<ACT>::type mask, float inv_m,
                                                            const float* __restrict__ rshift) {
     const int cvec = C / VEC, rows = TPB / cvec, tid = threadIdx.x;
     const int col = tid % cvec, row = tid / cvec;
@@ -467,7 +497,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
     const int p0 = blockIdx.x * pix_per_chunk, p1 = min(HW, p0 + pix_per_chunk);
     const unsigned char* pidx = POOL ? reinterpret_cast<const unsigned char*>(act) : nullptr;
     const int W = POOL ? ldact : 0;
-    if constexpr (POOL) act = nullptr;
+    if constexpr (POOL || ACT == ACT_LEAKY) act = nullptr;
     // dx = sc*(g - k1 - xhat*k2) = g*sc + x*a + b  with a = -sc*k2*invstd, b = sc*(mean*invstd*k2 - k1)
     const bool recompute = rshift != nullptr;        // ReLU mask from x*scale + shift > 0 (scale IS the forward scale) instead of act > 0
     float sc[VEC], ca[VEC], cb[VEC], mk[VEC], fh[VEC];
@@ -476,7 +506,8 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
         const int c = col * VEC + q;
         sc[q] = scale[c];
         bn_bwd_coef(sc[q], mean[c], invstd[c], sums[c], sums[C + c], inv_m, ca[q], cb[q]);
-        mk[q] = mask ? mask[(long)n * C + c] : 1.f;
+        if constexpr (ACT == ACT_LEAKY) mk[q] = 1.f;
+        else mk[q] = mask ? mask[(long)n * C + c] : 1.f;
         fh[q] = recompute ? rshift[c] : 0.f;
     }
     const long ib = (long)n * HW;
@@ -501,7 +532,8 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
             float gg = g[q];
-            if (act) gg = (av[q] > 0.f) ? gg * mk[q] : 0.f;
+            if constexpr (ACT == ACT_LEAKY) gg = leaky_grad(gg, bn_pre(xv[q], sc[q], fh[q]), mask);
+            else if (act) gg = (av[q] > 0.f) ? gg * mk[q] : 0.f;
             else if (recompute) gg = (bn_pre(xv[q], sc[q], fh[q]) > 0.f) ? gg * mk[q] : 0.f;
             r[q] = bn_bwd_dx(gg, sc[q], xv[q], ca[q], cb[q]);
         }
@@ -779,5 +811,96 @@ extern "C" int runet_bn_bwd_apply_pooled(const float* dpool, int ldp, const unsi
     const int chunks = stream_chunks(n_img, hw, c, TPB / (c / 4), ppc);
     hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true>), dim3(chunks, n_img), dim3(TPB), 0, st, dpool, ldp, x, ldx,
                        reinterpret_cast<const float*>(idx), w, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, nullptr, inv_m, relu_shift);
+    RUNET_CHECK_LAUNCH();
+}
+
+// ---- LeakyReLU(slope) forms of the BatchNorm kernels (YOLOSeg: every BatchNorm2d is followed by nn.LeakyReLU(0.1)).  The backward ones
+// recompute the factor from x with the forward's scale / shift (the relu_scale / relu_shift form of the ReLU entries).  Same launch
+// geometry and summation order as the ReLU entries; the ACT_LEAKY instances of the same kernels.
+extern "C" int runet_bn_apply_leaky(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale, const float* shift,
+                                    float slope, void* stream) {
+    RUNET_REQUIRE(x && y && scale && shift, "null pointer");
+    REQ_VEC(c);
+    RUNET_REQUIRE(pixels > 0 && hw > 0 && ldx >= c && ldy >= c, "bad shape");
+    RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
+    hipStream_t st = (hipStream_t)stream;
+    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
+    int ppc;
+    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
+    if (vec == 4) hipLaunchKernelGGL((bn_apply_leaky_kernel<4>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift, slope);
+    else hipLaunchKernelGGL((bn_apply_leaky_kernel<1>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift, slope);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_bwd_reduce_leaky(const float* dy, int lddy, const float* x, int ldx, int n_img, int hw, int c, const float* mean,
+                                         const float* invstd, float* workspace, float* sums, const float* scale, const float* shift, float slope,
+                                         void* stream) {
+    RUNET_REQUIRE(dy && x && mean && invstd && workspace && sums && scale && shift, "null pointer");
+    REQ_VEC(c);
+    RUNET_REQUIRE(n_img > 0 && hw > 0 && lddy >= c && ldx >= c, "bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    const int vec = (c % 4 == 0) ? 4 : 1, rows = TPB / (c / vec);
+    const int chunks = pick_chunks(n_img, hw, c, rows);
+    const int ppc = (hw + chunks - 1) / chunks;
+    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
+    dim3 grid(chunks, n_img);
+    if (vec == 4) hipLaunchKernelGGL((bn_bwd_reduce_partial<4, false, ACT_LEAKY>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, slope, ppc, workspace, scale, shift);
+    else hipLaunchKernelGGL((bn_bwd_reduce_partial<1, false, ACT_LEAKY>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, slope, ppc, workspace, scale, shift);
+    const int cw = final_cw(c, (long)chunks * n_img);
+    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_bwd_apply_leaky(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, long pixels, int hw, int c,
+                                        const float* mean, const float* invstd, const float* scale, const float* sums, long m_total, const float* shift,
+                                        float slope, void* stream) {
+    RUNET_REQUIRE(dy && x && dx && mean && invstd && scale && sums && shift, "null pointer");
+    REQ_VEC(c);
+    RUNET_REQUIRE(pixels > 0 && hw > 0 && lddy >= c && ldx >= c && lddx >= c, "bad shape");
+    RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
+    hipStream_t st = (hipStream_t)stream;
+    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
+    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
+    int ppc;
+    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
+    if (vec == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<4, false, ACT_LEAKY>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, slope, inv_m, shift);
+    else hipLaunchKernelGGL((bn_bwd_apply_kernel<1, false, ACT_LEAKY>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, slope, inv_m, shift);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_bwd_reduce_pooled_leaky(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, int n_img, int h,
+                                                int w, int c, const float* mean, const float* invstd, float* workspace, float* sums,
+                                                const float* scale, const float* shift, float slope, void* stream) {
+    RUNET_REQUIRE(dpool && idx && x && mean && invstd && workspace && sums && scale && shift, "null pointer");
+    REQ_POOLED(h, w, c);
+    RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && ldp % 4 == 0 && ldx % 4 == 0, "bad shape");
+    RUNET_REQUIRE(((uintptr_t)dpool % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
+    hipStream_t st = (hipStream_t)stream;
+    const int hw = h * w, rows = TPB / (c / 4);
+    const int chunks = pick_chunks(n_img, hw, c, rows);
+    const int ppc = (hw + chunks - 1) / chunks;
+    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
+    hipLaunchKernelGGL((bn_bwd_reduce_partial<4, true, ACT_LEAKY>), dim3(chunks, n_img), dim3(TPB), lds, st, dpool, ldp, x, ldx,
+                       reinterpret_cast<const float*>(idx), w, hw, c, mean, invstd, slope, ppc, workspace, scale, shift);
+    const int cw = final_cw(c, (long)chunks * n_img);
+    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_bwd_apply_pooled_leaky(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, float* dx, int lddx,
+                                               int n_img, int h, int w, int c, const float* mean, const float* invstd, const float* scale,
+                                               const float* sums, long m_total, const float* shift, float slope, void* stream) {
+    RUNET_REQUIRE(dpool && idx && x && dx && mean && invstd && scale && sums && shift, "null pointer");
+    REQ_POOLED(h, w, c);
+    RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && lddx >= c && ldp % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, "bad shape");
+    RUNET_REQUIRE(((uintptr_t)dpool % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dx % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
+    hipStream_t st = (hipStream_t)stream;
+    const long pixels = (long)n_img * h * w;
+    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
+    const int hw = h * w;
+    int ppc;
+    const int chunks = stream_chunks(n_img, hw, c, TPB / (c / 4), ppc);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true, ACT_LEAKY>), dim3(chunks, n_img), dim3(TPB), 0, st, dpool, ldp, x, ldx,
+                       reinterpret_cast<const float*>(idx), w, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, slope, inv_m, shift);
     RUNET_CHECK_LAUNCH();
 }

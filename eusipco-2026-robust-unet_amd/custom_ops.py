@@ -9,6 +9,9 @@ hand-written data-gradient / weight-gradient kernels.
     torch.ops.runet.maxpool2_nhwc(x) -> (y, idx)                 MaxPool2d(2) with the argmax byte  (+ maxpool2_nhwc_bwd)
     torch.ops.runet.maxunpool2_nhwc(x, idx)                      MaxUnpool2d(2, 2) by those bytes (comne.py:177-211); backward = the gather
     torch.ops.runet.bn_relu_maxpool2_nhwc(t, scale, shift)       maxpool2(relu(t * scale + shift)) in one pass -> (y, idx); forward only
+    torch.ops.runet.bn_leaky_maxpool2_nhwc(t, scale, shift, negative_slope)
+                                                                 maxpool2(leaky_relu(t * scale + shift)) -> (y, idx) (Main_Final.py:436-510)
+                                                                 (+ bn_leaky_maxpool2_nhwc_bwd)
     torch.ops.runet.bce_loss(prob, target)                       nn.BCELoss() mean, ATen clamp semantics (Main_Final.py:551)
     torch.ops.runet.cross_entropy(logits, target)                nn.CrossEntropyLoss() mean (train_water_segmentation.py:304)
     torch.ops.runet.seg_counts(pred, target, threshold)          per-image tp / predicted / target / agreement counts (Main_Final.py:519-547)
@@ -231,6 +234,54 @@ def _(t, scale, shift):
     return t.new_empty((n, h // 2, w // 2, c)), t.new_empty((n, h // 2, w // 2, c), dtype=torch.uint8)
 
 
+@custom_op("runet::bn_leaky_maxpool2_nhwc", mutates_args=(), device_types=_DEV)
+def bn_leaky_maxpool2_nhwc(t: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, negative_slope: float) -> tuple[torch.Tensor, torch.Tensor]:
+    _chk_nhwc(t)
+    from . import blocks
+    return blocks.bn_leaky_maxpool_forward(t.contiguous(), scale.contiguous(), shift.contiguous(), negative_slope)
+
+
+@bn_leaky_maxpool2_nhwc.register_fake
+def _(t, scale, shift, negative_slope):
+    n, h, w, c = t.shape
+    return t.new_empty((n, h // 2, w // 2, c)), t.new_empty((n, h // 2, w // 2, c), dtype=torch.uint8)
+
+
+@custom_op("runet::bn_leaky_maxpool2_nhwc_bwd", mutates_args=(), device_types=_DEV)
+def bn_leaky_maxpool2_nhwc_bwd(dy: torch.Tensor, idx: torch.Tensor, t: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                               negative_slope: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (dt, dscale, dshift): the pooled-gradient LeakyReLU BatchNorm kernels with mean 0, invstd 1 (so xhat = t) and no batch-statistics
+    terms: dt = g * scale, dscale = sum g * t, dshift = sum g, g = leaky'(t * scale + shift) * the scattered dy."""
+    from . import blocks
+    c = t.shape[3]
+    sums = torch.empty(2 * c, device=t.device, dtype=torch.float32)
+    zero, one = torch.zeros(c, device=t.device), torch.ones(c, device=t.device)
+    dt = blocks.bn_backward_pooled_leaky(dy.contiguous(), idx.contiguous(), t.contiguous(), zero, one, scale.contiguous(), sums, shift.contiguous(),
+                                         negative_slope, training=False)
+    return dt, sums[:c].clone(), sums[c:].clone()
+
+
+@bn_leaky_maxpool2_nhwc_bwd.register_fake
+def _(dy, idx, t, scale, shift, negative_slope):
+    c = t.shape[3]
+    return t.new_empty(t.shape), t.new_empty((c,)), t.new_empty((c,))
+
+
+def _leaky_pool_setup(ctx, inputs, output):
+    t, scale, shift, slope = inputs
+    ctx.save_for_backward(t, scale, shift, output[1])
+    ctx.slope = slope
+
+
+def _leaky_pool_bwd(ctx, dy, _didx):
+    t, scale, shift, idx = ctx.saved_tensors
+    dt, dscale, dshift = torch.ops.runet.bn_leaky_maxpool2_nhwc_bwd(dy.contiguous(), idx, t, scale, shift, ctx.slope)
+    return dt, dscale, dshift, None
+
+
+register_autograd("runet::bn_leaky_maxpool2_nhwc", _leaky_pool_bwd, setup_context=_leaky_pool_setup)
+
+
 # ------------------------------------------------------------------------------------------------ losses / metrics / resize
 @custom_op("runet::bce_loss", mutates_args=(), device_types=_DEV)
 def bce_loss(prob: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -346,4 +397,5 @@ register_autograd("runet::bilinear_resize", _bil_bwd, setup_context=_bil_setup)
 
 OPS = ("conv2d_nhwc", "conv2d_nhwc_dgrad", "conv2d_nhwc_wgrad", "convt2x2s2_nhwc", "convt2x2s2_nhwc_dgrad", "convt2x2s2_nhwc_wgrad",
        "maxpool2_nhwc", "maxpool2_nhwc_bwd", "bce_loss", "bce_loss_bwd", "cross_entropy", "cross_entropy_bwd", "seg_counts",
-       "bilinear_resize", "bilinear_resize_bwd", "maxunpool2_nhwc", "maxunpool2_nhwc_bwd", "bn_relu_maxpool2_nhwc")
+       "bilinear_resize", "bilinear_resize_bwd", "maxunpool2_nhwc", "maxunpool2_nhwc_bwd", "bn_relu_maxpool2_nhwc",
+       "bn_leaky_maxpool2_nhwc", "bn_leaky_maxpool2_nhwc_bwd")

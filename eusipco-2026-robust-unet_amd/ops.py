@@ -1018,11 +1018,19 @@ def conv_general_wgrad(x, dy, kh, kw, stride, pad, dil=1, cin_w=None, out=None):
     return out
 
 
-def convt4_fwd(x, w_hwio, bias, out=None):
+def convt4_fwd(x, w_hwio, bias, out=None, stats=None):
+    """ConvTranspose2d(k4, s2, p1).  stats: dict that receives the BatchNorm statistics partials of the output (runet_convt4_igemm_stats,
+    see conv_fwd's `stats`); left empty under RUNET_NO_EPILOGUE_STATS=1 and for fewer than 32 output channels, where the epilogue was measured
+    slower than the separate pass (YOLOSeg's last transposed conv, 32 -> 16 at 128^2: 195 vs 186 us)."""
     n, h, w, cin = x.shape
     cout = w_hwio.shape[3]
     if out is None:
         out = empty_nhwc(n, 2 * h, 2 * w, cout, x)
+    if stats is not None and EPILOGUE_STATS and cout >= 32:
+        sp = _stats_buf(stats, lib.runet_convt4_igemm_stats_parts(n, h, w, cout), cout, x.device)
+        check(lib.runet_convt4_igemm_stats(x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
+                                           ld(out), n, h, w, cin, cout, sp, stream()))
+        return out
     check(lib.runet_convt4_igemm(x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out),
                                  n, h, w, cin, cout, CONVT_FWD, 0, stream()))
     return out

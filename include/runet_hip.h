@@ -457,6 +457,42 @@ int runet_bn_bwd_apply_pooled(const float* dpool, int ldp, const unsigned char* 
 int runet_maxunpool2_bwd(const float* du, int lddu, const unsigned char* idx, float* dpool, int ldp, int n_img, int h, int w, int c,
                          void* stream);
 
+/* ---- YOLOSeg baseline (Main_Final.py:436-510): every BatchNorm2d is followed by nn.LeakyReLU(0.1, inplace=True); the backbone's four
+ *      stages end in nn.MaxPool2d(2, stride=2) (:446, :452, :464, :476); seg_head is four ConvTranspose2d(k4, s2, p1) + BatchNorm2d +
+ *      LeakyReLU (:481-498) and Conv2d(16, 1, 3) + sigmoid (runet_head3x3_fwd / _bwd above, :501, :506).
+ * LeakyReLU(slope): act(z) = z > 0 ? z : z * slope with z = x * scale + shift (runet_bn_apply's fused multiply-add), the product in fp32 -
+ *   the same bits as torch.nn.functional.leaky_relu(z, slope).  Not ReLU with slope 0 (that gives -0.0 for negative z).
+ * runet_bn_apply_leaky: y = act(x * scale + shift) - runet_bn_apply(relu=0) followed by leaky_relu, in one pass.
+ * runet_bn_bwd_reduce_leaky / runet_bn_bwd_apply_leaky: runet_bn_bwd_reduce / _apply of g = dy * (z > 0 ? 1 : slope), z recomputed from x
+ *   with the forward's scale / shift (bitwise the forward's decision): the same bits as aten's leaky_relu backward on z followed by the plain
+ *   calls (no act, no relu_scale / relu_shift).  Workspace, sums and m_total as there.
+ * runet_bn_leaky_maxpool2_fwd: y, idx = maxpool2(act(t * scale + shift)) - a backbone stage's last BatchNorm + LeakyReLU and the pool
+ *   that is its only consumer (:444-446, :450-452, :462-464, :474-476); t is read once, the full-resolution activation is never written.
+ *   Same values and bytes as runet_bn_apply_leaky followed by runet_maxpool2_fwd (byte k = dy*2 + dx, first maximum, NaN wins).
+ * runet_bn_bwd_reduce_pooled_leaky / runet_bn_bwd_apply_pooled_leaky: the LeakyReLU forms of runet_bn_bwd_reduce_pooled / _apply_pooled
+ *   (pooled gradient + the pool's bytes, factor from x): the same bits as runet_maxpool2_bwd(accumulate=0) + the two calls above.
+ * Pooled forms: c a multiple of 4, h and w (t's / x's size) even, pixel strides multiples of 4, tensors 16-byte and idx 4-byte aligned.
+ * runet_convt4_igemm_stats: runet_convt4_igemm(RUNET_CONVT_FWD, accumulate 0) that also leaves the BatchNorm statistics partials of y
+ *   for runet_bn_stats_finalize, stats [runet_convt4_igemm_stats_parts(n_img, h, w_, cout)][cout][3] = (count, mean, M2) per tile and
+ *   output parity class; y has the same bits as the plain call.  h, w_: x's size. */
+int runet_bn_apply_leaky(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale, const float* shift,
+                         float slope, void* stream);
+int runet_bn_bwd_reduce_leaky(const float* dy, int lddy, const float* x, int ldx, int n_img, int hw, int c, const float* mean, const float* invstd,
+                              float* workspace, float* sums, const float* scale, const float* shift, float slope, void* stream);
+int runet_bn_bwd_apply_leaky(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, long pixels, int hw, int c, const float* mean,
+                             const float* invstd, const float* scale, const float* sums, long m_total, const float* shift, float slope, void* stream);
+int runet_bn_leaky_maxpool2_fwd(const float* t, int ldt, const float* scale, const float* shift, float slope, float* y, int ldy, unsigned char* idx,
+                                int n_img, int h, int w, int c, void* stream);
+int runet_bn_bwd_reduce_pooled_leaky(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, int n_img, int h, int w, int c,
+                                     const float* mean, const float* invstd, float* workspace, float* sums, const float* scale, const float* shift,
+                                     float slope, void* stream);
+int runet_bn_bwd_apply_pooled_leaky(const float* dpool, int ldp, const unsigned char* idx, const float* x, int ldx, float* dx, int lddx, int n_img,
+                                    int h, int w, int c, const float* mean, const float* invstd, const float* scale, const float* sums, long m_total,
+                                    const float* shift, float slope, void* stream);
+int runet_convt4_igemm_stats_parts(int n_img, int h, int w_, int cout);
+int runet_convt4_igemm_stats(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int h, int w_, int cin,
+                             int cout, float* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
