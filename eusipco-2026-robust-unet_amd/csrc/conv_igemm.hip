@@ -1220,17 +1220,21 @@ extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ld
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // General (strided / large-kernel / k4 transposed) convolutions for the DeepLabV3+ baseline (/root/reference/Main_Final.py:325-433:
-// Conv2d 7x7 s2 p3, 3x3 s2 p1, 3x3 dilation 6/12/18, ConvTranspose2d k4 s2 p1).  Same kernels, other geometry.
+// Conv2d 7x7 s2 p3, 3x3 s2 p1, 3x3 dilation 6/12/18, ConvTranspose2d k4 s2 p1) and SegFormer-Lite (Extended_Baseline_Comparison.py:645,
+// 677-688: Conv2d 7x7 s4 p3 and the key / value reductions, kernel = stride = 8, 4, 2, no padding).  Same kernels, other geometry: kernels
+// up to 8x8, strides up to 8.
 extern "C" int runet_conv2d_general(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int hin,
                                     int win, int cin, int cin_w, int cout, int kh, int kw, int stride, int pad, int dil, int mode,
                                     int accumulate, void* stream) {
     RUNET_REQUIRE(x && w && y, "null pointer");
     RUNET_REQUIRE(cin > 0 && cin % 4 == 0 && cin_w > 0 && cin_w <= cin && cout > 0 && cout % 4 == 0, "channel counts must be multiples of 4");
-    RUNET_REQUIRE(kh >= 1 && kh <= 7 && kw >= 1 && kw <= 7 && stride >= 1 && stride <= 2 && pad >= 0 && dil >= 1, "unsupported geometry");
+    RUNET_REQUIRE(kh >= 1 && kh <= 8 && kw >= 1 && kw <= 8 && stride >= 1 && stride <= 8 && pad >= 0 && dil >= 1, "unsupported geometry");
     RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
     const int ho = (hin + 2 * pad - dil * (kh - 1) - 1) / stride + 1, wo = (win + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
     RUNET_REQUIRE(ho > 0 && wo > 0, "empty output");
     hipStream_t st = (hipStream_t)stream;
+    // measurement knob (tools/segformer_step.py --kernels): the kernel = stride data gradient through the general a_div form below
+    static const bool no_live_tap = getenv("RUNET_NO_LIVE_TAP_DGRAD") && atoi(getenv("RUNET_NO_LIVE_TAP_DGRAD")) != 0;
     IGemmArgs a{};
     a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = accumulate; a.KH = kh; a.KW = kw;
     a.a_div = 1; a.o_scale = 1;
@@ -1241,6 +1245,18 @@ extern "C" int runet_conv2d_general(const float* x, int ldx, const float* w, con
         a.H = ho; a.W = wo; a.Hin = hin; a.Win = win; a.a_scale = stride; a.tdh = dil; a.tdw = dil; a.bh = -pad; a.bw = -pad;
         a.Hout = ho; a.Wout = wo;
         dispatch_igemm<false>(a, 1, st);
+    } else if (mode == RUNET_CONV_DGRAD && kh == stride && kw == stride && stride > 1 && pad == 0 && dil == 1 && hin == ho * stride &&
+               win == wo * stride && !no_live_tap) {
+        // kernel = stride, no padding (SegFormer-Lite's key / value reductions): each dx pixel has exactly one live tap, the one at its position
+        // modulo the stride, so the data gradient is s^2 GEMMs dy [pixels, cin] . w_tap^T [cin, cout] whose rows land on the pixels
+        // (h * s + r, w * s + c) of tap (r, c) = blockIdx.z: a GEMM plus a permutation, the k2-s2 transposed forward's z_taps form.  The general
+        // form below would run all s^2 taps through the matrix loop for every pixel (a_div masking), s^2 - 1 of them dead.
+        RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
+        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
+        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
+        a.H = ho; a.W = wo; a.Hin = ho; a.Win = wo; a.a_scale = 1; a.KH = 1; a.KW = 1;
+        a.Hout = hin; a.Wout = win; a.o_scale = stride; a.z_taps = stride;
+        dispatch_igemm<true>(a, stride * stride, st);
     } else if (mode == RUNET_CONV_DGRAD) { // x := dy [n,ho,wo,cin(=conv Cout)] -> y := dx [n,hin,win,cout(=conv Cin)]; w [kh,kw,cout,cin]
         RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
         a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
@@ -1322,6 +1338,7 @@ extern "C" int runet_conv_wgrad_general(const float* x, int ldx, const float* dy
                                         int transposed4, void* stream) {
     RUNET_REQUIRE(x && dy && dw, "null pointer");
     RUNET_REQUIRE(cin % 4 == 0 && cin_w > 0 && cin_w <= cin && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "channel counts / strides must be multiples of 4");
+    RUNET_REQUIRE(transposed4 || (kh >= 1 && kh <= 8 && kw >= 1 && kw <= 8 && stride >= 1 && stride <= 8 && pad >= 0 && dil >= 1), "unsupported geometry");
     hipStream_t st = (hipStream_t)stream;
     WGradArgs a{};
     a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy; a.Kci = cin; a.Kvalid = cin_w; a.Nco = cout; a.Nimg = n_img; a.KH = kh; a.KW = kw;

@@ -669,14 +669,6 @@ extern "C" int runet_add_inplace(float* dst, const float* src, long n, void* str
 // Harness helpers: bilinear resize of the probability map when output and mask sizes differ (/root/reference/Main_Final.py:577-578,
 // 596-597,648-649; ATen upsample_bilinear2d, align_corners=False) and the per-pixel product of the standalone SpatialAttention (:117).
 namespace {
-__device__ __forceinline__ void bilin_src(int o, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
-    float src = scale * ((float)o + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    i0 = (int)src;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    l0 = 1.f - l1;
-}
 __global__ __launch_bounds__(TPB) void bilinear_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long planes, int H, int W, int Ho,
                                                            int Wo, float sh, float sw) {
     const long total = planes * Ho * Wo;
@@ -702,10 +694,9 @@ __global__ __launch_bounds__(TPB) void bilinear_bwd_kernel(const float* __restri
         const int iy = (int)(t % H);
         const float* gp = dy + (t / H) * Ho * Wo;
         // candidate outputs: src in (i - 1, i + 1)  <=>  o in ((i - 0.5) / scale - 0.5, (i + 1.5) / scale - 0.5); row 0 also takes the clamped ones
-        int oy_lo = iy == 0 ? 0 : max(0, (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1);
-        int oy_hi = min(Ho - 1, (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1);
-        int ox_lo = ix == 0 ? 0 : max(0, (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1);
-        int ox_hi = min(Wo - 1, (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1);
+        int oy_lo, oy_hi, ox_lo, ox_hi;
+        bilin_adj_range(iy, sh, Ho, oy_lo, oy_hi);
+        bilin_adj_range(ix, sw, Wo, ox_lo, ox_hi);
         float acc = 0.f;
         for (int oy = oy_lo; oy <= oy_hi; ++oy) {
             int y0, y1;
@@ -724,6 +715,65 @@ __global__ __launch_bounds__(TPB) void bilinear_bwd_kernel(const float* __restri
             acc += wy * row;
         }
         dx[i] = acc;
+    }
+}
+// NHWC forms (SegFormer-Lite's decoder, Extended_Baseline_Comparison.py:737-739): thread per (pixel, 4 channels); x and y may be channel
+// slices of wider buffers (pixel strides ldx / ldy), so the three resizes write straight into the concat buffer.  Same source-index rule
+// and the same fixed-order gather adjoint as the planar kernels above.
+__global__ __launch_bounds__(TPB) void bilinear_nhwc_fwd_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, int N, int H,
+                                                                int W, int Ho, int Wo, int C, float sh, float sw) {
+    const int cv = C >> 2;
+    const long total = (long)N * Ho * Wo * cv;
+    for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
+        const int c = (int)(i % cv) * 4;
+        const long p = i / cv;
+        const int ox = (int)(p % Wo);
+        const long t = p / Wo;
+        const int oy = (int)(t % Ho);
+        const float* xp = x + (t / Ho) * H * W * (long)ldx + c;
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        bilin_src(oy, sh, H, y0, y1, ly0, ly1);
+        bilin_src(ox, sw, W, x0, x1, lx0, lx1);
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xp + ((long)y0 * W + x0) * ldx);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(xp + ((long)y0 * W + x1) * ldx);
+        const f32x4 d = *reinterpret_cast<const f32x4*>(xp + ((long)y1 * W + x0) * ldx);
+        const f32x4 e = *reinterpret_cast<const f32x4*>(xp + ((long)y1 * W + x1) * ldx);
+        *reinterpret_cast<f32x4*>(y + p * ldy + c) = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d + lx1 * e);
+    }
+}
+__global__ __launch_bounds__(TPB) void bilinear_nhwc_bwd_kernel(const float* __restrict__ dy, int lddy, float* __restrict__ dx, int lddx, int N,
+                                                                int H, int W, int Ho, int Wo, int C, float sh, float sw) {
+    const int cv = C >> 2;
+    const long total = (long)N * H * W * cv;
+    for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
+        const int c = (int)(i % cv) * 4;
+        const long p = i / cv;
+        const int ix = (int)(p % W);
+        const long t = p / W;
+        const int iy = (int)(t % H);
+        const float* gp = dy + (t / H) * Ho * Wo * (long)lddy + c;
+        int oy_lo, oy_hi, ox_lo, ox_hi;
+        bilin_adj_range(iy, sh, Ho, oy_lo, oy_hi);
+        bilin_adj_range(ix, sw, Wo, ox_lo, ox_hi);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+            int y0, y1;
+            float ly0, ly1;
+            bilin_src(oy, sh, H, y0, y1, ly0, ly1);
+            const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
+            if (wy == 0.f) continue;
+            f32x4 row = {0.f, 0.f, 0.f, 0.f};
+            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+                int x0, x1;
+                float lx0, lx1;
+                bilin_src(ox, sw, W, x0, x1, lx0, lx1);
+                const float wx = (x0 == ix ? lx0 : 0.f) + (x1 == ix ? lx1 : 0.f);
+                if (wx != 0.f) row += wx * *reinterpret_cast<const f32x4*>(gp + ((long)oy * Wo + ox) * lddy);
+            }
+            acc += wy * row;
+        }
+        *reinterpret_cast<f32x4*>(dx + p * lddx + c) = acc;
     }
 }
 __global__ __launch_bounds__(TPB) void mul_pixel_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ s, float* __restrict__ y,
@@ -749,6 +799,26 @@ extern "C" int runet_bilinear_bwd(const float* dy, float* dx, long planes, int h
     RUNET_REQUIRE(dy && dx && planes > 0 && h > 0 && w > 0 && ho > 0 && wo > 0, "bad arguments");
     hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(ew_grid(planes * h * w)), dim3(TPB), 0, (hipStream_t)stream, dy, dx, planes, h, w, ho, wo,
                        (float)h / (float)ho, (float)w / (float)wo);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bilinear_nhwc_fwd(const float* x, int ldx, float* y, int ldy, int n_img, int h, int w, int ho, int wo, int c, void* stream) {
+    RUNET_REQUIRE(x && y, "null pointer");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ho > 0 && wo > 0 && c > 0 && c % 4 == 0, "bad shape (c must be a positive multiple of 4)");
+    RUNET_REQUIRE(ldx >= c && ldy >= c && ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0,
+                  "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
+    hipLaunchKernelGGL(bilinear_nhwc_fwd_kernel, dim3(ew_grid((long)n_img * ho * wo * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy,
+                       n_img, h, w, ho, wo, c, (float)h / (float)ho, (float)w / (float)wo);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bilinear_nhwc_bwd(const float* dy, int lddy, float* dx, int lddx, int n_img, int h, int w, int ho, int wo, int c, void* stream) {
+    RUNET_REQUIRE(dy && dx, "null pointer");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ho > 0 && wo > 0 && c > 0 && c % 4 == 0, "bad shape (c must be a positive multiple of 4)");
+    RUNET_REQUIRE(lddy >= c && lddx >= c && lddy % 4 == 0 && lddx % 4 == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dx % 16) == 0,
+                  "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
+    hipLaunchKernelGGL(bilinear_nhwc_bwd_kernel, dim3(ew_grid((long)n_img * h * w * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, dx, lddx,
+                       n_img, h, w, ho, wo, c, (float)h / (float)ho, (float)w / (float)wo);
     RUNET_CHECK_LAUNCH();
 }
 

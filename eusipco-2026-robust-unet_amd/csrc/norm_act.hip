@@ -303,12 +303,14 @@ __global__ __launch_bounds__(TPB) void chan_stats_finalize_kernel(const float* _
 // ACT_LEAKY (YOLOSeg: LeakyReLU with a run-time slope).  The ACT_RELU forms are the kernels as they were (same code).  LeakyReLU is NOT ReLU
 // with slope 0 (that gives -0.0 for negative inputs): leaky_act is aten's expression z > 0 ? z : z * slope (the product in fp32, the slope
 // a float) and leaky_grad its backward g * (z > 0 ? 1 : slope), z always bn_pre's, so the backward's decision is the forward's.
-enum { ACT_RELU = 0, ACT_LEAKY = 1 };
+// ACT_GELU (SegFormer-Lite's patch embeddings): nn.GELU() (erf form, gelu_f / gelu_grad of runet_common.h), z recomputed the same way.
+enum { ACT_RELU = 0, ACT_LEAKY = 1, ACT_GELU = 2 };
 __device__ __forceinline__ float leaky_act(const float z, const float slope) { return z > 0.f ? z : z * slope; }
 __device__ __forceinline__ float leaky_grad(const float g, const float z, const float slope) { return z > 0.f ? g : g * slope; }
-// the ACT_LEAKY instances of the backward kernels have no Dropout2d mask and take the slope in its argument slot
+// the ACT_LEAKY instances of the backward kernels have no Dropout2d mask and take the slope in its argument slot (ACT_GELU: unused)
 template <int ACT> struct MaskArg { typedef const float* __restrict__ type; };
 template <> struct MaskArg<ACT_LEAKY> { typedef float type; };
+template <> struct MaskArg<ACT_GELU> { typedef float type; };
 
 template <int VEC, int ACT>
 __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, int HW, int C,
@@ -337,6 +339,8 @@ __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, int l
             float r = bn_pre(v[q], sc[q], sh[q]);
             if constexpr (ACT == ACT_LEAKY) {
                 v[q] = leaky_act(r, slope);
+            } else if constexpr (ACT == ACT_GELU) {
+                v[q] = gelu_f(r);
             } else {
                 if (relu) r = fmaxf(r, 0.f);
                 v[q] = r * mk[q];
@@ -360,6 +364,12 @@ __global__ __launch_bounds__(TPB) void bn_apply_leaky_kernel(const float* __rest
                                                              int HW, int C, int pix_per_chunk, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, float slope) {
     bn_apply_body<VEC, ACT_LEAKY>(x, ldx, y, ldy, HW, C, pix_per_chunk, scale, shift, nullptr, 1, slope);
+}
+template <int VEC>
+__global__ __launch_bounds__(TPB) void bn_apply_gelu_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
+                                                            int HW, int C, int pix_per_chunk, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift) {
+    bn_apply_body<VEC, ACT_GELU>(x, ldx, y, ldy, HW, C, pix_per_chunk, scale, shift, nullptr, 1, 0.f);
 }
 
 // The incoming gradient of a 2x2 max-pool (POOL): dy is the POOLED gradient [n, H/2, W/2] (pixel stride lddy) and pidx its winner bytes
@@ -394,7 +404,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
     const int p0 = chunk * pix_per_chunk, p1 = min(HW, p0 + pix_per_chunk);
     const unsigned char* pidx = POOL ? reinterpret_cast<const unsigned char*>(act) : nullptr;
     const int W = POOL ? ldact : 0;
-    if constexpr (POOL || ACT == ACT_LEAKY) act = nullptr;
+    if constexpr (POOL || ACT != ACT_RELU) act = nullptr;
     // ReLU(+Dropout2d) backward: either from the saved activation (act > 0) or, when rscale/rshift are given, recomputed from x with
     // the forward's own expression x*scale + shift > 0 - one tensor less to read
     const bool recompute = rscale != nullptr;
@@ -405,7 +415,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
         const int c = col * VEC + q;
         const bool ok = row < rows;
         mu[q] = ok ? mean[c] : 0.f; is[q] = ok ? invstd[c] : 0.f;
-        if constexpr (ACT == ACT_LEAKY) mk[q] = 1.f;
+        if constexpr (ACT != ACT_RELU) mk[q] = 1.f;
         else mk[q] = (ok && mask) ? mask[(long)n * C + c] : 1.f;
         fs[q] = (ok && recompute) ? rscale[c] : 0.f; fh[q] = (ok && recompute) ? rshift[c] : 0.f;
     }
@@ -433,6 +443,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
             for (int q = 0; q < VEC; ++q) {
                 float gg = g[q];
                 if constexpr (ACT == ACT_LEAKY) gg = leaky_grad(gg, bn_pre(xv[q], fs[q], fh[q]), mask);
+                else if constexpr (ACT == ACT_GELU) gg = gelu_grad(gg, bn_pre(xv[q], fs[q], fh[q]));
                 else if (act) gg = (av[q] > 0.f) ? gg * mk[q] : 0.f;
                 else if (recompute) gg = (bn_pre(xv[q], fs[q], fh[q]) > 0.f) ? gg * mk[q] : 0.f;
                 sg[q] += gg;
@@ -497,7 +508,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
     const int p0 = blockIdx.x * pix_per_chunk, p1 = min(HW, p0 + pix_per_chunk);
     const unsigned char* pidx = POOL ? reinterpret_cast<const unsigned char*>(act) : nullptr;
     const int W = POOL ? ldact : 0;
-    if constexpr (POOL || ACT == ACT_LEAKY) act = nullptr;
+    if constexpr (POOL || ACT != ACT_RELU) act = nullptr;
     // dx = sc*(g - k1 - xhat*k2) = g*sc + x*a + b  with a = -sc*k2*invstd, b = sc*(mean*invstd*k2 - k1)
     const bool recompute = rshift != nullptr;        // ReLU mask from x*scale + shift > 0 (scale IS the forward scale) instead of act > 0
     float sc[VEC], ca[VEC], cb[VEC], mk[VEC], fh[VEC];
@@ -506,7 +517,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
         const int c = col * VEC + q;
         sc[q] = scale[c];
         bn_bwd_coef(sc[q], mean[c], invstd[c], sums[c], sums[C + c], inv_m, ca[q], cb[q]);
-        if constexpr (ACT == ACT_LEAKY) mk[q] = 1.f;
+        if constexpr (ACT != ACT_RELU) mk[q] = 1.f;
         else mk[q] = mask ? mask[(long)n * C + c] : 1.f;
         fh[q] = recompute ? rshift[c] : 0.f;
     }
@@ -533,6 +544,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
         for (int q = 0; q < VEC; ++q) {
             float gg = g[q];
             if constexpr (ACT == ACT_LEAKY) gg = leaky_grad(gg, bn_pre(xv[q], sc[q], fh[q]), mask);
+            else if constexpr (ACT == ACT_GELU) gg = gelu_grad(gg, bn_pre(xv[q], sc[q], fh[q]));
             else if (act) gg = (av[q] > 0.f) ? gg * mk[q] : 0.f;
             else if (recompute) gg = (bn_pre(xv[q], sc[q], fh[q]) > 0.f) ? gg * mk[q] : 0.f;
             r[q] = bn_bwd_dx(gg, sc[q], xv[q], ca[q], cb[q]);
@@ -902,5 +914,58 @@ extern "C" int runet_bn_bwd_apply_pooled_leaky(const float* dpool, int ldp, cons
     const int chunks = stream_chunks(n_img, hw, c, TPB / (c / 4), ppc);
     hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true, ACT_LEAKY>), dim3(chunks, n_img), dim3(TPB), 0, st, dpool, ldp, x, ldx,
                        reinterpret_cast<const float*>(idx), w, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, slope, inv_m, shift);
+    RUNET_CHECK_LAUNCH();
+}
+
+// ---- GELU forms of the BatchNorm kernels (SegFormer-Lite's patch embeddings, Extended_Baseline_Comparison.py:677-688: Conv2d -> BatchNorm2d ->
+// nn.GELU()).  The ACT_GELU instances of the same kernels: same launch geometry and summation order as the LeakyReLU entries; the backward
+// recomputes z = x * scale + shift with the forward's scale / shift.
+extern "C" int runet_bn_apply_gelu(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale, const float* shift,
+                                   void* stream) {
+    RUNET_REQUIRE(x && y && scale && shift, "null pointer");
+    REQ_VEC(c);
+    RUNET_REQUIRE(pixels > 0 && hw > 0 && ldx >= c && ldy >= c, "bad shape");
+    RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
+    hipStream_t st = (hipStream_t)stream;
+    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
+    int ppc;
+    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
+    if (vec == 4) hipLaunchKernelGGL((bn_apply_gelu_kernel<4>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift);
+    else hipLaunchKernelGGL((bn_apply_gelu_kernel<1>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_bwd_reduce_gelu(const float* dy, int lddy, const float* x, int ldx, int n_img, int hw, int c, const float* mean,
+                                        const float* invstd, float* workspace, float* sums, const float* scale, const float* shift, void* stream) {
+    RUNET_REQUIRE(dy && x && mean && invstd && workspace && sums && scale && shift, "null pointer");
+    REQ_VEC(c);
+    RUNET_REQUIRE(n_img > 0 && hw > 0 && lddy >= c && ldx >= c, "bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    const int vec = (c % 4 == 0) ? 4 : 1, rows = TPB / (c / vec);
+    const int chunks = pick_chunks(n_img, hw, c, rows);
+    const int ppc = (hw + chunks - 1) / chunks;
+    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
+    dim3 grid(chunks, n_img);
+    if (vec == 4) hipLaunchKernelGGL((bn_bwd_reduce_partial<4, false, ACT_GELU>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, 0.f, ppc, workspace, scale, shift);
+    else hipLaunchKernelGGL((bn_bwd_reduce_partial<1, false, ACT_GELU>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, 0.f, ppc, workspace, scale, shift);
+    const int cw = final_cw(c, (long)chunks * n_img);
+    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_bn_bwd_apply_gelu(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, long pixels, int hw, int c,
+                                       const float* mean, const float* invstd, const float* scale, const float* sums, long m_total, const float* shift,
+                                       void* stream) {
+    RUNET_REQUIRE(dy && x && dx && mean && invstd && scale && sums && shift, "null pointer");
+    REQ_VEC(c);
+    RUNET_REQUIRE(pixels > 0 && hw > 0 && lddy >= c && ldx >= c && lddx >= c, "bad shape");
+    RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
+    hipStream_t st = (hipStream_t)stream;
+    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
+    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
+    int ppc;
+    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
+    if (vec == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<4, false, ACT_GELU>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, 0.f, inv_m, shift);
+    else hipLaunchKernelGGL((bn_bwd_apply_kernel<1, false, ACT_GELU>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, 0.f, inv_m, shift);
     RUNET_CHECK_LAUNCH();
 }

@@ -80,3 +80,29 @@ __device__ __forceinline__ void bn_bwd_coef(const float sc, const float mean, co
 __device__ __forceinline__ float bn_bwd_dx(const float gg, const float sc, const float x, const float ca, const float cb) {
     return __builtin_fmaf(gg, sc, __builtin_fmaf(x, ca, cb));
 }
+
+// GELU, the exact erf form (nn.GELU(), SegFormer-Lite's patch embeddings and MixFFN): ATen's expressions, shared by the BatchNorm + GELU
+// kernels (norm_act.hip) and the depthwise convolution + GELU kernels (dwconv.hip).  gelu_grad(g, z) = g * GELU'(z).
+__device__ __forceinline__ float gelu_f(const float z) { return z * 0.5f * (1.0f + erff(z * 0.70710678118654752440f)); }
+__device__ __forceinline__ float gelu_grad(const float g, const float z) {
+    const float cdf = 0.5f * (1.0f + erff(z * 0.70710678118654752440f));
+    const float pdf = expf(-0.5f * z * z) * 0.39894228040143267794f;     // M_2_SQRTPI * M_SQRT1_2 * 0.5
+    return g * (cdf + z * pdf);
+}
+
+// ATen's align_corners=False source index of a bilinear resize (upsample_bilinear2d): src = max(0, (o + 0.5) * scale - 0.5), scale = in / out;
+// the two source taps i0, i1 (i1 clamped to the last row / column) and their weights.  Shared by the planar (runet_bilinear_*) and the NHWC
+// (runet_bilinear_nhwc_*) kernels of misc.hip, so both follow the same rule bit for bit.
+__device__ __forceinline__ void bilin_src(int o, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
+    float src = scale * ((float)o + 0.5f) - 0.5f;
+    src = src < 0.f ? 0.f : src;
+    i0 = (int)src;
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l1 = src - (float)i0;
+    l0 = 1.f - l1;
+}
+// adjoint (gather) range: the outputs whose two source taps can include input index i lie in [lo, hi] (index 0 also takes the clamped ones)
+__device__ __forceinline__ void bilin_adj_range(int i, float scale, int out, int& lo, int& hi) {
+    lo = i == 0 ? 0 : max(0, (int)floorf(((float)i - 0.5f) / scale - 0.5f) - 1);
+    hi = min(out - 1, (int)ceilf(((float)i + 1.5f) / scale - 0.5f) + 1);
+}

@@ -12,6 +12,10 @@ hand-written data-gradient / weight-gradient kernels.
     torch.ops.runet.bn_leaky_maxpool2_nhwc(t, scale, shift, negative_slope)
                                                                  maxpool2(leaky_relu(t * scale + shift)) -> (y, idx) (Main_Final.py:436-510)
                                                                  (+ bn_leaky_maxpool2_nhwc_bwd)
+    torch.ops.runet.kv_attention_nhwc(q, kv, heads) -> (o, lse)   SegFormer-Lite's reduced-KV softmax attention (Extended_Baseline_Comparison.py:
+                                                                 647-662), heads of 32 channels  (+ kv_attention_nhwc_bwd)
+    torch.ops.runet.dwconv3x3_gelu_nhwc(x, w_hwio, bias)         GELU(depthwise 3x3 conv, padding 1) of the MixFFN (:628-633), w_hwio [3, 3, 1, C]
+                                                                 (+ dwconv3x3_gelu_nhwc_bwd)
     torch.ops.runet.bce_loss(prob, target)                       nn.BCELoss() mean, ATen clamp semantics (Main_Final.py:551)
     torch.ops.runet.cross_entropy(logits, target)                nn.CrossEntropyLoss() mean (train_water_segmentation.py:304)
     torch.ops.runet.seg_counts(pred, target, threshold)          per-image tp / predicted / target / agreement counts (Main_Final.py:519-547)
@@ -395,7 +399,92 @@ def _bil_bwd(ctx, dy):
 
 register_autograd("runet::bilinear_resize", _bil_bwd, setup_context=_bil_setup)
 
+# ------------------------------------------------------------------------------------------------ SegFormer-Lite (Extended_Baseline_Comparison.py:622-664)
+@custom_op("runet::kv_attention_nhwc", mutates_args=(), device_types=_DEV)
+def kv_attention_nhwc(q: torch.Tensor, kv: torch.Tensor, heads: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """q [N, H, W, C], kv [N, Hr, Wr, 2C] (k = channels [0, C), v = [C, 2C)), C = 32 * heads -> (o [N, H, W, C], lse [N, heads, H * W])"""
+    _chk_nhwc(q)
+    _chk_nhwc(kv)
+    from . import segformer
+    return segformer.kv_attention(q.contiguous(), kv.contiguous(), int(heads))
+
+
+@kv_attention_nhwc.register_fake
+def _(q, kv, heads):
+    n, h, w, c = q.shape
+    return q.new_empty((n, h, w, c)), q.new_empty((n, heads, h * w))
+
+
+@custom_op("runet::kv_attention_nhwc_bwd", mutates_args=(), device_types=_DEV)
+def kv_attention_nhwc_bwd(q: torch.Tensor, kv: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor, dlse: torch.Tensor,
+                          heads: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """-> (dq, dkv) of kv_attention_nhwc for the output gradients do (of o) and dlse (of lse)"""
+    from . import segformer
+    return segformer.kv_attention_backward(q.contiguous(), kv.contiguous(), o.contiguous(), lse.contiguous(), do.contiguous(), int(heads),
+                                           dlse=dlse.contiguous())
+
+
+@kv_attention_nhwc_bwd.register_fake
+def _(q, kv, o, lse, do, dlse, heads):
+    return q.new_empty(q.shape), kv.new_empty(kv.shape)
+
+
+def _attn_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[0], output[1])
+    ctx.heads = inputs[2]
+
+
+def _attn_bwd(ctx, do, dlse):
+    q, kv, o, lse = ctx.saved_tensors
+    do = torch.zeros_like(o) if do is None else do
+    dlse = torch.zeros_like(lse) if dlse is None else dlse
+    dq, dkv = torch.ops.runet.kv_attention_nhwc_bwd(q, kv, o, lse, do.contiguous(), dlse.contiguous(), ctx.heads)
+    return dq, dkv, None
+
+
+register_autograd("runet::kv_attention_nhwc", _attn_bwd, setup_context=_attn_setup)
+
+
+@custom_op("runet::dwconv3x3_gelu_nhwc", mutates_args=(), device_types=_DEV)
+def dwconv3x3_gelu_nhwc(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """GELU(bias + depthwise 3x3 convolution of x [N, H, W, C], padding 1), w_hwio [3, 3, 1, C] (nn.Conv2d(C, C, 3, groups=C) weight's HWIO)"""
+    _chk_nhwc(x)
+    from . import segformer
+    return segformer.dwconv_gelu(x.contiguous(), w_hwio.contiguous(), bias.contiguous(), keep_z=False)[1]
+
+
+@dwconv3x3_gelu_nhwc.register_fake
+def _(x, w_hwio, bias):
+    return x.new_empty(x.shape)
+
+
+@custom_op("runet::dwconv3x3_gelu_nhwc_bwd", mutates_args=(), device_types=_DEV)
+def dwconv3x3_gelu_nhwc_bwd(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tensor, da: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (dx, dw [3, 3, 1, C], dbias) of dwconv3x3_gelu_nhwc; z is recomputed from x, w and bias"""
+    from . import segformer
+    c = x.shape[3]
+    dx, dwdb = segformer.dwconv_gelu_backward(x.contiguous(), None, da.contiguous().clone(), w_hwio.contiguous(), bias.contiguous())
+    return dx, dwdb[:9 * c].view(3, 3, 1, c).clone(), dwdb[9 * c:].clone()
+
+
+@dwconv3x3_gelu_nhwc_bwd.register_fake
+def _(x, w_hwio, bias, da):
+    return x.new_empty(x.shape), w_hwio.new_empty(w_hwio.shape), bias.new_empty(bias.shape)
+
+
+def _dw_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _dw_bwd(ctx, da):
+    x, w, b = ctx.saved_tensors
+    return torch.ops.runet.dwconv3x3_gelu_nhwc_bwd(x, w, b, da.contiguous())
+
+
+register_autograd("runet::dwconv3x3_gelu_nhwc", _dw_bwd, setup_context=_dw_setup)
+
 OPS = ("conv2d_nhwc", "conv2d_nhwc_dgrad", "conv2d_nhwc_wgrad", "convt2x2s2_nhwc", "convt2x2s2_nhwc_dgrad", "convt2x2s2_nhwc_wgrad",
        "maxpool2_nhwc", "maxpool2_nhwc_bwd", "bce_loss", "bce_loss_bwd", "cross_entropy", "cross_entropy_bwd", "seg_counts",
        "bilinear_resize", "bilinear_resize_bwd", "maxunpool2_nhwc", "maxunpool2_nhwc_bwd", "bn_relu_maxpool2_nhwc",
-       "bn_leaky_maxpool2_nhwc", "bn_leaky_maxpool2_nhwc_bwd")
+       "bn_leaky_maxpool2_nhwc", "bn_leaky_maxpool2_nhwc_bwd", "kv_attention_nhwc", "kv_attention_nhwc_bwd", "dwconv3x3_gelu_nhwc",
+       "dwconv3x3_gelu_nhwc_bwd")

@@ -357,7 +357,8 @@ int runet_stem_wgrad(const float* x, int ldx, const float* dy, int ldy, float* d
                      int h, int w, int cin_w, int cout, int ksize, void* stream);
 
 /* ---- DeepLabV3+ baseline (Main_Final.py:325-433): the same implicit-GEMM kernels with general geometry ----
- * runet_conv2d_general: Conv2d(kh x kw <= 7x7, stride 1|2, padding, dilation).  mode RUNET_CONV_FWD: x [n,hin,win,cin] -> y [n,ho,wo,cout],
+ * runet_conv2d_general: Conv2d(kh x kw <= 8x8, stride 1..8, padding, dilation).  mode RUNET_CONV_FWD: x [n,hin,win,cin] -> y [n,ho,wo,cout],
+ * (kernel = stride, no padding, hin = ho * stride: the data gradient takes the one live tap per pixel, s^2 GEMMs + a permutation)
  * w [kh,kw,cin_w,cout];  mode RUNET_CONV_DGRAD: x := dy [n,ho,wo,cin(=conv Cout)] -> y := dx [n,hin,win,cout(=conv Cin)], w [kh,kw,cout,cin].
  * runet_convt4_igemm: ConvTranspose2d(k4, s2, p1), w [4,4,cin,cout]; RUNET_CONVT_FWD x [n,h,w,cin] -> y [n,2h,2w,cout];
  * RUNET_CONVT_DGRAD x := dy [n,2h,2w,cin(=Cout)] -> y := dx [n,h,w,cout(=Cin)].
@@ -492,6 +493,54 @@ int runet_bn_bwd_apply_pooled_leaky(const float* dpool, int ldp, const unsigned 
 int runet_convt4_igemm_stats_parts(int n_img, int h, int w_, int cout);
 int runet_convt4_igemm_stats(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int h, int w_, int cin,
                              int cout, float* stats, void* stream);
+
+/* ---- SegFormer-Lite baseline (Extended_Baseline_Comparison.py:622-744).  Everything else it runs is shared: the 1x1 convolutions (q, kv,
+ *      proj, fc1, fc2, linear_c*, linear_fuse) and the head's 3x3 through runet_conv_igemm & co., the patch embeddings' 7x7 s4 and 3x3 s2
+ *      convolutions and the r x r s r key / value reductions through runet_conv2d_general / runet_conv_wgrad_general, BatchNorm + ReLU of the
+ *      decoder, runet_outc_* (head's 1x1 + sigmoid), runet_bilinear_* (the probability map's resize).
+ * runet_kv_attention_fwd / _bwd: EfficientSelfAttention's core (:647-662).  q [n, nq, c] (pixel stride ldq), kv [n, nk, 2c] (k = channels
+ *   [0, c), v = [c, 2c)), heads split the channels contiguously (channel = head * 32 + j): c must be 32 * heads (head dimension 32, anything
+ *   else is an error).  o [n, nq, c] = softmax((q k^T) * 32^-0.5) v per head, lse [n, heads, nq] the log-sum-exp of each query's scaled
+ *   scores.  Any nq, any nk >= 1.  The backward takes the forward's o and lse, dO [n, nq, c] and an optional gradient of lse (dlse
+ *   [n, heads, nq], may be NULL); it writes dq [n, nq, c] and dkv [n, nk, 2c]
+ *   (no accumulation), bitwise reproducible (fixed summation order, no atomics).  workspace >= runet_kv_attention_bwd_workspace_floats
+ *   floats (-1: bad shape).  fp32 throughout; pixel strides multiples of 4 floats, tensors 16-byte aligned.
+ * runet_dwconv3x3_gelu_fwd: MixFFN's depthwise 3x3 (padding 1, groups = c, bias) + nn.GELU() (:628-633).  x [n, h, w, c], w [3][3][c] (the
+ *   HWIO memory of the [c, 1, 3, 3] weight), b [c]; z = b + dwconv(x) (may be NULL: not kept), a = GELU(z), erf form.
+ * runet_dwconv3x3_gelu_bwd_wgrad: g = da * GELU'(z) (g may be da itself, with the same stride) and dwdb [10c] = (dw [3][3][c] | db [c]),
+ *   summed in a fixed order through `workspace` (>= runet_dwconv3x3_gelu_bwd_workspace_floats floats, -1: bad shape).  z NULL: z is
+ *   recomputed from x, w and b (the nine neighbours of x are read for dw anyway), so the forward need not keep it.
+ * runet_dwconv3x3_bwd_data: dx [n, h, w, c] = the depthwise convolution's data gradient of g.
+ *   Depthwise: c a multiple of 4 up to 1024, pixel strides multiples of 4, tensors 16-byte aligned.
+ * runet_bn_apply_gelu / runet_bn_bwd_reduce_gelu / runet_bn_bwd_apply_gelu: the patch embeddings' BatchNorm2d + nn.GELU() (:677-688), the GELU
+ *   forms of runet_bn_apply_leaky / runet_bn_bwd_reduce_leaky / runet_bn_bwd_apply_leaky (the same kernels with another activation, the
+ *   backward recomputes z = x * scale + shift with the forward's scale / shift).  Workspace, sums and m_total as there.
+ * runet_bilinear_nhwc_fwd / _bwd: F.interpolate(mode='bilinear', align_corners=False) of NHWC maps (:737-739), x [n, h, w, 0:c] (pixel stride
+ *   ldx) -> y [n, ho, wo, 0:c] (ldy): either side may be a channel slice of a wider buffer (the decoder resizes straight into its 1024-channel
+ *   concat buffer).  The backward is the adjoint in gather form, fixed summation order, dx overwritten.  Same source-index rule as
+ *   runet_bilinear_fwd / _bwd.  c a multiple of 4, pixel strides multiples of 4, pointers 16-byte aligned. */
+long runet_kv_attention_bwd_workspace_floats(int n_img, int nq, int nk, int c, int heads);
+int runet_kv_attention_fwd(const float* q, int ldq, const float* kv, int ldkv, float* o, int ldo, float* lse, int n_img, int nq, int nk, int c,
+                           int heads, void* stream);
+int runet_kv_attention_bwd(const float* q, int ldq, const float* kv, int ldkv, const float* o, int ldo, const float* dout, int lddo,
+                           const float* lse, const float* dlse, float* dq, int lddq, float* dkv, int lddkv, float* workspace, long workspace_floats,
+                           int n_img, int nq,
+                           int nk, int c, int heads, void* stream);
+int runet_dwconv3x3_gelu_fwd(const float* x, int ldx, const float* w, const float* b, float* z, int ldz, float* a, int lda, int n_img, int h,
+                             int w_, int c, void* stream);
+long runet_dwconv3x3_gelu_bwd_workspace_floats(int n_img, int h, int w_, int c);
+int runet_dwconv3x3_gelu_bwd_wgrad(const float* x, int ldx, const float* w, const float* b, const float* da, int ldda, const float* z, int ldz,
+                                   float* g, int ldg, float* workspace, long workspace_floats, float* dwdb, int n_img, int h, int w_, int c,
+                                   void* stream);
+int runet_dwconv3x3_bwd_data(const float* g, int ldg, const float* w, float* dx, int lddx, int n_img, int h, int w_, int c, void* stream);
+int runet_bn_apply_gelu(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale, const float* shift,
+                        void* stream);
+int runet_bn_bwd_reduce_gelu(const float* dy, int lddy, const float* x, int ldx, int n_img, int hw, int c, const float* mean, const float* invstd,
+                             float* workspace, float* sums, const float* scale, const float* shift, void* stream);
+int runet_bn_bwd_apply_gelu(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, long pixels, int hw, int c, const float* mean,
+                            const float* invstd, const float* scale, const float* sums, long m_total, const float* shift, void* stream);
+int runet_bilinear_nhwc_fwd(const float* x, int ldx, float* y, int ldy, int n_img, int h, int w, int ho, int wo, int c, void* stream);
+int runet_bilinear_nhwc_bwd(const float* dy, int lddy, float* dx, int lddx, int n_img, int h, int w, int ho, int wo, int c, void* stream);
 
 #ifdef __cplusplus
 }
