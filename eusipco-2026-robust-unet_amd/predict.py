@@ -1,0 +1,382 @@
+"""Prediction with the plain 2-class U-Net: the reference's `CoastlineExtractor` (predict_coastline.py:336-652) on the gfx950 kernels.
+
+Reference pipeline, one image at a time (line numbers of predict_coastline.py):
+  1. :358-363, :387  PIL bilinear Resize((512, 512)) -> ToTensor -> Normalize(ImageNet)      host resize, then runet_scene_to_tiles
+  2. :390-392        UNet(3, 2).eval(), argmax(logits, dim=1)                                 unet_forward(nhwc=True), runet_argmax_stitch
+  3. :395-396        cv2.resize(pred, (W, H), INTER_NEAREST)                                  runet_resize_nearest_u8
+  4. :595-602        MORPH_ELLIPSE k x k, cv2.dilate, dilated - mask                          runet_dilate_diff_u8 (+ the two pixel counts)
+  5. :605-616        cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), > 10 points,       host: trace_external_contours, approx_poly_dp
+                     approxPolyDP(0.002 * arcLength)
+  6. :404-413, :620-652  result dict, two PNG masks (* 255), <base>_coastlines.json           save_extraction_result
+
+Between the upload of the uint8 image and the single download of (water mask, coastline mask, counts) nothing returns to the host.
+`predict_scene` is the addition for scenes larger than one network input: the scene is cut into overlapping tiles at its own resolution and
+every output pixel is taken from exactly one tile's core (tile_plan), so there is no blending and the result is bit-deterministic.
+
+OpenCV is not a dependency.  Steps 3-5 restate OpenCV's rules (index rule, ellipse spans, Suzuki-Abe border following); vertex-for-vertex
+equality of the contours with cv2 is not claimed.  GDAL band handling, the matplotlib report, the GUI and the CLI are out of scope.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import os
+from datetime import datetime
+
+import numpy as np
+import torch
+from PIL import Image
+
+from . import data, ops
+from ._lib import check, lib
+
+MAX_DILATION = 31
+
+
+# ------------------------------------------------------------------------------------------------ host-side plans
+def ellipse_spans(k):
+    """-> (j1, j2): row i of cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)) is set on columns [j1[i], j2[i])."""
+    k = int(k)
+    if k < 1 or k > MAX_DILATION or k % 2 == 0:
+        raise ValueError(f"dilation size must be odd and in 1..{MAX_DILATION} (got {k})")
+    j1, j2 = (ctypes.c_int * k)(), (ctypes.c_int * k)()
+    check(lib.runet_ellipse_spans(k, j1, j2))
+    return np.array(j1, dtype=np.int64), np.array(j2, dtype=np.int64)
+
+
+def ellipse_element(k):
+    j1, j2 = ellipse_spans(k)
+    cols = np.arange(k)[None, :]
+    return ((cols >= j1[:, None]) & (cols < j2[:, None])).astype(np.uint8)
+
+
+def tile_plan(h, w, tile=512, halo=64):
+    """-> int32 [n, 2] tile origins (y0, x0).  Cores of side tile - 2 * halo partition the scene from (0, 0): tile t owns the pixels
+    [y0 + halo, y0 + tile - halo) x [x0 + halo, x0 + tile - halo) clipped to the scene and reads halo pixels of context around them, so
+    origins start at -halo and the last row / column of tiles may overhang."""
+    if tile <= 0 or tile % 16:
+        raise ValueError("tile must be a positive multiple of 16 (four 2x2 poolings)")
+    if halo < 0 or 2 * halo >= tile:
+        raise ValueError("2 * halo must be smaller than the tile")
+    if h <= 0 or w <= 0:
+        raise ValueError("empty scene")
+    core = tile - 2 * halo
+    ys = np.arange(0, h, core, dtype=np.int32) - halo
+    xs = np.arange(0, w, core, dtype=np.int32) - halo
+    return np.stack(np.meshgrid(ys, xs, indexing="ij"), axis=-1).reshape(-1, 2).astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ device steps
+def _dev_u8(a, device):
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.uint8:
+            raise ValueError("expected a uint8 tensor")
+        return a.to(device).contiguous()
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError("expected a uint8 array")
+    return torch.from_numpy(a).to(device)
+
+
+def scene_to_tiles(scene, origins, tile):
+    """scene: device uint8 [H, W, 3]; origins: device int32 [n, 2] -> float32 [n, tile, tile, 4] (ToTensor + Normalize, outside = 0)."""
+    h, w, _ = scene.shape
+    n = origins.shape[0]
+    out = torch.empty((n, tile, tile, 4), device=scene.device, dtype=torch.float32)
+    m, s = data.IMAGENET_MEAN, data.IMAGENET_STD
+    check(lib.runet_scene_to_tiles(scene.data_ptr(), h, w, scene.stride(0), origins.data_ptr(), n, tile, m[0], m[1], m[2], s[0], s[1], s[2],
+                                   out.data_ptr(), ops.stream()))
+    return out
+
+
+def argmax_stitch(z4, origins, halo, mask, n_classes=2):
+    """z4: the head's NHWC output [n, T, T, 4]; writes the class index of every tile's core into mask (device uint8 [H, W])."""
+    n, tile = z4.shape[0], z4.shape[1]
+    check(lib.runet_argmax_stitch(z4.data_ptr(), n, tile, n_classes, origins.data_ptr(), halo, mask.data_ptr(), mask.shape[0], mask.shape[1],
+                                  ops.stream()))
+    return mask
+
+
+def resize_nearest(src, size, out=None):
+    """cv2.resize(src, (W, H), interpolation=INTER_NEAREST) of a device uint8 mask; size = (H, W).  The same size returns src itself."""
+    dh, dw = size
+    if (dh, dw) == tuple(src.shape) and out is None:
+        return src
+    if out is None:
+        out = torch.empty((dh, dw), device=src.device, dtype=torch.uint8)
+    if (dh, dw) == tuple(src.shape):
+        return out.copy_(src)
+    check(lib.runet_resize_nearest_u8(src.data_ptr(), src.shape[0], src.shape[1], out.data_ptr(), dh, dw, ops.stream()))
+    return out
+
+
+def dilate_diff(mask, k=5, coast=None, counts=None, want_dilated=False):
+    """-> (coastline = dilate(mask, ellipse k) - mask, counts int32 [2] = (water, coastline pixels), dilated or None), all on the device."""
+    ellipse_spans(k)                                     # ValueError for an even / too large k, before anything is allocated
+    h, w = mask.shape
+    if coast is None:
+        coast = torch.empty((h, w), device=mask.device, dtype=torch.uint8)
+    if counts is None:
+        counts = torch.empty(2, device=mask.device, dtype=torch.int32)
+    dil = torch.empty((h, w), device=mask.device, dtype=torch.uint8) if want_dilated else None
+    if dil is not None and (dil.data_ptr() - coast.data_ptr()) % 16:
+        raise RuntimeError("allocator returned masks of different 16-byte phase")
+    check(lib.runet_dilate_diff_u8(mask.data_ptr(), h, w, int(k), coast.data_ptr(), dil.data_ptr() if want_dilated else None, counts.data_ptr(),
+                                   ops.stream()))
+    return coast, counts, dil
+
+
+# ------------------------------------------------------------------------------------------------ contours (host)
+# the 8 neighbours in counter-clockwise order as seen on the image (y grows downwards): E, NE, N, NW, W, SW, S, SE
+_DI = (0, -1, -1, -1, 0, 1, 1, 1)
+_DJ = (1, 1, 0, -1, -1, -1, 0, 1)
+
+
+def trace_external_contours(mask):
+    """cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) by Suzuki-Abe border following (8-connected): the outer border of every
+    top-level component, in raster order of their start pixels, each an int32 [n, 2] array of (x, y) with collinear runs reduced to their end
+    points.  Border pixels are marked +id (the pixel to the right not seen to be background) or -id (right neighbour is background), and a
+    start candidate whose last marked pixel to the left is positive lies inside a traced border and is skipped - which is how holes and what is
+    inside them stay out.  Only candidates (pixel set, left neighbour clear: found with numpy) and border pixels are visited from Python."""
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError("mask must be 2-D")
+    h, w = m.shape
+    img = np.zeros((h + 2, w + 2), dtype=np.int32)
+    img[1:-1, 1:-1] = m != 0
+    cand_i, cand_j = np.nonzero((img[:, 1:] == 1) & (img[:, :-1] == 0))
+    cand_j = cand_j + 1
+    W = w + 2
+    flat = img.reshape(-1)
+    f = memoryview(flat)
+    off = [_DI[d] * W + _DJ[d] for d in range(8)]
+    contours = []
+    nbd = 1
+    for i, j in zip(cand_i.tolist(), cand_j.tolist()):
+        p0 = i * W + j
+        if f[p0] != 1:
+            continue                                     # already on a traced border
+        left = img[i, :j]
+        marked = np.flatnonzero((left > 1) | (left < 0))
+        if marked.size and left[marked[-1]] > 0:
+            continue                                     # inside an outer border: a hole's far side, or an island in a hole
+        nbd += 1
+        # first neighbour clockwise from the west one
+        d1 = -1
+        for s in range(8):
+            d = (4 - s) % 8
+            if f[p0 + off[d]] != 0:
+                d1 = d
+                break
+        if d1 < 0:
+            f[p0] = -nbd
+            contours.append(np.array([[j - 1, i - 1]], dtype=np.int32))
+            continue
+        p1 = p0 + off[d1]
+        pts, dirs = [], []                               # visited pixels and the direction each was LEFT in
+        p3, d_from = p0, d1                              # d_from: direction from p3 to the previous pixel p2
+        while True:
+            east_clear = False
+            d = d_from
+            for _ in range(8):
+                d = (d + 1) % 8
+                if f[p3 + off[d]] != 0:
+                    break
+                if d == 0:
+                    east_clear = True
+            p4 = p3 + off[d]
+            if east_clear:
+                f[p3] = -nbd
+            elif f[p3] == 1:
+                f[p3] = nbd
+            pts.append(p3)
+            dirs.append(d)
+            if p4 == p0 and p3 == p1:
+                break
+            p3, d_from = p4, (d + 4) % 8
+        n = len(pts)
+        keep = [t for t in range(n) if dirs[t] != dirs[t - 1]] if n > 1 else [0]
+        pa = np.array([pts[t] for t in keep], dtype=np.int64)
+        contours.append(np.stack([pa % W - 1, pa // W - 1], axis=1).astype(np.int32))
+    return contours
+
+
+def arc_length(points, closed=True):
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    if len(p) < 2:
+        return 0.0
+    d = np.diff(np.vstack([p, p[:1]]) if closed else p, axis=0)
+    return float(np.hypot(d[:, 0], d[:, 1]).sum())
+
+
+def _seg_dist(p, a, b):
+    ab = b - a
+    den = float(ab @ ab)
+    t = np.clip(((p - a) @ ab) / den, 0.0, 1.0) if den > 0 else np.zeros(len(p))
+    q = a + t[:, None] * ab
+    return np.hypot(p[:, 0] - q[:, 0], p[:, 1] - q[:, 1])
+
+
+def _dp_chain(p, eps):
+    """Douglas-Peucker on an open chain: indices of the kept points (both ends kept)."""
+    keep = np.zeros(len(p), dtype=bool)
+    keep[0] = keep[-1] = True
+    stack = [(0, len(p) - 1)]
+    while stack:
+        a, b = stack.pop()
+        if b - a < 2:
+            continue
+        d = _seg_dist(p[a + 1:b], p[a], p[b])
+        k = int(d.argmax())
+        if d[k] > eps:
+            k += a + 1
+            keep[k] = True
+            stack += [(a, k), (k, b)]
+    return np.flatnonzero(keep)
+
+
+def approx_poly_dp(points, eps, closed=True):
+    """cv2.approxPolyDP: Douglas-Peucker with tolerance eps (every dropped vertex within eps of the segment that replaces it).  A closed curve
+    is split at its first vertex and the vertex farthest from it.  -> int32 [n, 2]"""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    n = len(p)
+    if n <= 2:
+        return np.asarray(points, dtype=np.int32).reshape(-1, 2)
+    if not closed:
+        idx = _dp_chain(p, eps)
+    else:
+        far = int(np.hypot(*(p - p[0]).T).argmax())
+        if far == 0:
+            return np.asarray(points, dtype=np.int32).reshape(-1, 2)[:1]
+        a = _dp_chain(p[:far + 1], eps)
+        b = _dp_chain(np.vstack([p[far:], p[:1]]), eps) + far
+        idx = np.concatenate([a, b[1:-1]])
+    return np.asarray(points, dtype=np.int32).reshape(-1, 2)[idx]
+
+
+def coastlines_from_mask(coastline_mask, min_points=10, eps_factor=0.002):
+    """predict_coastline.py:605-616 -> list of [[x, y], ...]"""
+    out = []
+    for c in trace_external_contours(coastline_mask):
+        if len(c) > min_points:
+            out.append(approx_poly_dp(c, eps_factor * arc_length(c, True), True).tolist())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the extractor
+def _load_rgb(image):
+    """-> (PIL RGB image, path or None)"""
+    if isinstance(image, (str, os.PathLike)):
+        return Image.open(image).convert("RGB"), os.fspath(image)
+    if isinstance(image, Image.Image):
+        return image.convert("RGB"), None
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("image must be a path, a PIL image or a uint8 [H, W, 3] array")
+    return Image.fromarray(np.ascontiguousarray(a)), None
+
+
+def save_extraction_result(result, output_dir):
+    """predict_coastline.py:620-652 without the matplotlib report: <base>_water_mask.png, <base>_coastline_mask.png (* 255) and
+    <base>_coastlines.json with the reference's keys."""
+    os.makedirs(output_dir, exist_ok=True)
+    base = os.path.splitext(os.path.basename(str(result["image_path"])))[0]
+    Image.fromarray(result["water_mask"] * 255).save(os.path.join(output_dir, f"{base}_water_mask.png"))
+    Image.fromarray(result["coastline_mask"] * 255).save(os.path.join(output_dir, f"{base}_coastline_mask.png"))
+    doc = {"image_path": result["image_path"], "image_size": result["image_size"], "coastlines": result["coastlines"],
+           "coastline_count": result["coastline_count"], "dilation_size": result.get("dilation_size", 5),
+           "extraction_time": result["extraction_time"]}
+    with open(os.path.join(output_dir, f"{base}_coastlines.json"), "w", encoding="utf-8") as fh:
+        json.dump(doc, fh, indent=2, ensure_ascii=False)
+
+
+class CoastlineExtractor:
+    """Drop-in for the reference's class (predict_coastline.py:336): same constructor and method names, results as described above."""
+
+    def __init__(self, model_path=None, device="cuda", model=None, input_size=512):
+        from .unet import UNet
+        if input_size <= 0 or input_size % 16:
+            raise ValueError("input_size must be a positive multiple of 16 (the reference uses 512)")
+        self.device = torch.device(device)
+        self.input_size = int(input_size)
+        if model is None:
+            model = UNet(n_channels=3, n_classes=2)
+            if model_path and os.path.exists(model_path):
+                model.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True))
+        elif not isinstance(model, UNet):
+            raise TypeError("model must be a UNet (2-class logits); the other models output probabilities")
+        self.model = model.to(self.device).eval()
+
+    # -- network ---------------------------------------------------------------------------------
+    def _z4(self, tiles):
+        from .unet import unet_forward
+        with torch.no_grad(), ops.precision(self.model.precision):
+            return unet_forward(self.model, tiles, save=False, nhwc=True)[0]
+
+    def _predict_resized(self, pil, out=None):
+        """steps 1-3: -> device uint8 [H, W] water mask at the image's own size"""
+        s = self.input_size
+        scene = torch.from_numpy(np.array(data.Resize((s, s))(pil), dtype=np.uint8)).to(self.device)
+        origin = torch.zeros((1, 2), device=self.device, dtype=torch.int32)
+        z4 = self._z4(scene_to_tiles(scene, origin, s))
+        w, h = pil.size
+        same = (h, w) == (s, s)
+        pred = out if same and out is not None else torch.empty((s, s), device=self.device, dtype=torch.uint8)
+        argmax_stitch(z4, origin, 0, pred, self.model.n_classes)
+        return pred if same else resize_nearest(pred, (h, w), out=out)
+
+    def _predict_tiled(self, scene, tile, halo, batch, out=None):
+        h, w, _ = scene.shape
+        plan = tile_plan(h, w, tile, halo)
+        if batch < 1:
+            raise ValueError("batch must be at least 1")
+        origins = torch.from_numpy(plan).to(self.device)
+        mask = out if out is not None else torch.empty((h, w), device=self.device, dtype=torch.uint8)
+        for i in range(0, len(plan), batch):
+            o = origins[i:i + batch]
+            argmax_stitch(self._z4(scene_to_tiles(scene, o, tile)), o, halo, mask, self.model.n_classes)
+        return mask
+
+    def predict_scene(self, image, tile=512, halo=64, batch=8, as_tensor=False):
+        """Water mask at the scene's own resolution, no resize: tiles of side `tile` whose cores (tile - 2 * halo) partition the scene, `batch`
+        tiles per network call.  Each pixel comes from exactly one core.  Beyond the scene the tiles read 0.0 (normalised units)."""
+        pil, _ = _load_rgb(image)
+        scene = _dev_u8(np.array(pil, dtype=np.uint8), self.device)
+        mask = self._predict_tiled(scene, tile, halo, batch)
+        return mask if as_tensor else mask.cpu().numpy()
+
+    # -- reference surface -----------------------------------------------------------------------
+    def extract_coastline_contours(self, water_mask, dilation_kernel_size=5):
+        """-> (coastlines, coastline_mask) as predict_coastline.py:583-618; water_mask: numpy array or device tensor, uint8."""
+        mask = _dev_u8(water_mask, self.device)
+        coast, _, _ = dilate_diff(mask, dilation_kernel_size)
+        coast = coast.cpu().numpy()
+        return coastlines_from_mask(coast), coast
+
+    def extract_coastline_from_image(self, image, output_dir=None, dilation_size=5, tiled=False, tile=512, halo=64, batch=8):
+        ellipse_spans(dilation_size)
+        pil, path = _load_rgb(image)
+        w, h = pil.size
+        # one device buffer for everything that goes back: water mask | coastline mask | the two counts -> one download
+        seg = (h * w + 15) // 16 * 16
+        buf = torch.empty(2 * seg + 16, device=self.device, dtype=torch.uint8)
+        water, coast = buf[:h * w].view(h, w), buf[seg:seg + h * w].view(h, w)
+        counts = buf[2 * seg:2 * seg + 8].view(torch.int32)
+        if tiled:
+            self._predict_tiled(_dev_u8(np.array(pil, dtype=np.uint8), self.device), tile, halo, batch, out=water)
+        else:
+            self._predict_resized(pil, out=water)
+        dilate_diff(water, dilation_size, coast=coast, counts=counts)
+        host = buf.cpu().numpy()
+        water_np = host[:h * w].reshape(h, w).copy()
+        coast_np = host[seg:seg + h * w].reshape(h, w).copy()
+        n_water, n_coast = (int(v) for v in host[2 * seg:2 * seg + 8].view(np.int32))
+        coastlines = coastlines_from_mask(coast_np)
+        result = {"image_path": path if path is not None else "image", "image_size": (w, h), "water_mask": water_np,
+                  "coastline_mask": coast_np, "coastlines": coastlines, "coastline_count": len(coastlines), "dilation_size": int(dilation_size),
+                  "extraction_time": str(datetime.now()), "water_pixels": n_water, "coastline_pixels": n_coast}
+        if output_dir:
+            save_extraction_result(result, output_dir)
+        return result
+
+    save_extraction_result = staticmethod(save_extraction_result)

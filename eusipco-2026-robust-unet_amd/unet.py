@@ -162,16 +162,25 @@ def _head_weights(net):
     return w4, b4
 
 
-def unet_forward(net: UNet, x, save=True):
+def unet_forward(net: UNet, x, save=True, nhwc=False):
+    """nhwc=False: x [N, C, H, W] -> logits [N, classes, H, W] (what UNet.forward returns).  nhwc=True (the prediction path, predict.py):
+    x is the stem's own input, [N, H, W, channels padded to 4] as runet_scene_to_tiles writes it, and the head's NHWC output z4
+    [N, H, W, 4] (n_classes valid) is returned as it stands - no NCHW tensor on either side."""
     tr = net.training
     dev = x.device
     sm = B.Small(dev)
     n = x.shape[0]
     C = {}
-    ops.branches_pay(n, x.shape[2], x.shape[3])
+    c_pad = (net.n_channels + 3) // 4 * 4
+    if nhwc:
+        if x.dim() != 4 or x.shape[3] != c_pad or not x.is_contiguous() or x.dtype != torch.float32:
+            raise ValueError(f"nhwc input must be a contiguous float32 [N, H, W, {c_pad}] tensor")
+        if x.shape[1] % 16 or x.shape[2] % 16:
+            raise ValueError("H and W must be multiples of 16 (four 2x2 poolings)")
+    ops.branches_pay(n, *(x.shape[1:3] if nhwc else x.shape[2:4]))
     if save:
         ops.prefetch_derived()
-    cur = B.to_nhwc_pad(x, (net.n_channels + 3) // 4 * 4)
+    cur = x if nhwc else B.to_nhwc_pad(x, c_pad)
     cats = {}
     for lvl, ch in enumerate(CH, 1):
         _, h, w, _ = cur.shape
@@ -191,6 +200,8 @@ def unet_forward(net: UNet, x, save=True):
         y, C[f"dec{lvl}"] = _block_forward(cats[lvl], getattr(net, f"dec{lvl}"), tr, sm, save=save)
     w4, b4 = _head_weights(net)
     z4 = ops.conv_fwd(y, w4, b4)
+    if nhwc:
+        return z4, None
     _, h, w, _ = z4.shape
     logits = torch.empty((n, net.n_classes, h, w), device=dev, dtype=torch.float32)
     check(lib.runet_nhwc_to_nchw(z4.data_ptr(), 4, logits.data_ptr(), n, net.n_classes, h * w, ops.stream()))

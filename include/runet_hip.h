@@ -542,6 +542,31 @@ int runet_bn_bwd_apply_gelu(const float* dy, int lddy, const float* x, int ldx, 
 int runet_bilinear_nhwc_fwd(const float* x, int ldx, float* y, int ldy, int n_img, int h, int w, int ho, int wo, int c, void* stream);
 int runet_bilinear_nhwc_bwd(const float* dy, int lddy, float* dx, int lddx, int n_img, int h, int w, int ho, int wo, int c, void* stream);
 
+/* ---- prediction: CoastlineExtractor (predict_coastline.py:336-618), everything between the uint8 upload and the two result masks
+ *      (csrc/coastline.hip).  Masks are dense uint8 [h][w]; tile origins are device int32 [n_tiles][2] = (y0, x0), may be negative or overhang.
+ * runet_scene_to_tiles: the to-tensor conversion and Normalize of the transform (:360-362, :387) of a uint8 HWC RGB scene (row_stride bytes per row) cut into T x T
+ *   tiles, written as the stem's padded NHWC input tiles [n_tiles][T][T][4] fp32 (channel 3 = 0): ((float)u8 / 255.0f - mean[c]) / std[c],
+ *   two true divisions, no contraction - the bits of the host transforms.  Pixels outside the scene are 0.0f.
+ * runet_argmax_stitch: torch.argmax(output, dim=1) (:392) read from the head's NHWC output as it stands (z4 [n_tiles][T][T][4], n_classes
+ *   <= 4 valid): the class index of each tile's core (tile minus halo on each side, clipped to the scene) goes into the scene mask.  First
+ *   maximal index; NaN is greater than everything, the first NaN wins (torch's CPU order).
+ * runet_resize_nearest_u8: cv2.resize(..., INTER_NEAREST) (:395-396) by OpenCV's index rule in IEEE double:
+ *   sx = min((int)floor(x * (1.0 / ((double)dw / sw))), sw - 1), likewise for y.  dst 16-byte aligned.
+ * runet_dilate_diff_u8: cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)), cv2.dilate and `dilated_mask - water_mask` (:595-602) in one pass
+ *   over a binary mask (any non-zero byte is water; outputs are 0 / 1): coast = dilate(mask) - mask, optionally dilated itself (NULL: not
+ *   written; must share coast's address modulo 16), counts2 = {water pixels, coastline pixels} (device int32 [2], cleared by the call; integer
+ *   atomics).  Outside the scene counts as 0.  k odd, 1 <= k <= 31.
+ * runet_ellipse_spans: HOST ONLY, no device work - the structuring element as column spans, row i = [j1[i], j2[i]) (k ints each), OpenCV's
+ *   MORPH_ELLIPSE rule: r = c = k / 2, dy = i - r, dx = round_half_even(c * sqrt((r*r - dy*dy) / (double)(r*r))), [max(c - dx, 0), min(c + dx + 1, k)). */
+int runet_ellipse_spans(int k, int* j1, int* j2);
+int runet_scene_to_tiles(const unsigned char* scene, int h, int w, long row_stride, const int* origins, int n_tiles, int tile, float mean0,
+                         float mean1, float mean2, float std0, float std1, float std2, float* tiles, void* stream);
+int runet_argmax_stitch(const float* z4, int n_tiles, int tile, int n_classes, const int* origins, int halo, unsigned char* mask, int h, int w,
+                        void* stream);
+int runet_resize_nearest_u8(const unsigned char* src, int sh, int sw, unsigned char* dst, int dh, int dw, void* stream);
+int runet_dilate_diff_u8(const unsigned char* mask, int h, int w, int k, unsigned char* coast, unsigned char* dilated, int* counts2,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

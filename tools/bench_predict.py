@@ -1,0 +1,219 @@
+"""Prediction path (predict.py, csrc/coastline.hip) on one MI355X:
+
+  * images/s of the reference-size path (predict_coastline.py:387-396, 595-602) on a 512 x 512 image: upload, network, arg-max, dilation
+    difference, one download - without the host-side contour tracing, which is reported on its own;
+  * Mpixel/s of predict_scene on a seeded 4096 x 4096 scene (tile 512, halo 64, batch 8);
+  * each of the four new kernels at 512^2 and 4096^2 against the same step composed from stock torch device ops on the same data, the two
+    alternated in windows of back-to-back calls timed with device events (>= 1 s per variant after a warm-up), with the bytes each kernel
+    must move (from the shapes) over its time;
+  * the post-processing share of one 512^2 prediction.
+
+Not a bench line of the contract (bench.py measures the Robust U-Net training metric); the figures are kept in profiles/predict_postprocess.txt.
+  python tools/bench_predict.py [--what all|path|kernels] [--window 0.5] [--out FILE]
+"""
+import argparse
+import importlib
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+pkg = importlib.import_module("eusipco-2026-robust-unet_amd")
+P = importlib.import_module("eusipco-2026-robust-unet_amd.predict")
+data = importlib.import_module("eusipco-2026-robust-unet_amd.data")
+DEV = torch.device("cuda:0")
+LINES = []
+
+
+def say(s):
+    LINES.append(s)
+    print(s, flush=True)
+
+
+def scene_u8(h, w, seed):
+    """smooth seeded blobs (a darker region on a brighter one) so that masks look like coastlines, not like noise"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[:h, :w].astype(np.float32)
+    f = np.zeros((h, w), np.float32)
+    for _ in range(6):
+        cy, cx, s = rng.uniform(0, h), rng.uniform(0, w), rng.uniform(0.08, 0.25) * min(h, w)
+        f += np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * s * s))
+    water = f > np.median(f)
+    img = np.where(water[..., None], 60, 150) + rng.integers(-20, 21, (h, w, 3))
+    return np.clip(img, 0, 255).astype(np.uint8), water.astype(np.uint8)
+
+
+def windows(fns, window_s):
+    """fns: the variants to alternate.  -> seconds per call of each (two windows per variant, each about window_s of back-to-back calls)."""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    reps = []
+    for f in fns:
+        f(); f()
+        ev[0].record(); f(); ev[1].record(); ev[1].synchronize()
+        reps.append(max(3, math.ceil(window_s / max(ev[0].elapsed_time(ev[1]) * 1e-3, 1e-6))))
+    tot = [0.0] * len(fns)
+    for _ in range(2):
+        for j, f in enumerate(fns):
+            ev[0].record()
+            for _ in range(reps[j]):
+                f()
+            ev[1].record()
+            ev[1].synchronize()
+            tot[j] += ev[0].elapsed_time(ev[1]) * 1e-3
+    return [t / (2 * r) for t, r in zip(tot, reps)], [2 * r for r in reps]
+
+
+def kernel_rows(size, window_s):
+    h = w = size
+    scene, water = scene_u8(h, w, size)
+    sd, wd = torch.from_numpy(scene).to(DEV), torch.from_numpy(water).to(DEV)
+    origin = torch.zeros((1, 2), device=DEV, dtype=torch.int32)
+    mean = torch.tensor(data.IMAGENET_MEAN, device=DEV)
+    std = torch.tensor(data.IMAGENET_STD, device=DEV)
+    z4 = torch.randn((1, h, w, 4), device=DEV)
+    mask = torch.empty((h, w), device=DEV, dtype=torch.uint8)
+    small = wd[::max(1, h // 512), ::max(1, w // 512)].contiguous() if size > 512 else wd
+    dh, dw = (h, w) if size > 512 else (1000, 1531)
+    out = torch.empty((dh, dw), device=DEV, dtype=torch.uint8)
+    inv_x, inv_y = 1.0 / (dw / small.shape[1]), 1.0 / (dh / small.shape[0])
+    ix = torch.clamp(torch.floor(torch.arange(dw, dtype=torch.float64) * inv_x).long(), max=small.shape[1] - 1).to(DEV)
+    iy = torch.clamp(torch.floor(torch.arange(dh, dtype=torch.float64) * inv_y).long(), max=small.shape[0] - 1).to(DEV)
+    k = 5
+    se = torch.from_numpy(P.ellipse_element(k).astype(np.float32)).to(DEV)[None, None]
+    coast, counts = torch.empty_like(wd), torch.empty(2, device=DEV, dtype=torch.int32)
+
+    def t_norm():
+        return F.pad((sd.float().div(255.0) - mean) / std, (0, 1))
+
+    def t_argmax():
+        return z4[0, :, :, :2].argmax(-1).to(torch.uint8)
+
+    def t_resize():
+        return small[iy[:, None], ix[None, :]]
+
+    def t_dilate():
+        d = (F.conv2d(wd[None, None].float(), se, padding=k // 2) > 0).to(torch.uint8)[0, 0]
+        c = d - wd
+        return c, torch.stack([wd.sum(), c.sum()])
+
+    cases = [
+        ("scene_to_tiles", lambda: P.scene_to_tiles(sd, origin, size), t_norm, 3 * h * w + 16 * h * w),
+        ("argmax_stitch", lambda: P.argmax_stitch(z4, origin, 0, mask, 2), t_argmax, 16 * h * w + h * w),
+        (f"resize_nearest {small.shape[0]}^2->{dh}x{dw}", lambda: P.resize_nearest(small, (dh, dw), out=out), t_resize,
+         small.numel() + dh * dw),
+        ("dilate_diff k=5", lambda: P.dilate_diff(wd, k, coast=coast, counts=counts), t_dilate, 2 * h * w),
+    ]
+    # same results first: a faster kernel that computes something else is not faster
+    # (stock device division by a scalar may multiply by the reciprocal: last-bit differences allowed for this one only)
+    assert torch.allclose(P.scene_to_tiles(sd, origin, size)[0], t_norm(), rtol=0, atol=2e-6)
+    assert torch.equal(P.argmax_stitch(z4, origin, 0, mask, 2), t_argmax())
+    assert torch.equal(P.resize_nearest(small, (dh, dw), out=out), t_resize())
+    c_ref, n_ref = t_dilate()
+    c_got, n_got, _ = P.dilate_diff(wd, k, coast=coast, counts=counts)
+    assert torch.equal(c_got, c_ref) and n_got.tolist() == n_ref.tolist()
+    rows = []
+    for name, hip, stock, nbytes in cases:
+        (t_hip, t_stock), (r_hip, r_stock) = windows((hip, stock), window_s)
+        rows.append({"size": size, "kernel": name, "hip_us": round(t_hip * 1e6, 2), "torch_us": round(t_stock * 1e6, 2),
+                     "torch_over_hip": round(t_stock / t_hip, 2), "bytes_min": nbytes, "hip_GBps": round(nbytes / t_hip * 1e-9, 1),
+                     "calls": [r_hip, r_stock]})
+        say(f"  {size:5d}^2  {name:34s} HIP {t_hip * 1e6:9.2f} us  {nbytes / t_hip * 1e-9:8.1f} GB/s   torch ops {t_stock * 1e6:9.2f} us"
+            f"   torch / HIP = {t_stock / t_hip:6.2f}   ({r_hip} / {r_stock} calls)")
+    return rows
+
+
+def path_rows(window_s):
+    torch.manual_seed(0)
+    ex = pkg.CoastlineExtractor(model=pkg.UNet(3, 2), device="cuda:0", input_size=512)
+    scene, _ = scene_u8(512, 512, 1)
+    from PIL import Image
+    pil = Image.fromarray(scene)
+    out = {}
+
+    def device_path():
+        buf = torch.empty(2 * 512 * 512 + 16, device=DEV, dtype=torch.uint8)
+        water, coast = buf[:512 * 512].view(512, 512), buf[512 * 512:2 * 512 * 512].view(512, 512)
+        ex._predict_resized(pil, out=water)
+        P.dilate_diff(water, 5, coast=coast, counts=buf[2 * 512 * 512:2 * 512 * 512 + 8].view(torch.int32))
+        return buf.cpu()
+
+    for _ in range(3):
+        device_path()
+    n, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < max(1.0, 2 * window_s):
+        device_path()
+        n += 1
+    dt = (time.perf_counter() - t0) / n
+    out["reference_size_512"] = {"images_per_s": round(1 / dt, 1), "ms_per_image": round(dt * 1e3, 3), "images": n}
+    say(f"  reference-size path, 512 x 512 image, upload -> masks + counts on the host: {1 / dt:7.1f} images/s ({dt * 1e3:.3f} ms, {n} images)")
+    # the four post-processing kernels of that prediction, back to back on the device
+    sd = torch.from_numpy(scene).to(DEV)
+    origin = torch.zeros((1, 2), device=DEV, dtype=torch.int32)
+    tiles = P.scene_to_tiles(sd, origin, 512)
+    z4 = ex._z4(tiles)
+    water, coast = torch.empty((512, 512), device=DEV, dtype=torch.uint8), torch.empty((512, 512), device=DEV, dtype=torch.uint8)
+    counts = torch.empty(2, device=DEV, dtype=torch.int32)
+
+    def post():
+        P.scene_to_tiles(sd, origin, 512)
+        P.argmax_stitch(z4, origin, 0, water, 2)
+        P.dilate_diff(water, 5, coast=coast, counts=counts)
+
+    (t_post, t_net), _ = windows((post, lambda: ex._z4(tiles)), window_s)
+    out["post_us_512"], out["network_us_512"] = round(t_post * 1e6, 2), round(t_net * 1e6, 2)
+    out["post_share_of_prediction"] = round(t_post / dt, 5)
+    say(f"  of which on the device: network {t_net * 1e3:.3f} ms, normalise + arg-max + dilation difference {t_post * 1e6:.1f} us "
+        f"= {100 * t_post / dt:.2f} % of the prediction")
+    res = ex.extract_coastline_from_image(scene)
+    t0 = time.perf_counter()
+    lines = P.coastlines_from_mask(res["coastline_mask"])
+    out["contours_host_ms_512"] = round((time.perf_counter() - t0) * 1e3, 2)
+    say(f"  host contour tracing + polygon simplification of that coastline mask: {out['contours_host_ms_512']} ms ({len(lines)} coastlines; "
+        f"untrained weights, so the mask is whatever the random network draws)")
+    big, _ = scene_u8(4096, 4096, 2)
+    ex.predict_scene(big[:1024, :1024], as_tensor=True)
+    torch.cuda.synchronize()
+    n, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < max(1.0, 2 * window_s):
+        ex.predict_scene(big, tile=512, halo=64, batch=8, as_tensor=True)
+        torch.cuda.synchronize()
+        n += 1
+    dt = (time.perf_counter() - t0) / n
+    out["predict_scene_4096"] = {"mpixel_per_s": round(4096 * 4096 / dt * 1e-6, 2), "s_per_scene": round(dt, 3), "tiles": len(P.tile_plan(4096, 4096)),
+                                 "scenes": n}
+    say(f"  predict_scene, 4096 x 4096, tile 512 / halo 64 / batch 8 ({out['predict_scene_4096']['tiles']} tiles): "
+        f"{out['predict_scene_4096']['mpixel_per_s']} Mpixel/s ({dt:.3f} s per scene incl. upload, {n} scenes)")
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--what", default="all", choices=("all", "path", "kernels"))
+    ap.add_argument("--window", type=float, default=0.5, help="seconds per timed window (two windows per variant)")
+    ap.add_argument("--out", help="also write the text report here")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_predict.py needs the GPU: there is no CPU path to time")
+    res = {}
+    say(f"prediction path on {torch.cuda.get_device_name(0)}; device-event windows of >= {2 * a.window:.1f} s per variant, alternated")
+    if a.what in ("all", "kernels"):
+        say("kernels (HIP = csrc/coastline.hip; torch ops = the same step composed from stock device ops, results checked equal first):")
+        res["kernels"] = kernel_rows(512, a.window) + kernel_rows(4096, a.window)
+    if a.what in ("all", "path"):
+        say("prediction (fp32, seeded untrained UNet(3, 2)):")
+        res["path"] = path_rows(a.window)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(LINES) + "\n")
+    print(json.dumps({"predict_bench": res}))
+
+
+if __name__ == "__main__":
+    main()
