@@ -889,3 +889,94 @@ def outc_backward(dprob, prob, x, w, sink, pre=""):
     check(lib.runet_outc_bwd(dprob.data_ptr(), prob.data_ptr(), x.data_ptr(), ops.ld(x), w.data_ptr(), dx.data_ptr(), ops.ld(dx), ws.data_ptr(),
                              dw_db.data_ptr(), n * h * wd, c, ops.stream()))
     return dx
+
+
+# =============================================================================== HRNet-Water head and fusion branches (csrc/hrnet.hip)
+# The head's 1x1 convolution and the fusion branches' BatchNorm affine commute with the bilinear interpolation (its weights sum to 1), so they
+# run on the small side of it.  RUNET_NO_FUSED_HR_HEAD=1 / RUNET_NO_FUSED_BN_UPSAMPLE=1: the reference's order on the shared kernels
+# (runet_bn_apply, runet_bilinear_nhwc_*, runet_outc_*) - the A/B partners the fusions are timed against.
+FUSED_HR_HEAD = os.environ.get("RUNET_NO_FUSED_HR_HEAD", "0") != "1"
+FUSED_BN_UPSAMPLE = os.environ.get("RUNET_NO_FUSED_BN_UPSAMPLE", "0") != "1"
+
+
+def _bilinear_nhwc(x, out):
+    n, h, w, c = x.shape
+    check(lib.runet_bilinear_nhwc_fwd(x.data_ptr(), ops.ld(x), out.data_ptr(), ops.ld(out), n, h, w, out.shape[1], out.shape[2], c, ops.stream()))
+    return out
+
+
+def _bilinear_nhwc_backward(dy, h, w):
+    n, ho, wo, c = dy.shape
+    dx = ops.empty_nhwc(n, h, w, c, dy)
+    check(lib.runet_bilinear_nhwc_bwd(dy.data_ptr(), ops.ld(dy), dx.data_ptr(), ops.ld(dx), n, h, w, ho, wo, c, ops.stream()))
+    return dx
+
+
+def hr_head_forward(t, scale, shift, w, b, fused=None):
+    """sigmoid(conv1x1(upsample2(relu(t * scale + shift)))) -> (prob [n, 1, 2h, 2w], saved).  t [n, h, w, c]: the head's raw 3x3 convolution
+    output, w [c] / b [1]: the 1x1 convolution.  Fused: the 1x1 at t's resolution, then the one-channel plane upsampled (saved = None: the
+    backward needs only t and prob).  Unfused: saved = (activation [n, h, w, c], its upsampling [n, 2h, 2w, c])."""
+    n, h, wd, c = t.shape
+    st = ops.stream()
+    if FUSED_HR_HEAD if fused is None else fused:
+        z = torch.empty((n, h, wd), device=t.device, dtype=torch.float32)
+        prob = torch.empty((n, 1, 2 * h, 2 * wd), device=t.device, dtype=torch.float32)
+        check(lib.runet_hr_head_fwd(t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), w.data_ptr(), b.data_ptr(), z.data_ptr(), n, h, wd, c, st))
+        check(lib.runet_up2_sigmoid_fwd(z.data_ptr(), prob.data_ptr(), n, h, wd, st))
+        return prob, None
+    a = bn_apply(t, scale, shift, None, relu=True)
+    up = _bilinear_nhwc(a, ops.empty_nhwc(n, 2 * h, 2 * wd, c, t))
+    prob, _ = outc_forward(up, w, b)
+    return prob, (a, up)
+
+
+def hr_head_backward(dprob, prob, t, scale, shift, w, mean, invstd, saved=None, training=True):
+    """-> (dt [n, h, w, c], out [3c + 1] = (dgamma | dbeta | dw | db)); saved: what hr_head_forward returned (None = the fused path)"""
+    n, h, wd, c = t.shape
+    dev = t.device
+    st = ops.stream()
+    out = torch.empty(3 * c + 1, device=dev, dtype=torch.float32)
+    if saved is None:
+        dz = torch.empty((n, h, wd), device=dev, dtype=torch.float32)
+        check(lib.runet_up2_sigmoid_bwd(dprob.data_ptr(), prob.data_ptr(), dz.data_ptr(), n, h, wd, st))
+        ws = scratch(lib.runet_hr_head_bwd_workspace_floats(n, h, wd, c), dev)
+        check(lib.runet_hr_head_bwd_reduce(dz.data_ptr(), t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), w.data_ptr(), mean.data_ptr(),
+                                           invstd.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), n, h, wd, c, st))
+        use = out if training else zeros(2 * c, dev)
+        dt = ops.empty_nhwc(n, h, wd, c, t)
+        check(lib.runet_hr_head_bwd_apply(dz.data_ptr(), t.data_ptr(), ops.ld(t), w.data_ptr(), dt.data_ptr(), ops.ld(dt), n, h, wd, c, mean.data_ptr(),
+                                          invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), use.data_ptr(), 0, st))
+        return dt, out
+    a, up = saved
+    dup = ops.empty_nhwc(n, 2 * h, 2 * wd, c, t)
+    check(lib.runet_outc_bwd(dprob.data_ptr(), prob.data_ptr(), up.data_ptr(), ops.ld(up), w.data_ptr(), dup.data_ptr(), ops.ld(dup),
+                             _ws(n, 4 * h * wd, c, dev).data_ptr(), out[2 * c:].data_ptr(), n * 4 * h * wd, c, st))
+    da = _bilinear_nhwc_backward(dup, h, wd)
+    dt = bn_backward(da, t, mean, invstd, scale, out[:2 * c], relu_shift=shift, out=da, training=training)
+    return dt, out
+
+
+def bn_bilinear_forward(x, scale, shift, out, s, fused=None):
+    """out [n, s h, s w, 0:c] (an NHWC view, normally a channel slice of the concat buffer) := upsample_s(x * scale + shift), s = 2 or 4"""
+    n, h, w, c = x.shape
+    if tuple(out.shape) != (n, s * h, s * w, c):
+        raise ValueError(f"bn_bilinear_forward: out {tuple(out.shape)} is not {s} x {tuple(x.shape)}")
+    if FUSED_BN_UPSAMPLE if fused is None else fused:
+        check(lib.runet_bn_bilinear_nhwc_fwd(x.data_ptr(), ops.ld(x), out.data_ptr(), ops.ld(out), scale.data_ptr(), shift.data_ptr(), n, h, w, s, c,
+                                             ops.stream()))
+        return out
+    return _bilinear_nhwc(bn_apply(x, scale, shift), out)
+
+
+def bn_bilinear_backward(dy, x, mean, invstd, scale, sums, s, training=True, fused=None):
+    """dy [n, s h, s w, 0:c]: the gradient of bn_bilinear_forward's out; sums [2c] receives (dgamma | dbeta).  -> dx [n, h, w, c]"""
+    n, h, w, c = x.shape
+    if not (FUSED_BN_UPSAMPLE if fused is None else fused):
+        g = _bilinear_nhwc_backward(dy, h, w)
+        return bn_backward(g, x, mean, invstd, scale, sums, out=g, training=training)
+    g = ops.empty_nhwc(n, h, w, c, x)
+    ws = scratch(lib.runet_bilinear_nhwc_bwd_sums_workspace_floats(n, h, w, c), x.device)
+    check(lib.runet_bilinear_nhwc_bwd_sums(dy.data_ptr(), ops.ld(dy), x.data_ptr(), ops.ld(x), mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), ops.ld(g),
+                                           ws.data_ptr(), ws.numel(), sums.data_ptr(), n, h, w, s, c, ops.stream()))
+    use = sums if training else zeros(2 * c, x.device)
+    return bn_bwd_apply(g, x, mean, invstd, scale, use, 0, out=g)

@@ -542,6 +542,47 @@ int runet_bn_bwd_apply_gelu(const float* dy, int lddy, const float* x, int ldx, 
 int runet_bilinear_nhwc_fwd(const float* x, int ldx, float* y, int ldy, int n_img, int h, int w, int ho, int wo, int c, void* stream);
 int runet_bilinear_nhwc_bwd(const float* dy, int lddy, float* dx, int lddx, int n_img, int h, int w, int ho, int wo, int c, void* stream);
 
+/* ---- HRNet-Water baseline (Extended_Baseline_Comparison.py:554-616; csrc/hrnet.hip).  Its convolutions (3x3, 3x3 stride 2 through
+ *      runet_conv2d_general, 1x1), BatchNorm + ReLU and the unfused A/B partners (runet_bilinear_nhwc_*, runet_outc_*) are shared; these are
+ *      the head and the two fusion branches with the 1x1 convolution / the BatchNorm affine moved across the bilinear interpolation (its
+ *      weights sum to 1, so both commute with it).  fp32, NHWC, pixel strides multiples of 4 floats that cover the channels, tensors 16-byte
+ *      aligned, c a multiple of 4 up to 1024.  No float atomics: every sum has a fixed order, results are bitwise reproducible.  The
+ *      source-index rule is runet_bilinear_nhwc_fwd's (ATen align_corners=False) at out = 2 in and 4 in.
+ * runet_hr_head_fwd: the head's BatchNorm + ReLU + Conv2d(c, 1, 1) at the 3x3 convolution's resolution (:599-601 with the 1x1 in front of the
+ *   Upsample): z [n, h, w] = b[0] + sum_c w[c] * relu(t * scale[c] + shift[c]); t [n, h, w, c] (pixel stride ldt) is the convolution's raw output,
+ *   the activated tensor is not written.
+ * runet_up2_sigmoid_fwd: prob [n, 2h, 2w] (dense, the model's [N, 1, H, W] output) = sigmoid(bilinear x2 of z) (:600,:601).
+ * runet_up2_sigmoid_bwd: dz [n, h, w] = the adjoint of that interpolation, in gather form, of dprob * prob * (1 - prob).
+ * runet_hr_head_bwd_reduce: one pass over t and dz -> out [3c + 1] = (dgamma [c] | dbeta [c] | dw [c] | db): the BatchNorm sums
+ *   (sum g * xhat | sum g) of g = dz * w[c] * (t * scale + shift > 0) in the (weight, bias) order of runet_bn_bwd_reduce,
+ *   dw[c] = sum dz * relu(t * scale + shift), db = sum dz.  workspace >= runet_hr_head_bwd_workspace_floats floats (-1: bad shape).
+ * runet_hr_head_bwd_apply: dt [n, h, w, c] (lddt) by runet_bn_bwd_apply's formula with g recomputed from dz, w and t (the activation's gradient
+ *   is never materialised); sums = out[0 : 2c] of the reduce (all-reduced with m_total the global element count, or zeros in eval mode where
+ *   dt = g * scale), m_total as there (0: the local pixel count).
+ * runet_bn_bilinear_nhwc_fwd: a fusion branch's BatchNorm + Upsample (:589-590, :593-594) as y [n, s h, s w, 0:c] (ldy; may be a channel
+ *   slice of the concat buffer, the neighbouring channels are not touched) = scale[c] * bilinear_s(x) + shift[c], x [n, h, w, c] the 1x1
+ *   convolution's raw output, s = 2 or 4.
+ * runet_bilinear_nhwc_bwd_sums: g [n, h, w, 0:c] (ldg) = the gather adjoint of the slice gradient dy [n, s h, s w, 0:c] (lddy) - the gradient of
+ *   the BatchNorm's output - and in the same pass sums [2c] = (sum g * xhat | sum g) against x (mean, invstd: the saved statistics), what
+ *   runet_bn_bwd_reduce(g, x) would compute; runet_bn_bwd_apply(g, x, act = NULL) then gives dx.  workspace >=
+ *   runet_bilinear_nhwc_bwd_sums_workspace_floats floats (-1: bad shape). */
+int runet_hr_head_fwd(const float* t, int ldt, const float* scale, const float* shift, const float* w, const float* b, float* z, int n_img, int h,
+                      int w_, int c, void* stream);
+int runet_up2_sigmoid_fwd(const float* z, float* prob, int n_img, int h, int w_, void* stream);
+int runet_up2_sigmoid_bwd(const float* dprob, const float* prob, float* dz, int n_img, int h, int w_, void* stream);
+long runet_hr_head_bwd_workspace_floats(int n_img, int h, int w_, int c);
+int runet_hr_head_bwd_reduce(const float* dz, const float* t, int ldt, const float* scale, const float* shift, const float* w, const float* mean,
+                             const float* invstd, float* workspace, long workspace_floats, float* out, int n_img, int h, int w_, int c,
+                             void* stream);
+int runet_hr_head_bwd_apply(const float* dz, const float* t, int ldt, const float* w, float* dt, int lddt, int n_img, int h, int w_, int c,
+                            const float* mean, const float* invstd, const float* scale, const float* shift, const float* sums, long m_total,
+                            void* stream);
+int runet_bn_bilinear_nhwc_fwd(const float* x, int ldx, float* y, int ldy, const float* scale, const float* shift, int n_img, int h, int w_, int s,
+                               int c, void* stream);
+long runet_bilinear_nhwc_bwd_sums_workspace_floats(int n_img, int h, int w_, int c);
+int runet_bilinear_nhwc_bwd_sums(const float* dy, int lddy, const float* x, int ldx, const float* mean, const float* invstd, float* g, int ldg,
+                                 float* workspace, long workspace_floats, float* sums, int n_img, int h, int w_, int s, int c, void* stream);
+
 /* ---- prediction: CoastlineExtractor (predict_coastline.py:336-618), everything between the uint8 upload and the two result masks
  *      (csrc/coastline.hip).  Masks are dense uint8 [h][w]; tile origins are device int32 [n_tiles][2] = (y0, x0), may be negative or overhang.
  * runet_scene_to_tiles: the to-tensor conversion and Normalize of the transform (:360-362, :387) of a uint8 HWC RGB scene (row_stride bytes per row) cut into T x T
