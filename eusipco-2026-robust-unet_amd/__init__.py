@@ -7,7 +7,8 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   RobustUNet, ResidualBlock, DilatedBlock, AttentionGate, ChannelAttention, SpatialAttention
   CoastalDataset, prepare_dataset, ModelEvaluator;  DeepLabV3Plus (baseline);  UNet (train_water_segmentation.py's 2-class model);
   SegNet (comne.py's baseline);  YOLOSeg (Main_Final.py's YOLO-style baseline);  SegFormerLite (Extended_Baseline_Comparison.py's
-  transformer baseline);  HRNetWater (the same script's multi-resolution baseline);  CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling)
+  transformer baseline);  HRNetWater (the same script's multi-resolution baseline);  WaterNet / WaterIndexModule (its water-index U-Net baseline);
+  CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
 Sub-modules are imported lazily so that host-only pieces (data, portable_rng) stay usable
@@ -34,7 +35,7 @@ _LAZY = {
     "ModelEvaluator": "evaluator", "FusedAdam": "optim", "bce_loss": "ops", "GradAllReducer": "ddp",
     "TrainStep": "trainer", "fit": "trainer", "UNet": "unet", "cross_entropy": "ops", "bilinear_resize": "ops",
     "SegNet": "segnet", "YOLOSeg": "yolo", "SegFormerLite": "segformer", "CoastlineExtractor": "predict",
-    "HRNetWater": "hrnet",
+    "HRNetWater": "hrnet", "WaterNet": "waternet", "WaterIndexModule": "waternet",
 }
 
 

@@ -980,3 +980,105 @@ def bn_bilinear_backward(dy, x, mean, invstd, scale, sums, s, training=True, fus
                                            ws.data_ptr(), ws.numel(), sums.data_ptr(), n, h, w, s, c, ops.stream()))
     use = sums if training else zeros(2 * c, x.device)
     return bn_bwd_apply(g, x, mean, invstd, scale, use, 0, out=g)
+
+
+
+# =============================================================================== WaterNet front end (csrc/water_index.hip)
+# WaterIndexModule + torch.cat (Extended_Baseline_Comparison.py:378-393, :458): Conv2d(3, 16, 1) -> BatchNorm2d -> ReLU -> Conv2d(16, 4, 1) ->
+# Sigmoid, cat([x, idx]) as the 8-channel NHWC buffer [R, G, B, s0..s3, 0] that enc1's first convolution reads with cin_w = 7.  Fused: every
+# 16-channel tensor is recomputed per pixel in registers (four launches + the shared finalize).  RUNET_NO_FUSED_WATER_INDEX=1: the reference's
+# order on the shared kernels (runet_to_nhwc_pad, the implicit-GEMM 1x1 convolutions, bn_coeff / bn_apply / bn_backward, conv_wgrad, chan_sum,
+# with runet_sigmoid_nhwc_* and runet_copy_nhwc for the sigmoid and the cat) - the A/B partner the fusion is timed against.
+FUSED_WATER_INDEX = os.environ.get("RUNET_NO_FUSED_WATER_INDEX", "0") != "1"
+WI_MID, WI_OUT = 16, 4
+
+
+class WaterIndexParams:
+    """w1 [1, 1, 3, 16] / w2 [1, 1, 16, 4]: the two 1x1 convolutions' weights in their physical (HWIO) layout; bn: BNState"""
+    __slots__ = ("w1", "b1", "bn", "w2", "b2")
+
+    def __init__(self, w1, b1, bn, w2, b2):
+        self.w1, self.b1, self.bn, self.w2, self.b2 = w1, b1, bn, w2, b2
+
+
+def _wi_src(x):
+    n, c, h, w = x.shape
+    if c != 3 or x.dtype != torch.float32:
+        raise ValueError("water_index: expected a float32 image [N, 3, H, W]")
+    return (x.data_ptr(),) + tuple(x.stride()) + (n, h, w)
+
+
+def _wi_coef(p: WaterIndexParams):
+    return (p.w1.data_ptr(), p.b1.data_ptr()), (p.w2.data_ptr(), p.b2.data_ptr())
+
+
+def water_index_forward(x_nchw, p: WaterIndexParams, training, sm: Small, fused=None):
+    """-> (buf [n, h, w, 8] = [R, G, B, s0..s3, 0], ctx for water_index_backward)"""
+    n, _, h, w = x_nchw.shape
+    dev, st = x_nchw.device, ops.stream()
+    src = _wi_src(x_nchw)
+    bn = p.bn
+    buf = torch.empty((n, h, w, 8), device=dev, dtype=torch.float32)
+    if FUSED_WATER_INDEX if fused is None else fused:
+        c1, c2 = _wi_coef(p)
+        scale, shift, mean, invstd = sm.f(WI_MID), sm.f(WI_MID), sm.f(WI_MID), sm.f(WI_MID)
+        if training:
+            nparts = lib.runet_water_index_parts(n, h, w)
+            part = scratch(nparts * WI_MID * 3, dev)
+            check(lib.runet_water_index_stats(*src, *c1, part.data_ptr(), part.numel(), st))
+            check(lib.runet_bn_stats_finalize(part.data_ptr(), nparts, WI_MID, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                              bn.running_var.data_ptr(), bn.nbt.data_ptr(), BN_MOMENTUM, BN_EPS, scale.data_ptr(), shift.data_ptr(),
+                                              mean.data_ptr(), invstd.data_ptr(), st))
+        else:
+            check(lib.runet_bn_finalize(None, None, n, WI_MID, h * w, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                        bn.running_var.data_ptr(), None, BN_MOMENTUM, BN_EPS, 0, scale.data_ptr(), shift.data_ptr(),
+                                        mean.data_ptr(), invstd.data_ptr(), st))
+        check(lib.runet_water_index_fwd(*src, *c1, scale.data_ptr(), shift.data_ptr(), *c2, buf.data_ptr(), 8, st))
+        return buf, dict(x=x_nchw, p=p, scale=scale, shift=shift, mean=mean, invstd=invstd, training=training, fused=True)
+    P = n * h * w
+    x4 = to_nhwc_pad(x_nchw, 4)
+    z = ops.conv_fwd(x4, p.w1, p.b1)
+    scale, shift, mean, invstd, _ = bn_coeff(z, bn, training, sm)
+    a = bn_apply(z, scale, shift, None, relu=True)
+    u = ops.conv_fwd(a, p.w2, p.b2)
+    check(lib.runet_copy_nhwc(x4.data_ptr(), 4, buf.data_ptr(), 8, P, 3, st))
+    check(lib.runet_sigmoid_nhwc_fwd(u.data_ptr(), WI_OUT, buf[..., 3:].data_ptr(), 8, P, WI_OUT, st))
+    check(lib.runet_copy_nhwc(x4[..., 3:].data_ptr(), 4, buf[..., 7:].data_ptr(), 8, P, 1, st))      # the padding channel: zero
+    return buf, dict(x4=x4, z=z, a=a, buf=buf, p=p, scale=scale, shift=shift, mean=mean, invstd=invstd, training=training, fused=False)
+
+
+def water_index_backward(ctx, g):
+    """g [n, h, w, 4]: an NHWC view (any pixel stride, any first channel) of the gradient of channels 3..6 of the forward's buffer.
+    -> out_red [100] = (dgamma [16] | dbeta [16] | dW2 [16][4] | db2 [4]), out_app [64] = (dW1 [3][16] | db1 [16]), physical layouts"""
+    p: WaterIndexParams = ctx["p"]
+    n, h, w, c = g.shape
+    if c != WI_OUT:
+        raise ValueError("water_index_backward: g must have 4 channels")
+    dev, st = g.device, ops.stream()
+    ldg = ops.ld(g)
+    training = ctx["training"]
+    out_red = torch.empty(2 * WI_MID + WI_MID * WI_OUT + WI_OUT, device=dev, dtype=torch.float32)
+    out_app = torch.empty(4 * WI_MID, device=dev, dtype=torch.float32)
+    scale, shift, mean, invstd = ctx["scale"], ctx["shift"], ctx["mean"], ctx["invstd"]
+    if ctx["fused"]:
+        src = _wi_src(ctx["x"])
+        c1, c2 = _wi_coef(p)
+        ws = scratch(lib.runet_water_index_workspace_floats(n, h, w), dev)
+        check(lib.runet_water_index_bwd_reduce(*src, g.data_ptr(), ldg, *c1, scale.data_ptr(), shift.data_ptr(), *c2, mean.data_ptr(), invstd.data_ptr(),
+                                               ws.data_ptr(), ws.numel(), out_red.data_ptr(), st))
+        use = out_red if training else zeros(2 * WI_MID, dev)
+        check(lib.runet_water_index_bwd_apply(*src, g.data_ptr(), ldg, *c1, scale.data_ptr(), shift.data_ptr(), *c2, mean.data_ptr(), invstd.data_ptr(),
+                                              use.data_ptr(), 0, ws.data_ptr(), ws.numel(), out_app.data_ptr(), st))
+        return out_red, out_app
+    P = n * h * w
+    buf, a, z, x4 = ctx["buf"], ctx["a"], ctx["z"], ctx["x4"]
+    du = torch.empty((n, h, w, WI_OUT), device=dev, dtype=torch.float32)
+    check(lib.runet_sigmoid_nhwc_bwd(g.data_ptr(), ldg, buf[..., 3:].data_ptr(), 8, du.data_ptr(), WI_OUT, P, WI_OUT, st))
+    k = 2 * WI_MID
+    ops.conv_wgrad(a, du, 1, 1, out=out_red[k:k + WI_MID * WI_OUT].view(1, 1, WI_MID, WI_OUT))
+    chan_sum(du, out_red[k + WI_MID * WI_OUT:])
+    da = ops.conv_dgrad(du, p.w2)
+    dz = bn_backward(da, z, mean, invstd, scale, out_red[:k], relu_shift=shift, out=da, training=training)
+    ops.conv_wgrad(x4, dz, 1, 1, cin_w=3, out=out_app[:3 * WI_MID].view(1, 1, 3, WI_MID))
+    chan_sum(dz, out_app[3 * WI_MID:])
+    return out_red, out_app

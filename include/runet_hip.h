@@ -583,6 +583,44 @@ long runet_bilinear_nhwc_bwd_sums_workspace_floats(int n_img, int h, int w_, int
 int runet_bilinear_nhwc_bwd_sums(const float* dy, int lddy, const float* x, int ldx, const float* mean, const float* invstd, float* g, int ldg,
                                  float* workspace, long workspace_floats, float* sums, int n_img, int h, int w_, int s, int c, void* stream);
 
+/* ---- WaterNet baseline (Extended_Baseline_Comparison.py:378-473; csrc/water_index.hip).  Its encoder / decoder (3x3 convolutions, BatchNorm +
+ *      ReLU, max-pool, the k2-s2 transposed convolutions, the CBAM channel attention, runet_outc_*) are shared; these are its front end,
+ *      WaterIndexModule + torch.cat (:378-393, :458): Conv2d(3, 16, 1) -> BatchNorm2d(16) -> ReLU -> Conv2d(16, 4, 1) -> Sigmoid, cat([x, idx]).
+ *      Every 16-channel tensor of that chain is recomputed per pixel in registers: z = W1 x + b1, y = z * scale + shift, a = relu(y),
+ *      u = W2 a + b2, s = sigmoid(u).  fp32.  x is the NCHW image [n, 3, h, w] read through its four strides sn, sc, sh, sw (in floats, as
+ *      runet_to_nhwc_pad).  Weights and their gradients in the physical (HWIO) layouts w1 [3][16], w2 [16][4].  No float atomics: every sum has
+ *      a fixed order and the block count depends on the shape only, results are bitwise reproducible.
+ * runet_water_index_parts: rows of the partials / workspace for a shape (-1: bad shape).  runet_water_index_workspace_floats: floats the two
+ *   backward entries need (-1: bad shape).
+ * runet_water_index_stats: part [runet_water_index_parts][16][3] = (count, mean, M2) of z over disjoint pixel sets (two passes per block over
+ *   pixels held in registers), the layout runet_bn_stats_finalize consumes.
+ * runet_water_index_fwd: out [n, h, w, 0:8] (pixel stride ldo, 16-byte aligned) = [R, G, B, s0, s1, s2, s3, 0], two 16-byte stores per pixel;
+ *   scale / shift from runet_bn_stats_finalize (training) or runet_bn_finalize on the running buffers (eval).
+ * runet_water_index_bwd_reduce: g = the gradient of channels 3..6 of that buffer (pointer to channel 3 of its first pixel, pixel stride ldg;
+ *   any 4-byte alignment, e.g. a slice of enc1's data gradient).  du = g s (1 - s), da = W2^T du masked by y > 0.
+ *   out [100] = (dgamma [16] = sum da * xhat | dbeta [16] = sum da | dW2 [16][4] = sum a du | db2 [4] = sum du).
+ * runet_water_index_bwd_apply: dz = runet_bn_bwd_apply's formula on da (sums = out[0 : 32] of the reduce, or zeros in eval mode where
+ *   dz = scale * da; m_total as there, 0: the local pixel count); out [64] = (dW1 [3][16] = sum x dz | db1 [16] = sum dz). */
+int runet_water_index_parts(int n_img, int h, int w_);
+long runet_water_index_workspace_floats(int n_img, int h, int w_);
+int runet_water_index_stats(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* w1, const float* b1,
+                            float* part, long part_floats, void* stream);
+int runet_water_index_fwd(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* w1, const float* b1,
+                          const float* scale, const float* shift, const float* w2, const float* b2, float* out, int ldo, void* stream);
+int runet_water_index_bwd_reduce(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* g, int ldg,
+                                 const float* w1, const float* b1, const float* scale, const float* shift, const float* w2, const float* b2,
+                                 const float* mean, const float* invstd, float* workspace, long workspace_floats, float* out, void* stream);
+int runet_water_index_bwd_apply(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* g, int ldg,
+                                const float* w1, const float* b1, const float* scale, const float* shift, const float* w2, const float* b2,
+                                const float* mean, const float* invstd, const float* sums, long m_total, float* workspace,
+                                long workspace_floats, float* out, void* stream);
+/* The element-wise steps of that chain in the reference's order that no shared kernel offers (the unfused A/B partner,
+ * RUNET_NO_FUSED_WATER_INDEX=1), over c channels of NHWC views that may start at any channel (4-byte accesses):
+ * y = sigmoid(u); du = dy * y * (1 - y); y = x (a channel-slice copy, the torch.cat). */
+int runet_sigmoid_nhwc_fwd(const float* u, int ldu, float* y, int ldy, long pixels, int c, void* stream);
+int runet_sigmoid_nhwc_bwd(const float* dy, int lddy, const float* y, int ldy, float* du, int lddu, long pixels, int c, void* stream);
+int runet_copy_nhwc(const float* x, int ldx, float* y, int ldy, long pixels, int c, void* stream);
+
 /* ---- prediction: CoastlineExtractor (predict_coastline.py:336-618), everything between the uint8 upload and the two result masks
  *      (csrc/coastline.hip).  Masks are dense uint8 [h][w]; tile origins are device int32 [n_tiles][2] = (y0, x0), may be negative or overhang.
  * runet_scene_to_tiles: the to-tensor conversion and Normalize of the transform (:360-362, :387) of a uint8 HWC RGB scene (row_stride bytes per row) cut into T x T
