@@ -235,6 +235,17 @@ CHAN_SUM_ON_SIDE = os.environ.get("RUNET_CHAN_SUM_MAIN", "0") != "1"
 # replaces ran at HBM speed) - opt-in (RUNET_FUSED_SHORTCUT_BN_SUMS=1), kept equal by tests/test_gpu_blocks.py
 FUSED_SHORTCUT_BN_SUMS = os.environ.get("RUNET_FUSED_SHORTCUT_BN_SUMS", "0") == "1"
 FUSED_GATE_BN_SUMS = os.environ.get("RUNET_NO_FUSED_GATE_BN_SUMS", "0") != "1"      # the attention gates' BatchNorm-backward sums taken in ag_bwd2
+# The ResidualBlock's edges folded into its tail kernels (exact: same operations on the same operands, bit-identical results):
+#   out   rb_out also writes a ReLU sign byte per 4 channels and, for the encoder blocks, the 2x2 max pool of its output (runet_rb_out_ex)
+#   bwd1  rb_bwd1 adds the pooled gradient's term in its load of dout and takes the ReLU mask from the sign bytes (runet_rb_bwd1_ex)
+#   bwd3  rb_bwd3 also applies the shortcut BatchNorm's backward, dr written over dv (runet_rb_bwd3_sc)
+# RUNET_NO_FUSED_RB_EDGES=1 restores the separate maxpool2_fwd / maxpool2_bwd / bn_bwd_apply launches.  Read at call time.
+FUSED_RB_EDGES = os.environ.get("RUNET_NO_FUSED_RB_EDGES", "0") != "1"
+RB_EDGE_PARTS = frozenset(("out", "bwd1", "bwd3"))      # tools/rb_edges_step.py narrows this to time one part alone; no other user
+
+
+def _edge(part):
+    return FUSED_RB_EDGES and part in RB_EDGE_PARTS
 
 
 def chan_sum(x, out):
@@ -260,8 +271,9 @@ class RBParams:
         self.cin_w = w1.shape[2]
 
 
-def rb_forward(x, p: RBParams, training, mask=None, save=True, stats_hook=None):
-    """x: [N,H,W,Cx] with Cx >= cin_w (stem: RGB zero-padded to 4).  -> (out [N,H,W,C], ctx or None)"""
+def rb_forward(x, p: RBParams, training, mask=None, save=True, stats_hook=None, pool=False):
+    """x: [N,H,W,Cx] with Cx >= cin_w (stem: RGB zero-padded to 4).  -> (out [N,H,W,C], ctx or None)
+    pool: the block feeds MaxPool2d(2) -> (out, ctx, pooled [N,H/2,W/2,C], winner bytes); ctx keeps the bytes as "pool_idx"."""
     n, h, w, _ = x.shape
     c = p.w1.shape[3]
     cr = p.w0p.shape[3]
@@ -324,15 +336,31 @@ def rb_forward(x, p: RBParams, training, mask=None, save=True, stats_hook=None):
     out = ops.empty_nhwc(n, h, w, c, x)
     if br is not None:
         br.join(r)
-    check(lib.runet_rb_out(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r),
-                           ss.data_ptr() if ss is not None else None, hs.data_ptr() if hs is not None else None, out.data_ptr(),
-                           ops.ld(out), P, hw, c, st))
+    relu_bits = pooled = pool_idx = None
+    if _edge("out"):
+        if save and _edge("bwd1"):
+            relu_bits = torch.empty((P, c // 4), device=x.device, dtype=torch.uint8)
+        if pool:
+            pooled = ops.empty_nhwc(n, h // 2, w // 2, c, x)
+            pool_idx = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.uint8)
+    if relu_bits is not None or pooled is not None:
+        check(lib.runet_rb_out_ex(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r),
+                                  ss.data_ptr() if ss is not None else None, hs.data_ptr() if hs is not None else None, out.data_ptr(),
+                                  ops.ld(out), relu_bits.data_ptr() if relu_bits is not None else None,
+                                  pooled.data_ptr() if pooled is not None else None, ops.ld(pooled) if pooled is not None else 0,
+                                  pool_idx.data_ptr() if pool_idx is not None else None, n, h, w, c, st))
+    else:
+        check(lib.runet_rb_out(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r),
+                               ss.data_ptr() if ss is not None else None, hs.data_ptr() if hs is not None else None, out.data_ptr(),
+                               ops.ld(out), P, hw, c, st))
+    if pool and pooled is None:
+        pooled, pool_idx = maxpool_forward(out)
     if not save:
-        return out, None
+        return (out, None, pooled, pool_idx) if pool else (out, None)
     ctx = dict(x=x, r=r, t1=t1, a1=a1, t2=t2, out=out, mask=use_mask, p=p, training=training, sync=stats_hook if training else None, s1=s1, h1=h1, mean1=mean1, invstd1=invstd1, s2=s2, h2=h2,
                mean2=mean2, invstd2=invstd2, ss=ss, mean_s=mean_s, invstd_s=invstd_s, A=A, B=B, ca=ca, avg=avg, mx=mx, idx=idx,
-               tval=tval, mean_nc=mean_nc, smap=smap, amax=amax, sa=sa, v1=kv1.get("V"), v2=kv2.get("V"))
-    return out, ctx
+               tval=tval, mean_nc=mean_nc, smap=smap, amax=amax, sa=sa, v1=kv1.get("V"), v2=kv2.get("V"), relu_bits=relu_bits, pool_idx=pool_idx)
+    return (out, ctx, pooled, pool_idx) if pool else (out, ctx)
 
 
 def rb_a1(ctx):
@@ -343,8 +371,10 @@ def rb_a1(ctx):
     return bn_apply(ctx["t1"], ctx["s1"], ctx["h1"], ctx["mask"], relu=True)
 
 
-def rb_backward(ctx, dout, sink, pre="", need_dx=True):
-    """Parameter gradients go to `sink` (names prefixed with `pre`).  -> dx or None"""
+def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None):
+    """Parameter gradients go to `sink` (names prefixed with `pre`).  -> dx or None
+    dpool, pool_idx: the gradient of the block's pooled output and the pool's winner bytes; the block's incoming gradient is then
+    dout + maxpool_backward(dpool, pool_idx).  dout is left unmodified unless the edges are unfused (it is then accumulated into)."""
     p: RBParams = ctx["p"]
     x, r, t1, a1, t2, out = ctx["x"], ctx["r"], ctx["t1"], ctx["a1"], ctx["t2"], ctx["out"]
     n, h, w, c = out.shape
@@ -356,8 +386,17 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True):
     A, B, sa, smap, amax = ctx["A"], ctx["B"], ctx["sa"], ctx["smap"], ctx["amax"]
     dv = ops.empty_nhwc(n, h, w, c, x)
     dq = torch.empty(P, device=dev, dtype=torch.float32)
-    check(lib.runet_rb_bwd1(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(),
-                            sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), P, hw, c, st))
+    relu_bits = ctx.get("relu_bits") if _edge("bwd1") else None
+    if dpool is not None and not _edge("bwd1"):
+        dout, dpool = maxpool_backward(dpool, pool_idx, dx=dout), None
+    if dpool is not None or relu_bits is not None:
+        check(lib.runet_rb_bwd1_ex(dout.data_ptr(), ops.ld(dout), dpool.data_ptr() if dpool is not None else None,
+                                   ops.ld(dpool) if dpool is not None else 0, pool_idx.data_ptr() if dpool is not None else None,
+                                   out.data_ptr(), ops.ld(out), relu_bits.data_ptr() if relu_bits is not None else None, t2.data_ptr(), ops.ld(t2),
+                                   A.data_ptr(), B.data_ptr(), sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), n, h, w, c, st))
+    else:
+        check(lib.runet_rb_bwd1(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(),
+                                sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), P, hw, c, st))
     dsm = torch.empty((P, 2), device=dev, dtype=torch.float32)
     dwsa = sink.buf(pre, [("sa.conv1.weight", (7, 7, 2, 1))])
     ws = scratch(lib.runet_sa_conv7_bwd_workspace_floats(n, h, w), dev)
@@ -397,9 +436,27 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True):
         (use2, m_total), (use_s, m_s) = sync.reduce_sums_many([sums2, sums_s], [P, P])
     else:
         use2, m_total = sync.reduce_sums(sums2, P)
-    check(lib.runet_rb_bwd3(dv.data_ptr(), ops.ld(dv), t2.data_ptr(), ops.ld(t2), sa.data_ptr(), dsm.data_ptr(), amax.data_ptr(),
-                            ctx["ca"].data_ptr(), davg.data_ptr(), dmx.data_ptr(), ctx["idx"].data_ptr(), ctx["mean2"].data_ptr(),
-                            ctx["invstd2"].data_ptr(), ctx["s2"].data_ptr(), use2.data_ptr(), dt2.data_ptr(), ops.ld(dt2), P, hw, c, m_total, st))
+    # the shortcut BatchNorm's backward rides in rb_bwd3 (training mode): its sums, over the dv that is final since rb_bwd1, are taken here
+    # instead of after conv1's gradients, and rb_bwd3 writes dr over dv.  Eval mode keeps the separate path.
+    dr = None
+    if p.ws is not None and tr and _edge("bwd3"):
+        if use_s is None:
+            if sums_s_fused is not None:
+                use_s, m_s = sums_s_fused, 0
+            else:
+                sums_s = sink.buf(pre, [("shortcut.1.weight", (c,)), ("shortcut.1.bias", (c,))])
+                bn_bwd_reduce(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], sums_s)
+                use_s, m_s = (sums_s, 0) if sync is None else sync.reduce_sums(sums_s, P)
+        check(lib.runet_rb_bwd3_sc(dv.data_ptr(), ops.ld(dv), t2.data_ptr(), ops.ld(t2), sa.data_ptr(), dsm.data_ptr(), amax.data_ptr(),
+                                   ctx["ca"].data_ptr(), davg.data_ptr(), dmx.data_ptr(), ctx["idx"].data_ptr(), ctx["mean2"].data_ptr(),
+                                   ctx["invstd2"].data_ptr(), ctx["s2"].data_ptr(), use2.data_ptr(), dt2.data_ptr(), ops.ld(dt2), r.data_ptr(),
+                                   ops.ld(r), ctx["mean_s"].data_ptr(), ctx["invstd_s"].data_ptr(), ctx["ss"].data_ptr(), use_s.data_ptr(), m_s,
+                                   P, hw, c, m_total, st))
+        dr = dv
+    else:
+        check(lib.runet_rb_bwd3(dv.data_ptr(), ops.ld(dv), t2.data_ptr(), ops.ld(t2), sa.data_ptr(), dsm.data_ptr(), amax.data_ptr(),
+                                ctx["ca"].data_ptr(), davg.data_ptr(), dmx.data_ptr(), ctx["idx"].data_ptr(), ctx["mean2"].data_ptr(),
+                                ctx["invstd2"].data_ptr(), ctx["s2"].data_ptr(), use2.data_ptr(), dt2.data_ptr(), ops.ld(dt2), P, hw, c, m_total, st))
     # the data gradient first: on the adjoint F(4x4) path it leaves Z = A dy A^T behind, which the weight gradient (side stream) reuses
     kz = {}
     da1 = ops.conv_dgrad(dt2, p.w2, keep_z=kz)
@@ -437,7 +494,9 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True):
     ctx["v1"] = None
     dx = None
     if p.ws is not None:
-        if use_s is not None:
+        if dr is not None:
+            pass                                       # rb_bwd3 has written it
+        elif use_s is not None:
             dr = bn_bwd_apply(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], use_s, m_s, out=dv)
         elif sums_s_fused is not None:
             dr = bn_bwd_apply(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], sums_s_fused if tr else zeros(2 * c, dev), 0, out=dv)

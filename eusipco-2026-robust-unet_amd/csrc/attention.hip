@@ -167,11 +167,16 @@ __global__ __launch_bounds__(256) void sa_conv7_kernel(const float* __restrict__
 
 // out = relu((t2*A+B)*sa + res), res = r*rs + rh (conv shortcut) or r (identity, rs == nullptr)
 // grid (chunks, images): a thread owns 4 channels (coefficients in registers) and every `rows`-th pixel of its chunk
-__global__ __launch_bounds__(TPB) void rb_out_kernel(const float* __restrict__ t2, int ld, const float* __restrict__ A,
-                                                     const float* __restrict__ B, const float* __restrict__ sa,
-                                                     const float* __restrict__ r, int ldr, const float* __restrict__ rs,
-                                                     const float* __restrict__ rh, float* __restrict__ out, int ldo, int HW, int C,
-                                                     int pix_per_chunk) {
+// BITS: relu_bits[p][C/4], one byte per 4 channels, bit e = out[c+e] > 0 from the value just stored (rb_bwd1's ReLU mask without `out`).
+__device__ __forceinline__ unsigned int relu_bits4(const f32x4 o) {
+    return (o[0] > 0.f ? 1u : 0u) | (o[1] > 0.f ? 2u : 0u) | (o[2] > 0.f ? 4u : 0u) | (o[3] > 0.f ? 8u : 0u);
+}
+// The edge kernels stay at the 8 waves per SIMD of the kernels they extend (64 VGPRs; unconstrained they come out at 65-71, one occupancy step lower).
+#define RB_EDGE_WAVES __attribute__((amdgpu_waves_per_eu(8, 8)))
+template <bool BITS>
+__device__ __forceinline__ void rb_out_body(const float* t2, int ld, const float* A, const float* B, const float* sa, const float* r, int ldr,
+                                            const float* rs, const float* rh, float* out, int ldo, unsigned char* bits, int HW, int C,
+                                            int pix_per_chunk) {
     const int cvec = C / 4, rows = TPB / cvec, tid = threadIdx.x;
     const int col = tid % cvec, row = tid / cvec;
     if (row >= rows) return;
@@ -190,6 +195,79 @@ __global__ __launch_bounds__(TPB) void rb_out_kernel(const float* __restrict__ t
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] = fmaxf(o[q], 0.f);
         *reinterpret_cast<f32x4*>(out + (ib + p) * ldo + c) = o;
+        if constexpr (BITS) bits[(ib + p) * cvec + col] = (unsigned char)relu_bits4(o);
+    }
+}
+__global__ __launch_bounds__(TPB) void rb_out_kernel(const float* __restrict__ t2, int ld, const float* __restrict__ A,
+                                                     const float* __restrict__ B, const float* __restrict__ sa,
+                                                     const float* __restrict__ r, int ldr, const float* __restrict__ rs,
+                                                     const float* __restrict__ rh, float* __restrict__ out, int ldo, int HW, int C,
+                                                     int pix_per_chunk) {
+    rb_out_body<false>(t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, nullptr, HW, C, pix_per_chunk);
+}
+__global__ __launch_bounds__(TPB) void rb_out_bits_kernel(const float* __restrict__ t2, int ld, const float* __restrict__ A,
+                                                          const float* __restrict__ B, const float* __restrict__ sa,
+                                                          const float* __restrict__ r, int ldr, const float* __restrict__ rs,
+                                                          const float* __restrict__ rh, float* __restrict__ out, int ldo,
+                                                          unsigned char* __restrict__ bits, int HW, int C, int pix_per_chunk) {
+    rb_out_body<true>(t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, bits, HW, C, pix_per_chunk);
+}
+// rb_out of an encoder block whose output feeds MaxPool2d(2): the thread walks the POOLED pixels of its chunk, computes the four outputs of
+// each 2x2 window with the expression above, stores them to `out`, and stores their maximum (pixel stride ldp) and the winner bytes (dense, C
+// per pooled pixel) as maxpool2_fwd_kernel would from `out`: scan order k = dy*2 + dx, v > m || v != v, first maximum wins.
+// pix_per_chunk counts pooled pixels; HW, W are the full-resolution sizes (both even).
+template <bool BITS>
+__global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_out_pool_kernel(const float* __restrict__ t2, int ld, const float* __restrict__ A,
+                                                          const float* __restrict__ B, const float* __restrict__ sa,
+                                                          const float* __restrict__ r, int ldr, const float* __restrict__ rs,
+                                                          const float* __restrict__ rh, float* __restrict__ out, int ldo,
+                                                          unsigned char* __restrict__ bits, float* __restrict__ pooled, int ldp,
+                                                          unsigned char* __restrict__ pool_idx, int HW, int W, int C, int pix_per_chunk) {
+    const int cvec = C / 4, rows = TPB / cvec, tid = threadIdx.x;
+    const int col = tid % cvec, row = tid / cvec;
+    if (row >= rows) return;
+    const int n = blockIdx.y, c = col * 4;
+    const int HWo = HW >> 2, Wo = W >> 1;
+    const int q0 = blockIdx.x * pix_per_chunk, q1 = min(HWo, q0 + pix_per_chunk);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(A + (long)n * C + c);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(B + (long)n * C + c);
+    f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, h4 = {0.f, 0.f, 0.f, 0.f};
+    if (rs) { s4 = *reinterpret_cast<const f32x4*>(rs + c); h4 = *reinterpret_cast<const f32x4*>(rh + c); }
+    const long ib = (long)n * HW, ibo = (long)n * HWo;
+    for (int q = q0 + row; q < q1; q += rows) {
+        const int ho = q / Wo, wo = q - ho * Wo;
+        const long pb = ib + (long)(ho * 2) * W + wo * 2;
+        f32x4 m;
+        unsigned int sel[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int kr = 0; kr < 4; kr += 2) {              // one window row at a time: two pixels' loads in flight
+            const long pr = pb + (kr >> 1) * W;
+            f32x4 t[2], res[2];
+            float s[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                t[j] = *reinterpret_cast<const f32x4*>(t2 + (pr + j) * ld + c);
+                res[j] = *reinterpret_cast<const f32x4*>(r + (pr + j) * ldr + c);
+                s[j] = sa[pr + j];
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int k = kr + j;
+                f32x4 o = (t[j] * a + b) * s[j] + (res[j] * s4 + h4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
+                *reinterpret_cast<f32x4*>(out + (pr + j) * ldo + c) = o;
+                if constexpr (BITS) bits[(pr + j) * cvec + col] = (unsigned char)relu_bits4(o);
+                if (k == 0) m = o;
+                else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (o[e] > m[e] || o[e] != o[e]) { m[e] = o[e]; sel[e] = k; }
+                }
+            }
+        }
+        *reinterpret_cast<f32x4*>(pooled + (ibo + q) * ldp + c) = m;
+        *reinterpret_cast<unsigned int*>(pool_idx + (ibo + q) * C + c) = sel[0] | (sel[1] << 8) | (sel[2] << 16) | (sel[3] << 24);
     }
 }
 
@@ -213,6 +291,56 @@ __global__ __launch_bounds__(TPB) void rb_bwd1_kernel(const float* __restrict__ 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 d[q] = o[q] > 0.f ? g[q] : 0.f;
+                s += d[q] * (t[q] * a[q] + b[q]);
+            }
+            *reinterpret_cast<f32x4*>(dv + p * lddv + c) = d;
+        }
+        s = grp_sum16(s);
+        if (sub == 0) {
+            const float v = sa[p];
+            dq[p] = s * v * (1.f - v);
+        }
+    }
+}
+
+// rb_bwd1 at the block edges.  POOL: the incoming gradient is g = dout + the pooled gradient's term, rebuilt from (dpool, pidx) by pooled_grad4 -
+// the one addition runet_maxpool2_bwd(accumulate=1) performs on dout, which is left unmodified.  BITS: the ReLU mask comes from rb_out's
+// relu_bits (a byte per 4 channels) instead of a read of `out`; else from `out` (NULL: no ReLU) as in rb_bwd1_kernel.  W: full-resolution width.
+template <bool POOL, bool BITS>
+__global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_bwd1_ex_kernel(const float* __restrict__ dout, int lddo, const float* __restrict__ dpool, int ldp,
+                                                         const unsigned char* __restrict__ pidx, const float* __restrict__ out, int ldo,
+                                                         const unsigned char* __restrict__ bits, const float* __restrict__ t2, int ld,
+                                                         const float* __restrict__ A, const float* __restrict__ B,
+                                                         const float* __restrict__ sa, float* __restrict__ dv, int lddv,
+                                                         float* __restrict__ dq, int HW, int W, int C) {
+    const int sub = threadIdx.x & (LPP - 1);
+    const int cvec = C / 4;
+    const int n = blockIdx.y;            // grid (pixel groups, images): the pixel's place in its image without a 64-bit division
+    for (int pi = blockIdx.x * PPB + (threadIdx.x / LPP); pi < HW; pi += gridDim.x * PPB) {
+        const long p = (long)n * HW + pi;
+        long pq = 0;                     // POOL: the pooled pixel over p and p's place in its window (pooled_grad4)
+        unsigned int pk = 0;
+        if constexpr (POOL) {
+            const int hh = pi / W, ww = pi - hh * W;
+            pq = (long)n * (HW >> 2) + (long)(hh >> 1) * (W >> 1) + (ww >> 1);
+            pk = (unsigned)((hh & 1) * 2 + (ww & 1));
+        }
+        float s = 0.f;
+        for (int c = sub * 4; c < C; c += LPP * 4) {
+            f32x4 g = *reinterpret_cast<const f32x4*>(dout + p * lddo + c);
+            if constexpr (POOL) g += pooled_grad4_at(dpool, ldp, pidx, C, pq, pk, c);
+            f32x4 o = {1.f, 1.f, 1.f, 1.f};
+            unsigned int m = 0xfu;
+            if constexpr (BITS) m = bits[p * cvec + (c >> 2)];
+            else if (out) o = *reinterpret_cast<const f32x4*>(out + p * ldo + c);
+            const f32x4 t = *reinterpret_cast<const f32x4*>(t2 + p * ld + c);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(A + (long)n * C + c);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(B + (long)n * C + c);
+            f32x4 d;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const bool on = BITS ? ((m >> q) & 1u) != 0u : o[q] > 0.f;
+                d[q] = on ? g[q] : 0.f;
                 s += d[q] * (t[q] * a[q] + b[q]);
             }
             *reinterpret_cast<f32x4*>(dv + p * lddv + c) = d;
@@ -452,14 +580,19 @@ __global__ void ca_bwd_final_kernel(const float* __restrict__ sdu, const float* 
 }
 
 // ---- backward 3: dt2 = s2*(du0 - k1 - xhat*k2);  same thread layout as rb_out
-__global__ __launch_bounds__(TPB) void rb_bwd3_kernel(const float* __restrict__ dv, int lddv, const float* __restrict__ t2, int ld,
-                                                      const float* __restrict__ sa, const float* __restrict__ dsm,
-                                                      const int* __restrict__ amax, const float* __restrict__ ca,
-                                                      const float* __restrict__ davg, const float* __restrict__ dmx,
-                                                      const int* __restrict__ idx, const float* __restrict__ mean2,
-                                                      const float* __restrict__ invstd2, const float* __restrict__ s2,
-                                                      const float* __restrict__ sums2, float* __restrict__ dt2, int lddt, int HW, int C,
-                                                      int pix_per_chunk, float inv_m) {
+// SC (blocks with a convolution shortcut): the shortcut BatchNorm's backward rides along.  dv is that BatchNorm's incoming gradient and r its
+// input, so the thread also loads r and writes dr = bn_bwd_dx(dv, ...) over the dv element it has just read - bn_bwd_apply_kernel<4> without
+// activation or mask, by the same helpers in the same order (its read of dv and its launch are saved).  sums_s must be final before the launch.
+struct RbScArgs {
+    const float* r; int ldr;
+    const float *mean_s, *invstd_s, *scale_s, *sums_s;
+    float inv_m_s;
+};
+template <bool SC>
+__device__ __forceinline__ void rb_bwd3_body(const float* dv, float* dvw, int lddv, const float* t2, int ld, const float* sa, const float* dsm,
+                                             const int* amax, const float* ca, const float* davg, const float* dmx, const int* idx,
+                                             const float* mean2, const float* invstd2, const float* s2, const float* sums2, float* dt2,
+                                             int lddt, int HW, int C, int pix_per_chunk, float inv_m, const RbScArgs& sc) {
     const int cvec = C / 4, rows = TPB / cvec, tid = threadIdx.x;
     const int col = tid % cvec, row = tid / cvec;
     if (row >= rows) return;
@@ -469,6 +602,7 @@ __global__ __launch_bounds__(TPB) void rb_bwd3_kernel(const float* __restrict__ 
     // dt2 = s2*( du*ca + davg/HW + [p==idx]*dmx - k1 - (t2-mean)*invstd*k2 ) = du*(s2*ca) + t2*e + f + [p==idx]*(s2*dmx)
     float cc[4], e[4], f[4], dmxs[4];
     int ix[4];
+    float scs[4], cas[4], cbs[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int k = n * C + c + q;
@@ -478,11 +612,17 @@ __global__ __launch_bounds__(TPB) void rb_bwd3_kernel(const float* __restrict__ 
         f[q] = s * (davg[k] * invHW - k1 + mean2[c + q] * is * k2);
         dmxs[q] = s * dmx[k];
         ix[q] = idx[k];
+        if constexpr (SC) {
+            scs[q] = sc.scale_s[c + q];
+            bn_bwd_coef(scs[q], sc.mean_s[c + q], sc.invstd_s[c + q], sc.sums_s[c + q], sc.sums_s[C + c + q], sc.inv_m_s, cas[q], cbs[q]);
+        }
     }
     const long ib = (long)n * HW;
     for (int p = p0 + row; p < p1; p += rows) {
         const f32x4 d = *reinterpret_cast<const f32x4*>(dv + (ib + p) * lddv + c);
         const f32x4 t = *reinterpret_cast<const f32x4*>(t2 + (ib + p) * ld + c);
+        f32x4 rv;
+        if constexpr (SC) rv = *reinterpret_cast<const f32x4*>(sc.r + (ib + p) * sc.ldr + c);
         const float v = sa[ib + p], g0 = dsm[(ib + p) * 2] * invC, g1 = dsm[(ib + p) * 2 + 1];
         const int am = amax[ib + p];
         f32x4 r;
@@ -492,7 +632,36 @@ __global__ __launch_bounds__(TPB) void rb_bwd3_kernel(const float* __restrict__ 
             r[q] = du * cc[q] + t[q] * e[q] + f[q] + (ix[q] == p ? dmxs[q] : 0.f);
         }
         *reinterpret_cast<f32x4*>(dt2 + (ib + p) * lddt + c) = r;
+        if constexpr (SC) {
+            f32x4 dr;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) dr[q] = bn_bwd_dx(d[q], scs[q], rv[q], cas[q], cbs[q]);
+            *reinterpret_cast<f32x4*>(dvw + (ib + p) * lddv + c) = dr;
+        }
     }
+}
+__global__ __launch_bounds__(TPB) void rb_bwd3_kernel(const float* __restrict__ dv, int lddv, const float* __restrict__ t2, int ld,
+                                                      const float* __restrict__ sa, const float* __restrict__ dsm,
+                                                      const int* __restrict__ amax, const float* __restrict__ ca,
+                                                      const float* __restrict__ davg, const float* __restrict__ dmx,
+                                                      const int* __restrict__ idx, const float* __restrict__ mean2,
+                                                      const float* __restrict__ invstd2, const float* __restrict__ s2,
+                                                      const float* __restrict__ sums2, float* __restrict__ dt2, int lddt, int HW, int C,
+                                                      int pix_per_chunk, float inv_m) {
+    rb_bwd3_body<false>(dv, nullptr, lddv, t2, ld, sa, dsm, amax, ca, davg, dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, HW, C, pix_per_chunk,
+                        inv_m, RbScArgs{});
+}
+// dv is read and written (each thread its own elements): not __restrict__
+__global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_bwd3_sc_kernel(float* dv, int lddv, const float* __restrict__ t2, int ld,
+                                                         const float* __restrict__ sa, const float* __restrict__ dsm,
+                                                         const int* __restrict__ amax, const float* __restrict__ ca,
+                                                         const float* __restrict__ davg, const float* __restrict__ dmx,
+                                                         const int* __restrict__ idx, const float* __restrict__ mean2,
+                                                         const float* __restrict__ invstd2, const float* __restrict__ s2,
+                                                         const float* __restrict__ sums2, float* __restrict__ dt2, int lddt, int HW, int C,
+                                                         int pix_per_chunk, float inv_m, RbScArgs sc) {
+    rb_bwd3_body<true>(dv, dv, lddv, t2, ld, sa, dsm, amax, ca, davg, dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, HW, C, pix_per_chunk, inv_m,
+                       sc);
 }
 
 // --------------------------------------------------------------------------------- attention gate
@@ -775,6 +944,73 @@ extern "C" int runet_rb_bwd1(const float* dout, int lddo, const float* out, int 
     RUNET_CHECK_LAUNCH();
 }
 
+// runet_rb_out that also leaves what the block's edges need: relu_bits (rb_bwd1's mask) and / or the 2x2 max pool of `out`.
+extern "C" int runet_rb_out_ex(const float* t2, int ld, const float* A, const float* B, const float* sa, const float* r, int ldr,
+                               const float* rs, const float* rh, float* out, int ldo, unsigned char* relu_bits, float* pooled, int ldp,
+                               unsigned char* pool_idx, int n_img, int h, int w, int c, void* stream) {
+    RUNET_REQUIRE(t2 && A && B && sa && r && out, "null pointer");
+    REQ_C4(c);
+    RUNET_REQUIRE(n_img >= 1 && h >= 1 && w >= 1, "bad shape");
+    RUNET_REQUIRE((pooled == nullptr) == (pool_idx == nullptr), "pooled and pool_idx come together");
+    RUNET_REQUIRE((long)h * w < (1L << 31), "image too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int hw = h * w;
+    int ppc;
+    if (!pooled) {
+        const int chunks = stream_chunks(hw, c, ppc);
+        if (relu_bits)
+            hipLaunchKernelGGL(rb_out_bits_kernel, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, relu_bits, hw, c, ppc);
+        else
+            hipLaunchKernelGGL(rb_out_kernel, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, hw, c, ppc);
+        RUNET_CHECK_LAUNCH();
+    }
+    RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0, "h and w must be even");
+    RUNET_REQUIRE(ldp >= c && ldp % 4 == 0, "bad pooled stride");
+    // a block's share of the tensor as in the plain form, counted in 2x2 windows
+    const int rows = TPB / (c / 4), hwo = hw / 4;
+    long per_img = ((long)hw * c + 16383) / 16384;
+    const long maxc = (hwo + rows - 1) / rows;
+    if (per_img > maxc) per_img = maxc;
+    if (per_img > 4096) per_img = 4096;
+    if (per_img < 1) per_img = 1;
+    ppc = (int)((hwo + per_img - 1) / per_img);
+    const int chunks = (hwo + ppc - 1) / ppc;
+    if (relu_bits)
+        hipLaunchKernelGGL(rb_out_pool_kernel<true>, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, relu_bits, pooled,
+                           ldp, pool_idx, hw, w, c, ppc);
+    else
+        hipLaunchKernelGGL(rb_out_pool_kernel<false>, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, nullptr, pooled,
+                           ldp, pool_idx, hw, w, c, ppc);
+    RUNET_CHECK_LAUNCH();
+}
+
+// runet_rb_bwd1 whose incoming gradient is dout + the gradient of the 2x2 max pool behind the block (dpool, pool_idx; dpool NULL: none) and
+// whose ReLU mask comes from relu_bits when given (else from out; both NULL: no ReLU).
+extern "C" int runet_rb_bwd1_ex(const float* dout, int lddo, const float* dpool, int ldp, const unsigned char* pool_idx, const float* out, int ldo,
+                                const unsigned char* relu_bits, const float* t2, int ld, const float* A, const float* B, const float* sa,
+                                float* dv, int lddv, float* dq, int n_img, int h, int w, int c, void* stream) {
+    RUNET_REQUIRE(dout && t2 && A && B && sa && dv && dq, "null pointer");
+    REQ_C4(c);
+    RUNET_REQUIRE(n_img >= 1 && h >= 1 && w >= 1 && (long)h * w < (1L << 31), "bad shape");
+    RUNET_REQUIRE((dpool == nullptr) == (pool_idx == nullptr), "dpool and pool_idx come together");
+    RUNET_REQUIRE(!dpool || (h % 2 == 0 && w % 2 == 0 && ldp >= c && ldp % 4 == 0), "pooled gradient: h and w must be even, stride a multiple of 4");
+    hipStream_t st = (hipStream_t)stream;
+    const int hw = h * w;
+    const long pixels = (long)n_img * hw;
+    int gx = px_grid(hw);                                   // about px_grid(pixels) blocks in all, as (pixel groups, images)
+    if (gx > 8192 / n_img) gx = 8192 / n_img > 0 ? 8192 / n_img : 1;
+    const dim3 grid(gx, n_img);
+#define RB_BWD1_EX(POOL, BITS)                                                                                                              \
+    hipLaunchKernelGGL((rb_bwd1_ex_kernel<POOL, BITS>), grid, dim3(TPB), 0, st, dout, lddo, dpool, ldp, pool_idx, out, ldo, relu_bits, t2, ld, A, B, \
+                       sa, dv, lddv, dq, hw, w, c)
+    if (dpool && relu_bits) RB_BWD1_EX(true, true);
+    else if (dpool) RB_BWD1_EX(true, false);
+    else if (relu_bits) RB_BWD1_EX(false, true);
+    else hipLaunchKernelGGL(rb_bwd1_kernel, dim3(px_grid(pixels)), dim3(TPB), 0, st, dout, lddo, out, ldo, t2, ld, A, B, sa, dv, lddv, dq, pixels, hw, c);
+#undef RB_BWD1_EX
+    RUNET_CHECK_LAUNCH();
+}
+
 extern "C" long runet_sa_conv7_bwd_workspace_floats(int n_img, int h, int w) { return (long)n_img * cdiv(h, 16) * cdiv(w, 16) * 98; }
 
 extern "C" int runet_sa_conv7_bwd(const float* smap, const float* dq, const float* wp, float* dsm, float* dwp, float* workspace,
@@ -872,6 +1108,25 @@ extern "C" int runet_rb_bwd3(const float* dv, int lddv, const float* t2, int ld,
     const int chunks = stream_chunks(hw, c, ppc);
     hipLaunchKernelGGL(rb_bwd3_kernel, dim3(chunks, (int)(pixels / hw)), dim3(TPB), 0, (hipStream_t)stream, dv, lddv, t2, ld, sa, dsm, amax, ca, davg,
                        dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, hw, c, ppc, 1.0f / (float)(m_total > 0 ? m_total : pixels));
+    RUNET_CHECK_LAUNCH();
+}
+
+// runet_rb_bwd3 of a block with a convolution shortcut that also applies the shortcut BatchNorm's backward: dv (read) becomes dr (written in
+// place) = runet_bn_bwd_apply(dv, r, ..., sums_s, m_total_s) without activation or mask.
+extern "C" int runet_rb_bwd3_sc(float* dv, int lddv, const float* t2, int ld, const float* sa, const float* dsm, const int* amax, const float* ca,
+                                const float* davg, const float* dmx, const int* idx, const float* mean2, const float* invstd2, const float* s2,
+                                const float* sums2, float* dt2, int lddt, const float* r, int ldr, const float* mean_s, const float* invstd_s,
+                                const float* scale_s, const float* sums_s, long m_total_s, long pixels, int hw, int c, long m_total, void* stream) {
+    RUNET_REQUIRE(dv && t2 && sa && dsm && amax && ca && davg && dmx && idx && mean2 && invstd2 && s2 && sums2 && dt2, "null pointer");
+    RUNET_REQUIRE(r && mean_s && invstd_s && scale_s && sums_s, "null pointer (shortcut BatchNorm)");
+    REQ_C4(c);
+    RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
+    RUNET_REQUIRE(ldr >= c && ldr % 4 == 0, "bad stride");
+    int ppc;
+    const int chunks = stream_chunks(hw, c, ppc);
+    const RbScArgs sc{r, ldr, mean_s, invstd_s, scale_s, sums_s, 1.0f / (float)(m_total_s > 0 ? m_total_s : pixels)};
+    hipLaunchKernelGGL(rb_bwd3_sc_kernel, dim3(chunks, (int)(pixels / hw)), dim3(TPB), 0, (hipStream_t)stream, dv, lddv, t2, ld, sa, dsm, amax, ca, davg,
+                       dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, hw, c, ppc, 1.0f / (float)(m_total > 0 ? m_total : pixels), sc);
     RUNET_CHECK_LAUNCH();
 }
 

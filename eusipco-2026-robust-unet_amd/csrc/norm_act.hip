@@ -376,18 +376,7 @@ __global__ __launch_bounds__(TPB) void bn_apply_gelu_kernel(const float* __restr
 // (dense, C per pooled pixel); the full-resolution g is rebuilt in registers exactly as runet_maxpool2_bwd(accumulate=0) would write it:
 // g(h, w) = pidx[h/2, w/2] == (h&1)*2 + (w&1) ? dy[h/2, w/2] : 0.  W is the full-resolution width.  The POOL instances below take pidx / W
 // in the act / ldact argument slots (they have no saved activation: ReLU from x), so the other instances keep their argument list and code.
-__device__ __forceinline__ f32x4 pooled_grad4(const float* __restrict__ dy, int lddy, const unsigned char* __restrict__ pidx, int W, int C,
-                                              int n, int HW, int p, int c) {
-    const int hh = p / W, ww = p - hh * W;
-    const long q = (long)n * (HW >> 2) + (long)(hh >> 1) * (W >> 1) + (ww >> 1);
-    const f32x4 t = *reinterpret_cast<const f32x4*>(dy + q * lddy + c);
-    const unsigned int s = *reinterpret_cast<const unsigned int*>(pidx + q * C + c);
-    const unsigned int k = (unsigned)((hh & 1) * 2 + (ww & 1));
-    f32x4 g;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) g[e] = (((s >> (8 * e)) & 0xff) == k) ? t[e] : 0.f;
-    return g;
-}
+// pooled_grad4 itself is in runet_common.h (the residual-block tail's backward shares it).
 
 // partial sums of g and g*xhat per channel; g = dy [* mask[n,c] * (act > 0)]   (ACT_LEAKY: leaky_grad(dy, x * rscale + rshift, slope))
 template <int VEC, bool POOL = false, int ACT = ACT_RELU>

@@ -81,6 +81,28 @@ __device__ __forceinline__ float bn_bwd_dx(const float gg, const float sc, const
     return __builtin_fmaf(gg, sc, __builtin_fmaf(x, ca, cb));
 }
 
+// The full-resolution gradient behind a 2x2 max-pool, rebuilt in registers from the POOLED gradient dy [n, H/2, W/2] (pixel stride lddy) and
+// the winner bytes pidx (dense, C per pooled pixel), exactly as runet_maxpool2_bwd(accumulate=0) would write it:
+// g(h, w) = pidx[h/2, w/2] == (h&1)*2 + (w&1) ? dy[h/2, w/2] : 0.  W is the full-resolution width, p the pixel inside image n, c the first of
+// the thread's 4 channels.  Shared by the BatchNorm-backward POOL instances (norm_act.hip) and rb_bwd1 (attention.hip).
+// pooled_grad4_at: the same from the pooled pixel q (over all images) and the position k = (h&1)*2 + (w&1) in its window, for callers that
+// visit several channel groups of one pixel.
+__device__ __forceinline__ f32x4 pooled_grad4_at(const float* __restrict__ dy, int lddy, const unsigned char* __restrict__ pidx, int C, long q,
+                                                 unsigned int k, int c) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(dy + q * lddy + c);
+    const unsigned int s = *reinterpret_cast<const unsigned int*>(pidx + q * C + c);
+    f32x4 g;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[e] = (((s >> (8 * e)) & 0xff) == k) ? t[e] : 0.f;
+    return g;
+}
+__device__ __forceinline__ f32x4 pooled_grad4(const float* __restrict__ dy, int lddy, const unsigned char* __restrict__ pidx, int W, int C,
+                                              int n, int HW, int p, int c) {
+    const int hh = p / W, ww = p - hh * W;
+    const long q = (long)n * (HW >> 2) + (long)(hh >> 1) * (W >> 1) + (ww >> 1);
+    return pooled_grad4_at(dy, lddy, pidx, C, q, (unsigned)((hh & 1) * 2 + (ww & 1)), c);
+}
+
 // GELU, the exact erf form (nn.GELU(), SegFormer-Lite's patch embeddings and MixFFN): ATen's expressions, shared by the BatchNorm + GELU
 // kernels (norm_act.hip) and the depthwise convolution + GELU kernels (dwconv.hip).  gelu_grad(g, z) = g * GELU'(z).
 __device__ __forceinline__ float gelu_f(const float z) { return z * 0.5f * (1.0f + erff(z * 0.70710678118654752440f)); }

@@ -508,14 +508,13 @@ def _net_forward(net: RobustUNet, x, save, want_logit=False):
     rbs = net._rbs()
     masks = _draw_masks(net, rbs, n, dev) if tr else {k: None for k in rbs}
     C = {}
-    x1, C["inc"] = B.rb_forward(x0, rbs["inc"].handles(), tr, masks["inc"], save, hook)
+    # the four encoder blocks leave their 2x2 max pool (values and winner bytes) behind themselves: rb_forward(pool=True)
+    x1, C["inc"], pooled, C["pool1"] = B.rb_forward(x0, rbs["inc"].handles(), tr, masks["inc"], save, hook, pool=True)
     skips = [x1]
-    cur = x1
     for lvl in (1, 2, 3):
-        pooled, C[f"pool{lvl}"] = B.maxpool_forward(cur)
-        cur, C[f"down{lvl}.1"] = B.rb_forward(pooled, rbs[f"down{lvl}.1"].handles(), tr, masks[f"down{lvl}.1"], save, hook)
+        cur, C[f"down{lvl}.1"], pooled, C[f"pool{lvl + 1}"] = B.rb_forward(pooled, rbs[f"down{lvl}.1"].handles(), tr, masks[f"down{lvl}.1"], save,
+                                                                           hook, pool=True)
         skips.append(cur)
-    pooled, C["pool4"] = B.maxpool_forward(cur)
     xd, C["bottleneck.1"] = B.dilated_forward(pooled, net.bottleneck[1].handles(), tr, save, hook)
     y, C["bottleneck.2"] = B.rb_forward(xd, rbs["bottleneck.2"].handles(), tr, masks["bottleneck.2"], save, hook)
     for lvl in (4, 3, 2, 1):
@@ -604,12 +603,11 @@ def _net_backward(C, dprob, sink, done):
     done("bottleneck.2")
     dpool = B.dilated_backward(C["bottleneck.1"], dxd, sink, pre="bottleneck.1.")
     done("bottleneck.1")
-    dcur = B.maxpool_backward(dpool, C["pool4"], dx=dskip[4])
+    # an encoder block's incoming gradient is its skip gradient + the gradient of the pool behind it: rb_backward adds the two
     for lvl in (3, 2, 1):
-        dpool = B.rb_backward(C[f"down{lvl}.1"], dcur, sink, pre=f"down{lvl}.1.")
+        dpool = B.rb_backward(C[f"down{lvl}.1"], dskip[lvl + 1], sink, pre=f"down{lvl}.1.", dpool=dpool, pool_idx=C[f"pool{lvl + 1}"])
         done(f"down{lvl}.1")
-        dcur = B.maxpool_backward(dpool, C[f"pool{lvl}"], dx=dskip[lvl])
-    B.rb_backward(C["inc"], dcur, sink, pre="inc.", need_dx=False)
+    B.rb_backward(C["inc"], dskip[1], sink, pre="inc.", need_dx=False, dpool=dpool, pool_idx=C["pool1"])
     done("inc")
 
 

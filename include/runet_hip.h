@@ -157,6 +157,19 @@ int runet_rb_out(const float* t2, int ld, const float* A, const float* B, const 
 /* dv = dout * (out > 0) (out NULL: dv = dout, no ReLU behind the attention), dq[p] = (sum_c dv*u) * sa*(1-sa) with u = t2*A+B */
 int runet_rb_bwd1(const float* dout, int lddo, const float* out, int ldo, const float* t2, int ld, const float* A, const float* B,
                   const float* sa, float* dv, int lddv, float* dq, long pixels, int hw, int c, void* stream);
+/* The block's edges folded into its tail (the encoder blocks of Main_Final.py:235-249 feed nn.MaxPool2d(2); :194 is the ReLU):
+ * runet_rb_out_ex = runet_rb_out, plus
+ *   relu_bits [pixels][c/4] (or NULL): one byte per 4 channels, bit e set when out[p, 4j+e] > 0 - runet_rb_bwd1_ex's ReLU mask;
+ *   pooled [n, h/2, w/2, c] (pixel stride ldp) + pool_idx (or both NULL): runet_maxpool2_fwd(out), same values and winner bytes
+ *   (dense, c per pooled pixel, byte k = dy*2 + dx of the first maximum).
+ * runet_rb_bwd1_ex = runet_rb_bwd1 on dout + runet_maxpool2_bwd(dpool, pool_idx) (dpool NULL: on dout alone; dout is not modified),
+ *   the ReLU mask from relu_bits when given, else from out (both NULL: no ReLU). */
+int runet_rb_out_ex(const float* t2, int ld, const float* A, const float* B, const float* sa, const float* r, int ldr, const float* rs,
+                    const float* rh, float* out, int ldo, unsigned char* relu_bits, float* pooled, int ldp, unsigned char* pool_idx, int n_img,
+                    int h, int w, int c, void* stream);
+int runet_rb_bwd1_ex(const float* dout, int lddo, const float* dpool, int ldp, const unsigned char* pool_idx, const float* out, int ldo,
+                     const unsigned char* relu_bits, const float* t2, int ld, const float* A, const float* B, const float* sa, float* dv,
+                     int lddv, float* dq, int n_img, int h, int w, int c, void* stream);
 long runet_sa_conv7_bwd_workspace_floats(int n_img, int h, int w);
 int runet_sa_conv7_bwd(const float* smap, const float* dq, const float* wp, float* dsm, float* dwp, float* workspace, int n_img, int h,
                        int w, void* stream);
@@ -175,6 +188,13 @@ int runet_ca_bwd(const float* sdu, const float* sdut, const float* s2, const flo
 int runet_rb_bwd3(const float* dv, int lddv, const float* t2, int ld, const float* sa, const float* dsm, const int* amax, const float* ca,
                   const float* davg, const float* dmx, const int* idx, const float* mean2, const float* invstd2, const float* s2,
                   const float* sums2, float* dt2, int lddt, long pixels, int hw, int c, long m_total, void* stream);
+/* runet_rb_bwd3 of a block with a convolution shortcut (Main_Final.py:170-174) that also applies the shortcut BatchNorm's backward: dv, that
+ * BatchNorm's incoming gradient, is overwritten with dr = runet_bn_bwd_apply(dv, r, mean_s, invstd_s, scale_s, sums_s, m_total_s) (no
+ * activation, no mask); sums_s as runet_bn_bwd_reduce(dv, r) left them (or all-reduced, or zeros in eval mode). */
+int runet_rb_bwd3_sc(float* dv, int lddv, const float* t2, int ld, const float* sa, const float* dsm, const int* amax, const float* ca,
+                     const float* davg, const float* dmx, const int* idx, const float* mean2, const float* invstd2, const float* s2,
+                     const float* sums2, float* dt2, int lddt, const float* r, int ldr, const float* mean_s, const float* invstd_s,
+                     const float* scale_s, const float* sums_s, long m_total_s, long pixels, int hw, int c, long m_total, void* stream);
 
 /* ---- AttentionGate (Main_Final.py:120-148): psi conv (F_int -> 1) and the gating multiply ---- */
 int runet_ag_psi(const float* g1, int ldg, const float* x1, int ldx, const float* sg, const float* hg, const float* sx, const float* hx,
