@@ -1141,3 +1141,197 @@ def water_index_backward(ctx, g):
     ops.conv_wgrad(x4, dz, 1, 1, cin_w=3, out=out_app[:3 * WI_MID].view(1, 1, 3, WI_MID))
     chan_sum(dz, out_app[3 * WI_MID:])
     return out_red, out_app
+
+
+# =============================================================================== MSWNet's MultiScaleBlock (csrc/multiscale.hip)
+# MultiScaleBlock (Extended_Baseline_Comparison.py:479-494): cat(1x1, 3x3, 5x5, maxpool3 -> 1x1), each Conv2d -> BatchNorm2d -> ReLU at a quarter of
+# the output channels.  ms_block_*: the four convolutions write channel slices of one buffer t, the four BatchNorms' vectors sit back to back in
+# one vector each, so BatchNorm + ReLU and its backward run once over all channels.  ms_stem_*: the first level, MultiScaleBlock(3, 64), fused
+# over the NCHW image (t is recomputed per pixel and never written).  RUNET_NO_FUSED_MS_STEM=1: the first level through ms_block_* on a
+# 4-channel NHWC copy of the image - the A/B partner the fusion is timed against (tools/mswnet_step.py; the A/B run that decides this default
+# is not measured yet: DESIGN.md section 3.12).
+FUSED_MS_STEM = os.environ.get("RUNET_NO_FUSED_MS_STEM", "0") != "1"
+MS_STEM_C, MS_STEM_Q = 64, 16
+
+
+class MSBlockParams:
+    """w, b: the four convolutions' weights (HWIO: [1,1,ci,q], [3,3,ci,q], [5,5,ci,q], [1,1,ci,q]) and biases in branch order; bn: four BNState"""
+    __slots__ = ("w", "b", "bn")
+
+    def __init__(self, w, b, bn):
+        self.w, self.b, self.bn = w, b, bn
+
+
+def maxpool3s1_forward(x, want_idx=True, out=None):
+    """MaxPool2d(3, stride 1, padding 1) of an NHWC view -> (y, winner bytes [n, h, w, c] or None)"""
+    n, h, w, c = x.shape
+    y = ops.empty_nhwc(n, h, w, c, x) if out is None else out
+    idx = torch.empty((n, h, w, c), device=x.device, dtype=torch.uint8) if want_idx else None
+    check(lib.runet_maxpool3s1_fwd(x.data_ptr(), ops.ld(x), y.data_ptr(), ops.ld(y), idx.data_ptr() if want_idx else None, n, h, w, c, ops.stream()))
+    return y, idx
+
+
+def maxpool3s1_backward(dy, idx, dx=None):
+    """dx given: accumulate into it (the block's other three data gradients are already there)."""
+    n, h, w, c = dy.shape
+    acc = dx is not None
+    if dx is None:
+        dx = ops.empty_nhwc(n, h, w, c, dy)
+    check(lib.runet_maxpool3s1_bwd(dy.data_ptr(), ops.ld(dy), idx.data_ptr(), dx.data_ptr(), ops.ld(dx), n, h, w, c, int(acc), ops.stream()))
+    return dx
+
+
+def _bn_coeff_into(x, bn: BNState, training, fused, scale, shift, mean, invstd):
+    """bn_coeff's two-launch routes for ONE BatchNorm whose input is a channel slice x, the coefficients written into the given slices of the
+    block's concatenated vectors"""
+    n, h, w, c = x.shape
+    st = ops.stream()
+    out = (scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), st)
+    if not training:
+        check(lib.runet_bn_finalize(None, None, n, c, h * w, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                    bn.running_var.data_ptr(), None, BN_MOMENTUM, BN_EPS, 0, *out))
+    elif FUSED_BN_STATS and fused and "part" in fused:
+        check(lib.runet_bn_stats_finalize(fused["part"].data_ptr(), fused["nparts"], c, bn.weight.data_ptr(), bn.bias.data_ptr(),
+                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.nbt.data_ptr(), BN_MOMENTUM, BN_EPS, *out))
+    else:
+        check(lib.runet_bn_stats(x.data_ptr(), ops.ld(x), n, h * w, c, _ws(n, h * w, c, x.device).data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(),
+                                 bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.nbt.data_ptr(), BN_MOMENTUM, BN_EPS, *out))
+
+
+def ms_block_forward(x, p: MSBlockParams, training, sm: Small, out=None, save=True):
+    """x [n, h, w, cx] NHWC (cx >= the weights' input channels: the RGB image zero-padded to 4) -> (relu(bn(cat)) written to `out`, ctx or None)"""
+    n, h, w, _ = x.shape
+    q = p.w[0].shape[3]
+    c = 4 * q
+    t = ops.empty_nhwc(n, h, w, c, x)
+    xp, idx = maxpool3s1_forward(x, want_idx=save)
+    vecs = [sm.f(c) for _ in range(4)]              # scale, shift, mean, invstd of the four BatchNorms back to back
+    for b in range(4):
+        sl = t[..., b * q:(b + 1) * q]
+        fs = {} if training else None
+        if b == 2:
+            ops.conv_general_fwd(x, p.w[b], p.b[b], 1, 2, out=sl)
+        else:
+            ops.conv_fwd(xp if b == 3 else x, p.w[b], p.b[b], out=sl, stats=fs)
+        _bn_coeff_into(sl, p.bn[b], training, fs, *(v[b * q:(b + 1) * q] for v in vecs))
+    scale, shift, mean, invstd = vecs
+    e = bn_apply(t, scale, shift, None, relu=True, out=out)
+    if not save:
+        return e, None
+    return e, dict(x=x, xp=xp, idx=idx, t=t, p=p, scale=scale, shift=shift, mean=mean, invstd=invstd, training=training, fused=False)
+
+
+def _ms_param_grads(x, xp, dt, p: MSBlockParams, G, pre):
+    """the four convolutions' weight and bias gradients from dt's channel slices -> G[pre + "branch{b}.{i}.weight" / ".bias"]"""
+    q = p.w[0].shape[3]
+    cin_w = p.w[0].shape[2]
+    for b in range(4):
+        sl = dt[..., b * q:(b + 1) * q]
+        name = f"{pre}branch{b + 1}.{1 if b == 3 else 0}"
+        if b == 2:
+            G[name + ".weight"] = ops.conv_general_wgrad(x, sl, 5, 5, 1, 2, cin_w=cin_w)
+        else:
+            k = 3 if b == 1 else 1
+            G[name + ".weight"] = ops.conv_wgrad(xp if b == 3 else x, sl, k, k, cin_w=cin_w)
+        G[name + ".bias"] = chan_sum(sl, torch.empty(q, device=dt.device, dtype=torch.float32))
+
+
+def _ms_bn_grads(sums, q, G, pre):
+    c = 4 * q
+    for b in range(4):
+        name = f"{pre}branch{b + 1}.{2 if b == 3 else 1}"
+        G[name + ".weight"], G[name + ".bias"] = sums[b * q:(b + 1) * q], sums[c + b * q:c + (b + 1) * q]
+
+
+def ms_block_backward(ctx, de, G, pre="", need_dx=True, keep=None):
+    """de: the gradient of ms_block_forward's output (an NHWC view).  Parameter gradients into G (physical layouts).  -> dx or None; the input
+    gradient is accumulated in a fixed order: 1x1, 3x3, 5x5, then the gather through the 3x3 pool of branch4's 1x1 data gradient.
+    keep: a dict that receives "dt", the gradient of the four convolutions' outputs."""
+    p: MSBlockParams = ctx["p"]
+    x, xp, t = ctx["x"], ctx["xp"], ctx["t"]
+    n, h, w, c = t.shape
+    q = c // 4
+    sums = torch.empty(2 * c, device=t.device, dtype=torch.float32)
+    dt = bn_backward(de, t, ctx["mean"], ctx["invstd"], ctx["scale"], sums, relu_shift=ctx["shift"], training=ctx["training"])
+    _ms_bn_grads(sums, q, G, pre)
+    if keep is not None:
+        keep["dt"] = dt
+    dx = None
+    if need_dx:
+        dx = ops.conv_dgrad(dt[..., :q], p.w[0])
+        ops.conv_dgrad(dt[..., q:2 * q], p.w[1], out=dx, accumulate=True)
+        ops.conv_general_dgrad(dt[..., 2 * q:3 * q], p.w[2], h, w, 1, 2, out=dx, accumulate=True)
+        d4 = ops.conv_dgrad(dt[..., 3 * q:], p.w[3])
+        maxpool3s1_backward(d4, ctx["idx"], dx=dx)
+    _ms_param_grads(x, xp, dt, p, G, pre)
+    return dx
+
+
+def _ms_src(x):
+    n, c, h, w = x.shape
+    if c != 3 or x.dtype != torch.float32:
+        raise ValueError("ms_stem: expected a float32 image [N, 3, H, W]")
+    return (x.data_ptr(),) + tuple(x.stride()) + (n, h, w)
+
+
+def _ms_wts(p: MSBlockParams):
+    if tuple(p.w[2].shape) != (5, 5, 3, MS_STEM_Q):
+        raise ValueError("ms_stem: the fused stem is MultiScaleBlock(3, 64)")
+    return tuple(t.data_ptr() for t in p.w) + tuple(t.data_ptr() for t in p.b)
+
+
+def ms_stem_forward(x_nchw, p: MSBlockParams, training, sm: Small, out=None, save=True, fused=None):
+    """MultiScaleBlock(3, 64) on the NCHW image -> (e [n, h, w, 64] written to `out`, ctx for ms_stem_backward or None)"""
+    n, _, h, w = x_nchw.shape
+    dev, st = x_nchw.device, ops.stream()
+    if not (FUSED_MS_STEM if fused is None else fused):
+        return ms_block_forward(to_nhwc_pad(x_nchw, 4), p, training, sm, out=out, save=save)
+    src, wts = _ms_src(x_nchw), _ms_wts(p)
+    c, q = MS_STEM_C, MS_STEM_Q
+    if out is None:
+        out = torch.empty((n, h, w, c), device=dev, dtype=torch.float32)
+    scale, shift, mean, invstd = sm.f(c), sm.f(c), sm.f(c), sm.f(c)
+    if training:
+        nparts = lib.runet_ms_stem_parts(n, h, w)
+        part = scratch(4 * nparts * q * 3, dev)
+        check(lib.runet_ms_stem_stats(*src, *wts, part.data_ptr(), part.numel(), st))
+    for b in range(4):
+        bn, sl = p.bn[b], slice(b * q, (b + 1) * q)
+        o = (scale[sl].data_ptr(), shift[sl].data_ptr(), mean[sl].data_ptr(), invstd[sl].data_ptr(), st)
+        if training:
+            check(lib.runet_bn_stats_finalize(part[b * nparts * q * 3:].data_ptr(), nparts, q, bn.weight.data_ptr(), bn.bias.data_ptr(),
+                                              bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.nbt.data_ptr(), BN_MOMENTUM, BN_EPS, *o))
+        else:
+            check(lib.runet_bn_finalize(None, None, n, q, h * w, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                        bn.running_var.data_ptr(), None, BN_MOMENTUM, BN_EPS, 0, *o))
+    check(lib.runet_ms_stem_fwd(*src, *wts, scale.data_ptr(), shift.data_ptr(), out.data_ptr(), ops.ld(out), st))
+    if not save:
+        return out, None
+    return out, dict(x=x_nchw, p=p, scale=scale, shift=shift, mean=mean, invstd=invstd, training=training, fused=True)
+
+
+def ms_stem_backward(ctx, de, G, pre="", want_dt=False):
+    """de [n, h, w, 64]: the gradient of the stem's output (an NHWC view).  Parameter gradients into G.  There is no input gradient (the input
+    is the image).  want_dt: also return dt, the gradient of the four convolutions' outputs."""
+    if not ctx["fused"]:
+        keep = {}
+        ms_block_backward(ctx, de, G, pre, need_dx=False, keep=keep)
+        return keep["dt"] if want_dt else None
+    p: MSBlockParams = ctx["p"]
+    x = ctx["x"]
+    n, _, h, w = x.shape
+    dev, st = de.device, ops.stream()
+    src, wts = _ms_src(x), _ms_wts(p)
+    c, q = MS_STEM_C, MS_STEM_Q
+    vec = (ctx["scale"].data_ptr(), ctx["shift"].data_ptr(), de.data_ptr(), ops.ld(de), ctx["mean"].data_ptr(), ctx["invstd"].data_ptr())
+    sums = torch.empty(2 * c, device=dev, dtype=torch.float32)
+    ws = scratch(lib.runet_ms_stem_workspace_floats(n, h, w), dev)
+    check(lib.runet_ms_stem_bwd_reduce(*src, *wts, *vec, ws.data_ptr(), ws.numel(), sums.data_ptr(), st))
+    use = sums if ctx["training"] else zeros(2 * c, dev)
+    dt = torch.empty((n, h, w, c), device=dev, dtype=torch.float32)
+    check(lib.runet_ms_stem_bwd_apply(*src, *wts, *vec, use.data_ptr(), 0, dt.data_ptr(), c, st))
+    _ms_bn_grads(sums, q, G, pre)
+    x4 = to_nhwc_pad(x, 4)
+    xp, _ = maxpool3s1_forward(x4, want_idx=False)
+    _ms_param_grads(x4, xp, dt, p, G, pre)
+    return dt if want_dt else None

@@ -641,6 +641,49 @@ int runet_sigmoid_nhwc_fwd(const float* u, int ldu, float* y, int ldy, long pixe
 int runet_sigmoid_nhwc_bwd(const float* dy, int lddy, const float* y, int ldy, float* du, int lddu, long pixels, int c, void* stream);
 int runet_copy_nhwc(const float* x, int ldx, float* y, int ldy, long pixels, int c, void* stream);
 
+/* ---- MSWNet baseline (Extended_Baseline_Comparison.py:479-548; csrc/multiscale.hip).  Its convolutions (1x1, 3x3, the 5x5 through
+ *      runet_conv2d_general), BatchNorm + ReLU, the 2x2 pools, the k2-s2 transposed convolutions and runet_outc_* are shared; these are the
+ *      MultiScaleBlock's 3x3 stride-1 max-pool and its first level, MultiScaleBlock(3, 64), fused over the image.  fp32.  No float atomics:
+ *      every sum has a fixed order and the block count depends on the shape only, results are bitwise reproducible.
+ * runet_maxpool3s1_fwd: MaxPool2d(3, stride 1, padding 1) (:490) over NHWC views (pixel strides ldx, ldy >= c; any channel count and 4-byte
+ *   alignment, 16-byte accesses where c, the strides and the pointers allow).  Padding counts as -inf.  idx (dense [n, h, w, c], may be NULL):
+ *   one byte per output element, k = dy * 3 + dx of the first maximum in row-major window order; a NaN wins over everything (ATen's CPU rule).
+ * runet_maxpool3s1_bwd: a gather - dx[p] = sum, in row-major order of the windows, of the dy of those of the <= 9 windows covering p whose
+ *   winner byte points at p; accumulate != 0: added onto what dx holds.
+ * The stem: x is the NCHW image [n, 3, h, w] read through its four strides (in floats, as runet_to_nhwc_pad).  Weights in their physical
+ *   (HWIO) layouts w1 [1][1][3][16], w3 [3][3][3][16], w5 [5][5][3][16], w4 [1][1][3][16] (branch4's 1x1 on the 3x3 max-pool of x), biases
+ *   b1, b3, b5, b4 [16].  t [64] = (w1 x + b1 | w3 * x + b3 | w5 * x + b5 | w4 maxpool3(x) + b4) per pixel (zero padding for the
+ *   convolutions), y = t * scale + shift, e = relu(y); scale, shift, mean, invstd [64]: the four BatchNorms' vectors in branch order.  t is
+ *   recomputed by the same FMAs in all four kernels and never written.  e, de, dt: NHWC views of 64 channels, pixel strides multiples of 4
+ *   floats, pointers 16-byte aligned.
+ * runet_ms_stem_parts: rows of the partials / workspace for a shape (-1: bad shape); runet_ms_stem_workspace_floats: floats
+ *   runet_ms_stem_bwd_reduce needs (-1: bad shape).
+ * runet_ms_stem_stats: part [4][runet_ms_stem_parts][16][3] = (count, mean, M2) of t per 8 x 32 pixel tile (two passes per block), one
+ *   array per branch in the layout runet_bn_stats_finalize consumes (c = 16).
+ * runet_ms_stem_fwd: e = relu(t * scale + shift).
+ * runet_ms_stem_bwd_reduce: g = de where y > 0; sums [128] = (dgamma [64] = sum g * xhat | dbeta [64] = sum g).
+ * runet_ms_stem_bwd_apply: dt = runet_bn_bwd_apply's formula on g (sums of the reduce, or zeros in eval mode where dt = scale * g; m_total
+ *   as there, 0: the local pixel count). */
+int runet_maxpool3s1_fwd(const float* x, int ldx, float* y, int ldy, unsigned char* idx, int n_img, int h, int w, int c, void* stream);
+int runet_maxpool3s1_bwd(const float* dy, int lddy, const unsigned char* idx, float* dx, int lddx, int n_img, int h, int w, int c,
+                         int accumulate, void* stream);
+int runet_ms_stem_parts(int n_img, int h, int w_);
+long runet_ms_stem_workspace_floats(int n_img, int h, int w_);
+int runet_ms_stem_stats(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* w1, const float* w3,
+                        const float* w5, const float* w4, const float* b1, const float* b3, const float* b5, const float* b4, float* part,
+                        long part_floats, void* stream);
+int runet_ms_stem_fwd(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* w1, const float* w3,
+                      const float* w5, const float* w4, const float* b1, const float* b3, const float* b5, const float* b4, const float* scale,
+                      const float* shift, float* e, int lde, void* stream);
+int runet_ms_stem_bwd_reduce(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* w1, const float* w3,
+                             const float* w5, const float* w4, const float* b1, const float* b3, const float* b5, const float* b4,
+                             const float* scale, const float* shift, const float* de, int ldde, const float* mean, const float* invstd,
+                             float* workspace, long workspace_floats, float* sums, void* stream);
+int runet_ms_stem_bwd_apply(const float* x, long sn, long sc, long sh, long sw, int n_img, int h, int w_, const float* w1, const float* w3,
+                            const float* w5, const float* w4, const float* b1, const float* b3, const float* b5, const float* b4,
+                            const float* scale, const float* shift, const float* de, int ldde, const float* mean, const float* invstd,
+                            const float* sums, long m_total, float* dt, int lddt, void* stream);
+
 /* ---- prediction: CoastlineExtractor (predict_coastline.py:336-618), everything between the uint8 upload and the two result masks
  *      (csrc/coastline.hip).  Masks are dense uint8 [h][w]; tile origins are device int32 [n_tiles][2] = (y0, x0), may be negative or overhang.
  * runet_scene_to_tiles: the to-tensor conversion and Normalize of the transform (:360-362, :387) of a uint8 HWC RGB scene (row_stride bytes per row) cut into T x T
