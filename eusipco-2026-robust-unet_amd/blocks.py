@@ -262,6 +262,48 @@ def chan_sum(x, out):
     return run()
 
 
+def vec(n, device):
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------- Conv2d -> BatchNorm2d -> ReLU (the baselines' step)
+def conv_bn_coeff(x, w, bias, bn: BNState, training, sm: Small, stride=1, stats=True, save=True):
+    """Conv2d (w HWIO, padding k // 2; stride 1 through ops.conv_fwd, stride 2 through ops.conv_general_fwd) and the coefficients of the
+    BatchNorm2d behind it.  stats: take the batch statistics from the convolution's epilogue where the kernel offers them (another
+    summation order than bn_coeff's own pass: a call site keeps its choice).
+    -> (t = conv x, scale, shift, the context conv_bn_relu_backward reads or None)"""
+    fs = None
+    if stride == 1:
+        fs = {} if (stats and training) else None
+        t = ops.conv_fwd(x, w, bias, stats=fs)
+    else:
+        t = ops.conv_general_fwd(x, w, bias, stride, w.shape[0] // 2)
+    s, h, mean, invstd, _ = bn_coeff(t, bn, training, sm, fused=fs)
+    return t, s, h, (dict(x=x, w=w, t=t, s=s, h=h, mean=mean, invstd=invstd, stride=stride) if save else None)
+
+
+def conv_bn_relu_forward(x, w, bias, bn: BNState, training, sm: Small, stride=1, stats=True, save=True, out=None):
+    """-> (relu(bn(conv x)), written to `out` - a concat slice - when given; context or None)"""
+    t, s, h, cx = conv_bn_coeff(x, w, bias, bn, training, sm, stride, stats, save)
+    return bn_apply(t, s, h, None, relu=True, out=out), cx
+
+
+def conv_bn_relu_backward(cx, dy, G, seq, i, training, out=None):
+    """dy: gradient of the activation.  The parameter gradients go into G (physical layouts) as {seq}.{i}.weight / .bias (the convolution;
+    on the weight-gradient stream) and {seq}.{i + 1}.weight / .bias (the BatchNorm).  out: where the BatchNorm backward writes (out=dy: in
+    place).  -> dt, the gradient of the convolution's output; the data gradient is the caller's"""
+    k, _, cin_w, c = cx["w"].shape
+    sums = vec(2 * c, dy.device)
+    dt = bn_backward(dy, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, relu_shift=cx["h"], out=out, training=training)
+    G[f"{seq}.{i + 1}.weight"], G[f"{seq}.{i + 1}.bias"] = sums[:c], sums[c:]
+    if cx["stride"] == 1:
+        G[f"{seq}.{i}.weight"] = ops.conv_wgrad(cx["x"], dt, k, k, cin_w=cin_w)
+    else:
+        G[f"{seq}.{i}.weight"] = ops.conv_general_wgrad(cx["x"], dt, k, k, cx["stride"], k // 2, cin_w=cin_w)
+    G[f"{seq}.{i}.bias"] = chan_sum(dt, vec(c, dy.device))
+    return dt
+
+
 # =============================================================================== ResidualBlock
 class RBParams:
     __slots__ = ("w1", "bn1", "w2", "bn2", "w0p", "w2p", "wsa", "ws", "bns", "cin_w")

@@ -7,7 +7,7 @@ BatchNorm2d -> ReLU, 64 channels at H/2), three branches of the same two-convolu
 (Conv2d 1x1 -> 48, BatchNorm2d, Upsample x2 / x4, no activation), torch.cat([hr, mr_up, lr_up]) and `head` (Conv2d 3x3 144 -> 64, BatchNorm2d,
 ReLU, Upsample x2, Conv2d 1x1 64 -> 1, Sigmoid).  forward(x [N, 3, H, W]) -> sigmoid probabilities [N, 1, H, W].
 
-One autograd node with an explicit backward, NHWC inside, as segnet.py / yolo.py / segformer.py:
+One autograd node with an explicit backward, NHWC inside (baseline.py):
   convolutions   3x3 stride 1 and 1x1 through ops.conv_fwd / conv_dgrad / conv_wgrad (BatchNorm statistics from the convolution's epilogue where
                  the kernel offers them), the three stride-2 ones through runet_conv2d_general / runet_conv_wgrad_general (the stem's reads
                  the RGB input padded to 4 channels, cin_w = 3); BatchNorm + ReLU as the U-Net's (runet_bn_apply, ReLU mask recomputed from
@@ -33,12 +33,12 @@ statistics only.
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import blocks as B
 from . import ops
-from .model import BatchNorm2d, Conv2d, _Act, _Holder, _require_cuda
+from .baseline import FusedNet, ReLU, Sigmoid, check_image, conv_bn_relu
+from .model import BatchNorm2d, Conv2d, _Holder
 
 # the four Sequentials of the form Conv2d 3x3 -> BatchNorm2d -> ReLU, twice: (attribute, ((cin, cout, stride), (cin, cout, stride)))
 BRANCHES = (("stem", ((3, 64, 2), (64, 64, 1))), ("hr_branch", ((64, 48, 1), (48, 48, 1))), ("mr_branch", ((64, 96, 2), (96, 96, 1))),
@@ -46,16 +46,6 @@ BRANCHES = (("stem", ((3, 64, 2), (64, 64, 1))), ("hr_branch", ((64, 48, 1), (48
 # the fusions Conv2d 1x1 -> BatchNorm2d -> Upsample: (attribute, cin, scale factor), in the concat's channel order behind hr's [0, 48)
 FUSIONS = (("mr_to_hr", 96, 2), ("lr_to_hr", 192, 4))
 HR, CAT, HEAD = 48, 144, 64
-
-
-class _ReLU(_Act):
-    def __init__(self, inplace=True):
-        super().__init__()
-        self.inplace = inplace
-
-
-class _Sigmoid(_Act):
-    pass
 
 
 class _Upsample(_Holder):
@@ -66,7 +56,9 @@ class _Upsample(_Holder):
         self.scale_factor, self.mode, self.align_corners = scale_factor, "bilinear", False
 
 
-class HRNetWater(nn.Module):
+class HRNetWater(FusedNet):
+    FP32_ONLY = "the head and fusion kernels are fp32"
+
     def __init__(self, n_classes=1):
         super().__init__()
         if n_classes != 1:
@@ -75,53 +67,17 @@ class HRNetWater(nn.Module):
         for name, convs in BRANCHES:
             mods = []
             for cin, cout, stride in convs:
-                mods += [Conv2d(cin, cout, 3, padding=1, stride=stride), BatchNorm2d(cout), _ReLU()]
+                mods += [Conv2d(cin, cout, 3, padding=1, stride=stride), BatchNorm2d(cout), ReLU()]
             setattr(self, name, nn.Sequential(*mods))
         for name, cin, s in FUSIONS:
             setattr(self, name, nn.Sequential(Conv2d(cin, HR, 1), BatchNorm2d(HR), _Upsample(s)))
-        self.head = nn.Sequential(Conv2d(CAT, HEAD, 3, padding=1), BatchNorm2d(HEAD), _ReLU(), _Upsample(2), Conv2d(HEAD, n_classes, 1), _Sigmoid())
-        self.precision = "f32"
+        self.head = nn.Sequential(Conv2d(CAT, HEAD, 3, padding=1), BatchNorm2d(HEAD), ReLU(), _Upsample(2), Conv2d(HEAD, n_classes, 1), Sigmoid())
 
-    def __setattr__(self, name, value):
-        # as SegNet / YOLOSeg: a cross-rank BatchNorm hook (ddp.GradAllReducer(sync_bn=True)) would silently train a different function
-        if name == "sync_bn_hook" and value is not None:
-            raise NotImplementedError("HRNetWater has no SyncBatchNorm path (per-rank BatchNorm statistics only): construct GradAllReducer(sync_bn=False)")
-        super().__setattr__(name, value)
+    def _check_input(self, x):
+        check_image(x, 8, "three stride-2 convolutions whose outputs are upsampled x2 / x4 into one concat")
 
-    def set_precision(self, mode):
-        if mode != "f32":
-            raise ValueError("HRNetWater runs in fp32 only (the head and fusion kernels are fp32)")
-        self.precision = mode
-        return self
-
-    def forward(self, x):
-        _require_cuda(x)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected x [N, 3, H, W]")
-        if x.shape[2] % 8 or x.shape[3] % 8:
-            raise ValueError("H and W must be multiples of 8 (three stride-2 convolutions whose outputs are upsampled x2 / x4 into one concat)")
-        params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _HRNetFn.apply(x, self, *params)
-        with ops.precision("f32"):
-            return hrnet_forward(self, x, save=False)[0]
-
-
-def _conv_bn_relu(seq, i, x, key, tr, sm, C, out=None):
-    """seq[i] (Conv2d 3x3, stride 1 or 2) -> seq[i + 1] (BatchNorm2d) -> ReLU; the activation goes to `out` (a concat slice) when given"""
-    conv, bn = seq[i], seq[i + 1]
-    w = ops.hwio(conv.weight)
-    stride = conv.stride[0]
-    fs = None
-    if stride == 1:
-        fs = {} if tr else None
-        t = ops.conv_fwd(x, w, conv.bias, stats=fs)
-    else:
-        t = ops.conv_general_fwd(x, w, conv.bias, stride, 1)
-    s, h, mean, invstd, _ = B.bn_coeff(t, bn.state(), tr, sm, fused=fs)
-    if C is not None:
-        C[key] = dict(x=x, w=w, t=t, s=s, h=h, mean=mean, invstd=invstd, stride=stride)
-    return B.bn_apply(t, s, h, None, relu=True, out=out)
+    def _passes(self):
+        return hrnet_forward, hrnet_backward
 
 
 def hrnet_forward(net: HRNetWater, x, save=True):
@@ -138,10 +94,10 @@ def hrnet_forward(net: HRNetWater, x, save=True):
     for name, _ in BRANCHES:
         seq = getattr(net, name)
         src = cur if name == "stem" else feats["mr_branch" if name == "lr_branch" else "stem"]
-        a = _conv_bn_relu(seq, 0, src, f"{name}.0", tr, sm, C)
+        a = conv_bn_relu(seq, 0, src, tr, sm, C, f"{name}.0")
         if name == "hr_branch":
             cat = ops.empty_nhwc(n, a.shape[1], a.shape[2], CAT, a)
-        feats[name] = _conv_bn_relu(seq, 3, a, f"{name}.3", tr, sm, C, out=cat[..., :HR] if name == "hr_branch" else None)
+        feats[name] = conv_bn_relu(seq, 3, a, tr, sm, C, f"{name}.3", out=cat[..., :HR] if name == "hr_branch" else None)
     for j, (name, _, s) in enumerate(FUSIONS):
         seq = getattr(net, name)
         f = feats["mr_branch" if name == "mr_to_hr" else "lr_branch"]
@@ -166,33 +122,20 @@ def hrnet_forward(net: HRNetWater, x, save=True):
 
 
 def hrnet_backward(net: HRNetWater, C, dprob):
-    """-> {parameter name: gradient with the parameter's logical shape}"""
+    """-> {parameter name: gradient in the parameter's PHYSICAL layout (conv weights HWIO)}"""
     G = {}
     dev = dprob.device
     tr = C["training"]
 
-    def vec(k):
-        return torch.empty(k, device=dev, dtype=torch.float32)
-
     def conv_grads(name, cx, dt):
-        """weight and bias gradient of the convolution that produced cx["t"] (dt: the gradient of that output)"""
+        """weight and bias gradient of the stride-1 convolution that produced cx["t"] (dt: the gradient of that output)"""
         k = cx["w"].shape[0]
-        if cx.get("stride", 1) == 1:
-            dw = ops.conv_wgrad(cx["x"], dt, k, k)
-        else:
-            dw = ops.conv_general_wgrad(cx["x"], dt, k, k, cx["stride"], 1, cin_w=cx["w"].shape[2])
-        G[name + ".weight"] = dw.permute(3, 2, 0, 1)
-        G[name + ".bias"] = B.chan_sum(dt, vec(dt.shape[3]))
+        G[name + ".weight"] = ops.conv_wgrad(cx["x"], dt, k, k)
+        G[name + ".bias"] = B.chan_sum(dt, B.vec(dt.shape[3], dev))
 
     def bn_relu_back(seq, i, dy):
-        """gradient of a Conv2d -> BatchNorm2d -> ReLU activation -> gradient of the convolution's output; parameter gradients into G"""
         cx = C[f"{seq}.{i}"]
-        c = cx["t"].shape[3]
-        sums = vec(2 * c)
-        dt = B.bn_backward(dy, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, relu_shift=cx["h"], training=tr)
-        G[f"{seq}.{i + 1}.weight"], G[f"{seq}.{i + 1}.bias"] = sums[:c], sums[c:]
-        conv_grads(f"{seq}.{i}", cx, dt)
-        return cx, dt
+        return cx, B.conv_bn_relu_backward(cx, dy, G, seq, i, tr)
 
     def pair_back(seq, dy, dsrc=None):
         """backward of a two-convolution Sequential; its input's gradient goes into dsrc (+=) when given.  -> that gradient"""
@@ -211,7 +154,7 @@ def hrnet_backward(net: HRNetWater, C, dprob):
     c = hc["t"].shape[3]
     dt, out = B.hr_head_backward(dprob, hc["prob"], hc["t"], hc["s"], hc["h"], hc["wo"], hc["mean"], hc["invstd"], saved=hc["saved"], training=tr)
     G["head.1.weight"], G["head.1.bias"] = out[:c], out[c:2 * c]
-    G["head.4.weight"], G["head.4.bias"] = out[2 * c:3 * c].view(1, c, 1, 1), out[3 * c:]
+    G["head.4.weight"], G["head.4.bias"] = out[2 * c:3 * c].view(1, 1, c, 1), out[3 * c:]
     conv_grads("head.0", hc, dt)
     dcat = ops.conv_dgrad(dt, hc["w"])
     del dt
@@ -219,7 +162,7 @@ def hrnet_backward(net: HRNetWater, C, dprob):
     dfeat = {}
     for j, (name, _, s) in enumerate(FUSIONS):
         fx = C[name]
-        sums = vec(2 * HR)
+        sums = B.vec(2 * HR, dev)
         dt = B.bn_bilinear_backward(dcat[..., HR * (j + 1):HR * (j + 2)], fx["t"], fx["mean"], fx["invstd"], fx["s"], sums, s, training=tr)
         G[f"{name}.1.weight"], G[f"{name}.1.bias"] = sums[:HR], sums[HR:]
         conv_grads(f"{name}.0", fx, dt)
@@ -231,24 +174,3 @@ def hrnet_backward(net: HRNetWater, C, dprob):
     pair_back("hr_branch", dcat[..., :HR], dsrc=dstem)
     pair_back("stem", dstem)
     return G
-
-
-class _HRNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        with ops.precision("f32"):
-            prob, C = hrnet_forward(net, x, save=True)
-        ctx.C, ctx.net = C, net
-        return prob
-
-    @staticmethod
-    def backward(ctx, dprob):
-        if ctx.C is None:
-            raise RuntimeError("HRNetWater backward called twice (activations were released after the first pass)")
-        net = ctx.net
-        with ops.precision("f32"), ops.wgrad_side_stream():
-            G = hrnet_backward(net, ctx.C, dprob.contiguous())
-        ctx.C = None
-        named = list(net.named_parameters())
-        ops.deliver_grads(net, [p for _, p in named], [G[k] for k, _ in named])      # fixed addresses, assigned here (not returned to autograd)
-        return (None, None) + (None,) * len(named)

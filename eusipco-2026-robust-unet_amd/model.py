@@ -151,7 +151,7 @@ class _CAFn(torch.autograd.Function):
         sink = B.DictSink(dy.device)
         dx = B.ca_backward(ctx.c, _nhwc(dy), sink)
         ctx.c = None
-        return _nchw(dx), _logical("fc.0.weight", sink.g["fc.0.weight"]), _logical("fc.2.weight", sink.g["fc.2.weight"])
+        return _nchw(dx), _logical(sink.g["fc.0.weight"]), _logical(sink.g["fc.2.weight"])
 
 
 class SpatialAttention(nn.Module):
@@ -178,7 +178,7 @@ class _SAFn(torch.autograd.Function):
         sink = B.DictSink(dy.device)
         dx = B.sa_backward(ctx.c, _nhwc(dy), sink)
         ctx.c = None
-        return _nchw(dx), _logical("conv1.weight", sink.g["conv1.weight"])
+        return _nchw(dx), _logical(sink.g["conv1.weight"])
 
 
 class AttentionGate(nn.Module):
@@ -224,13 +224,14 @@ class _GateFn(torch.autograd.Function):
         ctx.gc = None
         names = ["W_g.0.weight", "W_g.0.bias", "W_g.1.weight", "W_g.1.bias", "W_x.0.weight", "W_x.0.bias", "W_x.1.weight",
                  "W_x.1.bias", "psi.0.weight", "psi.0.bias", "psi.1.weight", "psi.1.bias"]
-        return (_nchw(dup), _nchw(dskip), None) + tuple(_logical(k, sink.g[k]) for k in names)
+        return (_nchw(dup), _nchw(dskip), None) + tuple(_logical(sink.g[k]) for k in names)
 
 
-def _logical(name, t):
-    """physical gradient -> tensor shaped/strided like the parameter it belongs to."""
+def _logical(t, transposed=False):
+    """physical gradient -> tensor shaped/strided like the parameter it belongs to: HWIO -> OIHW for a convolution weight, [kh, kw, cin, cout]
+    -> [cin, cout, kh, kw] for the weight of a transposed convolution (`transposed`: the owning module's type decides, never its name)."""
     if t.dim() == 4:
-        return t.permute(2, 3, 0, 1) if name.startswith("up") and name.endswith("weight") else t.permute(3, 2, 0, 1)
+        return t.permute(2, 3, 0, 1) if transposed else t.permute(3, 2, 0, 1)
     return t
 
 
@@ -303,7 +304,7 @@ class _RBFn(torch.autograd.Function):
         ctx.c = None
         if dx is not None:
             dx = _nchw(dx[..., :ctx.cin]) if dx.shape[3] != ctx.cin else _nchw(dx)
-        return (dx, None) + tuple(_logical(k, sink.g[k]) for k in ctx.names)
+        return (dx, None) + tuple(_logical(sink.g[k]) for k in ctx.names)
 
 
 # ----------------------------------------------------------------------------- DilatedBlock
@@ -346,7 +347,7 @@ class _DilFn(torch.autograd.Function):
         sink = B.DictSink(dout.device)
         dx = B.dilated_backward(ctx.c, _nhwc(dout), sink, need_dx=ctx.need_dx)
         ctx.c = None
-        return (_nchw(dx) if dx is not None else None, None) + tuple(_logical(k, sink.g[k]) for k in ctx.names)
+        return (_nchw(dx) if dx is not None else None, None) + tuple(_logical(sink.g[k]) for k in ctx.names)
 
 
 class MaxPool2d(nn.Module):
@@ -644,7 +645,7 @@ class _NetFn(torch.autograd.Function):
             for k, p in named:
                 if not p.requires_grad:
                     continue
-                g = _logical(k, sink.g[k])
+                g = _logical(sink.g[k], isinstance(net.get_submodule(k.rpartition(".")[0]), ConvTranspose2d))
                 if p.grad is None:
                     p.grad = g
                 else:

@@ -7,7 +7,7 @@ of the block's channels - concatenated; MaxPool2d(2) between the levels; `bridge
 `up4..1` (ConvTranspose2d k2 s2) with cat([up, skip]) into `dec4..1` (one Conv2d 3x3 -> BatchNorm2d -> ReLU each); `outc` (Conv2d 1x1 64 -> 1,
 Sigmoid).  forward(x [N, 3, H, W]) -> sigmoid probabilities [N, 1, H, W].
 
-One autograd node with an explicit backward, NHWC inside, as waternet.py:
+One autograd node with an explicit backward, NHWC inside (baseline.py):
   enc1          blocks.ms_stem_forward (csrc/multiscale.hip): the image -> the 64-channel activation in one pass, the pre-BatchNorm tensor
                 recomputed per pixel and never written; backward runet_ms_stem_bwd_reduce / _bwd_apply, the four weight gradients from the
                 apply kernel's output on a 4-channel NHWC copy of the image (no input gradient: the input is the image)
@@ -33,28 +33,11 @@ import torch.nn as nn
 
 from . import blocks as B
 from . import ops
-from .model import BatchNorm2d, Conv2d, ConvTranspose2d, _Act, _Holder, _require_cuda
+from .baseline import FusedNet, MaxPool2d, ReLU, Sigmoid, check_image, conv_bn_relu
+from .model import BatchNorm2d, Conv2d, ConvTranspose2d, _require_cuda
 
 CH = (64, 128, 256, 512)
 BRIDGE = 1024
-
-
-class _ReLU(_Act):
-    def __init__(self, inplace=True):
-        super().__init__()
-        self.inplace = inplace
-
-
-class _Sigmoid(_Act):
-    pass
-
-
-class _MaxPool2d(_Holder):
-    """nn.MaxPool2d stand-in (no parameters; the enclosing forward runs the pool kernel)."""
-
-    def __init__(self, kernel_size=2, stride=None, padding=0):
-        super().__init__()
-        self.kernel_size, self.stride, self.padding = kernel_size, kernel_size if stride is None else stride, padding
 
 
 class MultiScaleBlock(nn.Module):
@@ -67,10 +50,10 @@ class MultiScaleBlock(nn.Module):
             raise ValueError("out_channels must be a positive multiple of 4 (four branches of out_channels // 4)")
         q = out_channels // 4
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.branch1 = nn.Sequential(Conv2d(in_channels, q, 1), BatchNorm2d(q), _ReLU())
-        self.branch2 = nn.Sequential(Conv2d(in_channels, q, 3, padding=1), BatchNorm2d(q), _ReLU())
-        self.branch3 = nn.Sequential(Conv2d(in_channels, q, 5, padding=2), BatchNorm2d(q), _ReLU())
-        self.branch4 = nn.Sequential(_MaxPool2d(3, stride=1, padding=1), Conv2d(in_channels, q, 1), BatchNorm2d(q), _ReLU())
+        self.branch1 = nn.Sequential(Conv2d(in_channels, q, 1), BatchNorm2d(q), ReLU())
+        self.branch2 = nn.Sequential(Conv2d(in_channels, q, 3, padding=1), BatchNorm2d(q), ReLU())
+        self.branch3 = nn.Sequential(Conv2d(in_channels, q, 5, padding=2), BatchNorm2d(q), ReLU())
+        self.branch4 = nn.Sequential(MaxPool2d(3, stride=1, padding=1), Conv2d(in_channels, q, 1), BatchNorm2d(q), ReLU())
 
     def handles(self):
         convs = (self.branch1[0], self.branch2[0], self.branch3[0], self.branch4[1])
@@ -94,10 +77,12 @@ class MultiScaleBlock(nn.Module):
 
 
 def _cbr(cin, cout):
-    return [Conv2d(cin, cout, 3, padding=1), BatchNorm2d(cout), _ReLU()]
+    return [Conv2d(cin, cout, 3, padding=1), BatchNorm2d(cout), ReLU()]
 
 
-class MSWNet(nn.Module):
+class MSWNet(FusedNet):
+    FP32_ONLY = "the multi-scale stem and pool kernels are fp32"
+
     def __init__(self, n_classes=1):
         super().__init__()
         if n_classes != 1:
@@ -107,52 +92,19 @@ class MSWNet(nn.Module):
         self.enc2 = MultiScaleBlock(64, 128)
         self.enc3 = MultiScaleBlock(128, 256)
         self.enc4 = MultiScaleBlock(256, 512)
-        self.pool = _MaxPool2d(2)
+        self.pool = MaxPool2d(2)
         self.bridge = nn.Sequential(*_cbr(512, BRIDGE), *_cbr(BRIDGE, BRIDGE))
         self.up4, self.dec4 = ConvTranspose2d(1024, 512, 2, stride=2), nn.Sequential(*_cbr(1024, 512))
         self.up3, self.dec3 = ConvTranspose2d(512, 256, 2, stride=2), nn.Sequential(*_cbr(512, 256))
         self.up2, self.dec2 = ConvTranspose2d(256, 128, 2, stride=2), nn.Sequential(*_cbr(256, 128))
         self.up1, self.dec1 = ConvTranspose2d(128, 64, 2, stride=2), nn.Sequential(*_cbr(128, 64))
-        self.outc = nn.Sequential(Conv2d(64, n_classes, 1), _Sigmoid())
-        self.precision = "f32"
+        self.outc = nn.Sequential(Conv2d(64, n_classes, 1), Sigmoid())
 
-    def __setattr__(self, name, value):
-        # as WaterNet: a cross-rank BatchNorm hook (ddp.GradAllReducer(sync_bn=True)) would silently train a different function
-        if name == "sync_bn_hook" and value is not None:
-            raise NotImplementedError("MSWNet has no SyncBatchNorm path (per-rank BatchNorm statistics only): construct GradAllReducer(sync_bn=False)")
-        super().__setattr__(name, value)
+    def _check_input(self, x):
+        check_image(x, 16, "four 2x2 poolings whose skips are concatenated with the upsampled path", fp32=True)
 
-    def set_precision(self, mode):
-        if mode != "f32":
-            raise ValueError("MSWNet runs in fp32 only (the multi-scale stem and pool kernels are fp32)")
-        self.precision = mode
-        return self
-
-    def forward(self, x):
-        _require_cuda(x)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected x [N, 3, H, W]")
-        if x.shape[2] % 16 or x.shape[3] % 16:
-            raise ValueError("H and W must be multiples of 16 (four 2x2 poolings whose skips are concatenated with the upsampled path)")
-        if x.dtype != torch.float32:
-            raise TypeError("MSWNet computes in fp32")
-        params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _MSWNetFn.apply(x, self, *params)
-        with ops.precision("f32"):
-            return mswnet_forward(self, x, save=False)[0]
-
-
-def _cbr_forward(seq, i, x, key, tr, sm, C):
-    """Conv2d 3x3 -> BatchNorm2d -> ReLU at seq[i : i + 3]"""
-    conv, bn = seq[i], seq[i + 1]
-    w = ops.hwio(conv.weight)
-    fs = {} if tr else None
-    t = ops.conv_fwd(x, w, conv.bias, stats=fs)
-    s, h, mean, invstd, _ = B.bn_coeff(t, bn.state(), tr, sm, fused=fs)
-    if C is not None:
-        C[f"{key}.{i}"] = dict(x=x, w=w, t=t, s=s, h=h, mean=mean, invstd=invstd)
-    return B.bn_apply(t, s, h, None, relu=True)
+    def _passes(self):
+        return mswnet_forward, mswnet_backward
 
 
 def mswnet_forward(net: MSWNet, x, save=True):
@@ -175,15 +127,15 @@ def mswnet_forward(net: MSWNet, x, save=True):
         else:
             _, encs[lvl] = B.ms_block_forward(cur, p, tr, sm, out=skip, save=save)
         cur, pools[lvl] = B.maxpool_forward(skip)
-    y = _cbr_forward(net.bridge, 0, cur, "bridge", tr, sm, C)
-    y = _cbr_forward(net.bridge, 3, y, "bridge", tr, sm, C)
+    y = conv_bn_relu(net.bridge, 0, cur, tr, sm, C, "bridge.0")
+    y = conv_bn_relu(net.bridge, 3, y, tr, sm, C, "bridge.3")
     ups = {}
     for lvl in (4, 3, 2, 1):
         up = getattr(net, f"up{lvl}")
         wup = ops.hwio_t(up.weight)
         ops.convt_fwd(y, wup, up.bias, out=cats[lvl][..., :CH[lvl - 1]])
         ups[lvl] = (y, wup)
-        y = _cbr_forward(getattr(net, f"dec{lvl}"), 0, cats[lvl], f"dec{lvl}", tr, sm, C)
+        y = conv_bn_relu(getattr(net, f"dec{lvl}"), 0, cats[lvl], tr, sm, C, f"dec{lvl}.0")
     wo = ops.hwio(net.outc[0].weight)
     prob, _ = B.outc_forward(y, wo, net.outc[0].bias)
     if save:
@@ -198,38 +150,27 @@ def mswnet_backward(net: MSWNet, C, dprob):
     sink = B.DictSink(dev)
     G = sink.g
 
-    def vec(k):
-        return torch.empty(k, device=dev, dtype=torch.float32)
-
-    def cbr_back(key, dy):
-        """gradient of a Conv2d -> BatchNorm2d -> ReLU activation -> (ctx, gradient of the convolution's output); parameter gradients into G"""
-        cx = C[key]
-        seq, i = key.rsplit(".", 1)
-        c = cx["t"].shape[3]
-        sums = vec(2 * c)
-        dt = B.bn_backward(dy, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, relu_shift=cx["h"], out=dy, training=tr)
-        G[f"{seq}.{int(i) + 1}.weight"], G[f"{seq}.{int(i) + 1}.bias"] = sums[:c], sums[c:]
-        G[f"{key}.weight"] = ops.conv_wgrad(cx["x"], dt, 3, 3)
-        G[f"{key}.bias"] = B.chan_sum(dt, vec(c))
-        return cx, dt
+    def cbr_back(seq, i, dy):
+        cx = C[f"{seq}.{i}"]
+        return cx, B.conv_bn_relu_backward(cx, dy, G, seq, i, tr, out=dy)
 
     y, wo, prob = C["head"]
     dy = B.outc_backward(dprob, prob, y, wo, sink, pre="outc.0.")
     dskip = {}
     for lvl in (1, 2, 3, 4):
         ch = CH[lvl - 1]
-        cx, dt = cbr_back(f"dec{lvl}.0", dy)
+        cx, dt = cbr_back(f"dec{lvl}", 0, dy)
         dcat = ops.conv_dgrad(dt, cx["w"])
         del dt
         dup, dskip[lvl] = dcat[..., :ch], dcat[..., ch:]
         yin, wup = C["ups"][lvl]
         G[f"up{lvl}.weight"] = ops.convt_wgrad(yin, dup)
-        G[f"up{lvl}.bias"] = B.chan_sum(dup, vec(ch))
+        G[f"up{lvl}.bias"] = B.chan_sum(dup, B.vec(ch, dev))
         dy = ops.convt_dgrad(dup, wup)
-    cx, dt = cbr_back("bridge.3", dy)
+    cx, dt = cbr_back("bridge", 3, dy)
     da = ops.conv_dgrad(dt, cx["w"])
     del dt
-    cx, dt = cbr_back("bridge.0", da)
+    cx, dt = cbr_back("bridge", 0, da)
     dcur = ops.conv_dgrad(dt, cx["w"])
     del dt
     for lvl in (4, 3, 2, 1):
@@ -239,30 +180,3 @@ def mswnet_backward(net: MSWNet, C, dprob):
         else:
             B.ms_stem_backward(C["encs"][lvl], dskip[lvl], G, pre="enc1.")
     return G
-
-
-class _MSWNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        with ops.precision("f32"):
-            prob, C = mswnet_forward(net, x, save=True)
-        ctx.C, ctx.net = C, net
-        return prob
-
-    @staticmethod
-    def backward(ctx, dprob):
-        if ctx.C is None:
-            raise RuntimeError("MSWNet backward called twice (activations were released after the first pass)")
-        net = ctx.net
-        with ops.precision("f32"), ops.wgrad_side_stream():
-            G = mswnet_backward(net, ctx.C, dprob.contiguous())
-        ctx.C = None
-        named = list(net.named_parameters())
-        out = []
-        for name, _ in named:
-            g = G[name]
-            if g.dim() == 4:                                   # physical -> logical: [2, 2, cin, cout] -> [cin, cout, 2, 2], HWIO -> OIHW
-                g = g.permute(2, 3, 0, 1) if name.startswith("up") else g.permute(3, 2, 0, 1)
-            out.append(g)
-        ops.deliver_grads(net, [p for _, p in named], out)      # fixed addresses, assigned here (not returned to autograd)
-        return (None, None) + (None,) * len(named)

@@ -7,7 +7,7 @@ channels; MixFFN 1x1 -> depthwise 3x3 -> GELU -> 1x1), and the MLP decoder (1x1 
 size, concatenated [_c4, _c3, _c2, _c1], 1x1 fuse + BatchNorm + ReLU, 3x3 + BatchNorm + ReLU, 1x1 + sigmoid), whose probability map is
 resized bilinearly to the input size.  forward(x [N, 3, H, W]) -> probabilities [N, 1, H, W].
 
-One autograd node with an explicit backward, NHWC inside, as segnet.py / yolo.py:
+One autograd node with an explicit backward, NHWC inside (baseline.py):
   patch embeddings   runet_conv2d_general (7x7 s4 with cin 3 padded to 4; 3x3 s2), runet_bn_apply_gelu / runet_bn_bwd_*_gelu
   attention          q / kv / proj 1x1 convolutions, the r x r stride-r reduction through runet_conv2d_general, runet_kv_attention_fwd / _bwd
                      (scores never reach HBM); proj writes on top of a copy of the stage tensor (accumulate), so the stage input survives
@@ -32,7 +32,8 @@ import torch.nn as nn
 from . import blocks as B
 from . import ops
 from ._lib import check, lib
-from .model import BatchNorm2d, Conv2d, _Act, _Holder, _require_cuda
+from .baseline import FusedNet, ReLU, Sigmoid, check_image, conv_bn_relu
+from .model import BatchNorm2d, Conv2d, _Act, _Holder
 
 HEAD_DIM = 32
 # MixFFN depthwise + GELU: z = dwconv(x) + b is kept from the forward for the backward (measured faster at every stage shape: the forward's
@@ -46,16 +47,6 @@ EMBED = ((3, 32, 7, 4, 3), (32, 64, 3, 2, 1), (64, 128, 3, 2, 1), (128, 256, 3, 
 
 class _GELU(_Act):
     """nn.GELU() stand-in (no parameters; fused into the BatchNorm / depthwise kernels)."""
-
-
-class _ReLU(_Act):
-    def __init__(self, inplace=True):
-        super().__init__()
-        self.inplace = inplace
-
-
-class _Sigmoid(_Act):
-    pass
 
 
 class DepthwiseConv2d(_Holder):
@@ -101,7 +92,9 @@ class EfficientSelfAttention(nn.Module):
         raise NotImplementedError("EfficientSelfAttention is fused into SegFormerLite's single autograd node")
 
 
-class SegFormerLite(nn.Module):
+class SegFormerLite(FusedNet):
+    FP32_ONLY = "the attention and depthwise kernels are fp32"
+
     def __init__(self, n_classes=1):
         super().__init__()
         if n_classes != 1:
@@ -116,33 +109,14 @@ class SegFormerLite(nn.Module):
         self.linear_c3 = Conv2d(128, 256, 1)
         self.linear_c2 = Conv2d(64, 256, 1)
         self.linear_c1 = Conv2d(32, 256, 1)
-        self.linear_fuse = nn.Sequential(Conv2d(256 * 4, 256, 1), BatchNorm2d(256), _ReLU())
-        self.head = nn.Sequential(Conv2d(256, 64, 3, padding=1), BatchNorm2d(64), _ReLU(), Conv2d(64, n_classes, 1), _Sigmoid())
-        self.precision = "f32"
+        self.linear_fuse = nn.Sequential(Conv2d(256 * 4, 256, 1), BatchNorm2d(256), ReLU())
+        self.head = nn.Sequential(Conv2d(256, 64, 3, padding=1), BatchNorm2d(64), ReLU(), Conv2d(64, n_classes, 1), Sigmoid())
 
-    def __setattr__(self, name, value):
-        # as SegNet / YOLOSeg: a cross-rank BatchNorm hook (ddp.GradAllReducer(sync_bn=True)) would silently train a different function
-        if name == "sync_bn_hook" and value is not None:
-            raise NotImplementedError("SegFormerLite has no SyncBatchNorm path (per-rank BatchNorm statistics only): construct GradAllReducer(sync_bn=False)")
-        super().__setattr__(name, value)
+    def _check_input(self, x):
+        check_image(x, 32, "the stride-4 embedding, three stride-2 embeddings and the stage-1 reduction by 8")
 
-    def set_precision(self, mode):
-        if mode != "f32":
-            raise ValueError("SegFormerLite runs in fp32 only (the attention and depthwise kernels are fp32)")
-        self.precision = mode
-        return self
-
-    def forward(self, x):
-        _require_cuda(x)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected x [N, 3, H, W]")
-        if x.shape[2] % 32 or x.shape[3] % 32:
-            raise ValueError("H and W must be multiples of 32 (the stride-4 embedding, three stride-2 embeddings and the stage-1 reduction by 8)")
-        params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _SegFormerFn.apply(x, self, *params)
-        with ops.precision("f32"):
-            return segformer_forward(self, x, save=False)[0]
+    def _passes(self):
+        return segformer_forward, segformer_backward
 
 
 # ------------------------------------------------------------------------------------------------------------------ kernel wrappers
@@ -274,7 +248,7 @@ def segformer_forward(net: SegFormerLite, x, save=True):
     dev = x.device
     sm = B.Small(dev)
     n, _, H, W = x.shape
-    C = {}
+    C = {} if save else None
     cur = B.to_nhwc_pad(x, 4)
     feats = []
     for i in range(1, 5):
@@ -295,48 +269,30 @@ def segformer_forward(net: SegFormerLite, x, save=True):
     w = ops.hwio(net.linear_c1.weight)
     ops.conv_fwd(c1, w, net.linear_c1.bias, out=cat[..., 768:1024])
     lin["linear_c1"] = (c1, w, h1, w1)
-    fconv, fbn = net.linear_fuse[0], net.linear_fuse[1]
-    wf = ops.hwio(fconv.weight)
-    fz = ops.conv_fwd(cat, wf, fconv.bias)
-    fs, fh, fmean, finv, _ = B.bn_coeff(fz, fbn.state(), tr, sm)
-    fa = B.bn_apply(fz, fs, fh, None, relu=True)
-    hconv, hbn, oconv = net.head[0], net.head[1], net.head[3]
-    wh = ops.hwio(hconv.weight)
-    hz = ops.conv_fwd(fa, wh, hconv.bias)
-    hs, hh, hmean, hinv, _ = B.bn_coeff(hz, hbn.state(), tr, sm)
-    ha = B.bn_apply(hz, hs, hh, None, relu=True)
+    fa = conv_bn_relu(net.linear_fuse, 0, cat, tr, sm, C, "fuse", stats=False)
+    ha = conv_bn_relu(net.head, 0, fa, tr, sm, C, "head", stats=False)
+    oconv = net.head[3]
     wo = ops.hwio(oconv.weight)
     psmall, _ = B.outc_forward(ha, wo, oconv.bias)
     prob = torch.empty((n, 1, H, W), device=dev, dtype=torch.float32)
     check(lib.runet_bilinear_fwd(psmall.data_ptr(), prob.data_ptr(), n, h1, w1, H, W, ops.stream()))
     if save:
-        C.update(lin=lin, cat=cat, fuse=dict(t=fz, w=wf, s=fs, h=fh, mean=fmean, invstd=finv, x=cat),
-                 head=dict(t=hz, w=wh, s=hs, h=hh, mean=hmean, invstd=hinv, x=fa), out=(ha, wo, psmall), training=tr, size=(H, W))
-    return prob, (C if save else None)
+        C.update(lin=lin, cat=cat, out=(ha, wo, psmall), training=tr, size=(H, W))
+    return prob, C
 
 
 def segformer_backward(net: SegFormerLite, C, dprob):
-    """-> {parameter name: gradient with the parameter's logical shape}"""
+    """-> {parameter name: gradient in the parameter's PHYSICAL layout (conv weights HWIO, the depthwise ones [3, 3, 1, c])}"""
     G = {}
     dev = dprob.device
     tr = C["training"]
 
-    def vec(k):
-        return torch.empty(k, device=dev, dtype=torch.float32)
-
     def conv_grads(name, x, dy, k=1, stride=1, pad=0, cin_w=None):
         if stride == 1 and pad == k // 2:
-            G[name + ".weight"] = ops.conv_wgrad(x, dy, k, k, cin_w=cin_w).permute(3, 2, 0, 1)
+            G[name + ".weight"] = ops.conv_wgrad(x, dy, k, k, cin_w=cin_w)
         else:
-            G[name + ".weight"] = ops.conv_general_wgrad(x, dy, k, k, stride, pad, cin_w=cin_w).permute(3, 2, 0, 1)
-        G[name + ".bias"] = B.chan_sum(dy, vec(dy.shape[3]))
-
-    def bn_relu_back(name, cx, dy):
-        c = cx["t"].shape[3]
-        sums = vec(2 * c)
-        dt = B.bn_backward(dy, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, relu_shift=cx["h"], training=tr)
-        G[name + ".weight"], G[name + ".bias"] = sums[:c], sums[c:]
-        return dt
+            G[name + ".weight"] = ops.conv_general_wgrad(x, dy, k, k, stride, pad, cin_w=cin_w)
+        G[name + ".bias"] = B.chan_sum(dy, B.vec(dy.shape[3], dev))
 
     # ---- head
     ha, wo, psmall = C["out"]
@@ -345,20 +301,18 @@ def segformer_backward(net: SegFormerLite, C, dprob):
     dps = torch.empty((n, 1, h1, w1), device=dev, dtype=torch.float32)
     check(lib.runet_bilinear_bwd(dprob.data_ptr(), dps.data_ptr(), n, h1, w1, H, W, ops.stream()))
     dha = ops.empty_nhwc(n, h1, w1, ch, ha)
-    dwdb = vec(ch + 1)
+    dwdb = B.vec(ch + 1, dev)
     ws = B._ws(n, h1 * w1, ch, dev)
     check(lib.runet_outc_bwd(dps.data_ptr(), psmall.data_ptr(), ha.data_ptr(), ops.ld(ha), wo.data_ptr(), dha.data_ptr(), ops.ld(dha), ws.data_ptr(),
                              dwdb.data_ptr(), n * h1 * w1, ch, ops.stream()))
-    G["head.3.weight"] = dwdb[:ch].view(1, ch, 1, 1)
+    G["head.3.weight"] = dwdb[:ch].view(1, 1, ch, 1)
     G["head.3.bias"] = dwdb[ch:]
     hc = C["head"]
-    dhz = bn_relu_back("head.1", hc, dha)
-    conv_grads("head.0", hc["x"], dhz, 3, 1, 1)
+    dhz = B.conv_bn_relu_backward(hc, dha, G, "head", 0, tr)
     dfa = ops.conv_dgrad(dhz, hc["w"])
     del dhz
     fc = C["fuse"]
-    dfz = bn_relu_back("linear_fuse.1", fc, dfa)
-    conv_grads("linear_fuse.0", fc["x"], dfz)
+    dfz = B.conv_bn_relu_backward(fc, dfa, G, "linear_fuse", 0, tr)
     dcat = ops.conv_dgrad(dfz, fc["w"])
     del dfz, dfa
     # ---- decoder projections: gradient of each encoder feature's decoder branch
@@ -374,7 +328,7 @@ def segformer_backward(net: SegFormerLite, C, dprob):
     for i in (4, 3, 2, 1):
         ec = C[f"embed{i}"]
         cout = ec["t"].shape[3]
-        sums = vec(2 * cout)
+        sums = B.vec(2 * cout, dev)
         dt = bn_backward_gelu(dc, ec["t"], ec["mean"], ec["invstd"], ec["s"], sums, ec["h"], training=tr)
         G[f"patch_embed{i}.1.weight"], G[f"patch_embed{i}.1.bias"] = sums[:cout], sums[cout:]
         conv_grads(f"patch_embed{i}.0", ec["x"], dt, ec["k"], ec["stride"], ec["pad"], cin_w=3 if i == 1 else None)
@@ -394,7 +348,7 @@ def _stage_backward(sc, dcf, G, an, fn, conv_grads):
     conv_grads(fn + ".fc2", sc["a"], dcf)
     dhid, dwdb = dwconv_gelu_backward(sc["hid"], sc["z"], da, sc["wd"], sc["bd"])
     c = sc["hid"].shape[3]
-    G[fn + ".dwconv.weight"] = dwdb[:9 * c].view(3, 3, 1, c).permute(3, 2, 0, 1)
+    G[fn + ".dwconv.weight"] = dwdb[:9 * c].view(3, 3, 1, c)
     G[fn + ".dwconv.bias"] = dwdb[9 * c:]
     conv_grads(fn + ".fc1", sc["ca"], dhid)
     dca = dcf.clone()
@@ -414,24 +368,3 @@ def _stage_backward(sc, dcf, G, an, fn, conv_grads):
     conv_grads(an + ".q", x, dq)
     ops.conv_dgrad(dq, sc["wq"], out=dc, accumulate=True)
     return dc
-
-
-class _SegFormerFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        with ops.precision("f32"):
-            prob, C = segformer_forward(net, x, save=True)
-        ctx.C, ctx.net = C, net
-        return prob
-
-    @staticmethod
-    def backward(ctx, dprob):
-        if ctx.C is None:
-            raise RuntimeError("SegFormerLite backward called twice (activations were released after the first pass)")
-        net = ctx.net
-        with ops.precision("f32"), ops.wgrad_side_stream():
-            G = segformer_backward(net, ctx.C, dprob.contiguous())
-        ctx.C = None
-        named = list(net.named_parameters())
-        ops.deliver_grads(net, [p for _, p in named], [G[k] for k, _ in named])      # fixed addresses, assigned here (not returned to autograd)
-        return (None, None) + (None,) * len(named)

@@ -5,7 +5,7 @@ comne.py:650-653): same constructor, attribute tree and state_dict (enc1..4 / de
 triples, dec1 ending in Conv2d(64, 1, 3); pool = MaxPool2d(2, 2, return_indices=True), unpool = MaxUnpool2d(2, 2), no parameters),
 forward(x [N, 3, H, W]) -> sigmoid probabilities [N, 1, H, W].
 
-One autograd node with an explicit backward, NHWC inside, as unet.py (whose block helpers run every Conv-BN-ReLU stack here):
+One autograd node with an explicit backward, NHWC inside (baseline.py); unet.py's block helpers run every Conv-BN-ReLU stack:
   encoder end   the last BatchNorm + ReLU and the pool that is its only consumer in one pass (runet_bn_relu_maxpool2_fwd): the
                 full-resolution activation is never written; backward through the pooled-gradient BatchNorm kernels
                 (runet_bn_bwd_reduce_pooled / _apply_pooled), so its full-resolution gradient never exists either
@@ -23,7 +23,8 @@ import torch.nn as nn
 from . import blocks as B
 from . import ops
 from ._lib import check, lib
-from .model import BatchNorm2d, Conv2d, _Act, _Holder, _require_cuda
+from .baseline import FusedNet, check_image
+from .model import BatchNorm2d, Conv2d, _Act, _Holder
 from .unet import _block_backward, _block_forward
 
 # (block, convolutions as (cin, cout)) in registration order; dec1's second entry is the head conv (no BatchNorm behind it)
@@ -58,7 +59,9 @@ class _MaxUnpool2d(_Holder):
         self.kernel_size, self.stride = 2, 2
 
 
-class SegNet(nn.Module):
+class SegNet(FusedNet):
+    PRECISIONS = ops.PRECISIONS
+
     def __init__(self, n_classes=1):
         super().__init__()
         if n_classes != 1:
@@ -70,31 +73,12 @@ class SegNet(nn.Module):
             setattr(self, name, _stack(convs, head=(64, n_classes) if name == "dec1" else None))
         self.pool = _MaxPool2dIdx()
         self.unpool = _MaxUnpool2d()
-        self.precision = "f32"
 
-    def __setattr__(self, name, value):
-        # as UNet: a cross-rank BatchNorm hook (ddp.GradAllReducer(sync_bn=True)) would silently train a different function
-        if name == "sync_bn_hook" and value is not None:
-            raise NotImplementedError("SegNet has no SyncBatchNorm path (per-rank BatchNorm statistics only): construct GradAllReducer(sync_bn=False)")
-        super().__setattr__(name, value)
+    def _check_input(self, x):
+        check_image(x, 16, "four 2x2 poolings")
 
-    def set_precision(self, mode):
-        if mode not in ops.PRECISIONS:
-            raise ValueError(f"precision must be one of {ops.PRECISIONS}")
-        self.precision = mode
-        return self
-
-    def forward(self, x):
-        _require_cuda(x)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected x [N, 3, H, W]")
-        if x.shape[2] % 16 or x.shape[3] % 16:
-            raise ValueError("H and W must be multiples of 16 (four 2x2 poolings)")
-        params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _SegNetFn.apply(x, self, *params)
-        with ops.precision(self.precision):
-            return segnet_forward(self, x, save=False)[0]
+    def _passes(self):
+        return segnet_forward, segnet_backward
 
 
 def segnet_forward(net: SegNet, x, save=True):
@@ -130,7 +114,7 @@ def segnet_backward(net: SegNet, C, dprob):
     y, wh, prob = C["head"]
     n, h, w, c = y.shape
     dy = ops.empty_nhwc(n, h, w, c, y)
-    dwdb = torch.empty(9 * c + 1, device=dev, dtype=torch.float32)
+    dwdb = B.vec(9 * c + 1, dev)
     wsb = B.scratch(lib.runet_head3x3_bwd_workspace_floats(n, h, w, c), dev)
     check(lib.runet_head3x3_bwd(dprob.data_ptr(), prob.data_ptr(), y.data_ptr(), ops.ld(y), wh.data_ptr(), dy.data_ptr(), ops.ld(dy), wsb.data_ptr(),
                                 dwdb.data_ptr(), n, h, w, c, ops.stream()))
@@ -146,25 +130,3 @@ def segnet_backward(net: SegNet, C, dprob):
             return B.bn_backward_pooled(dp, idx, t, mean, invstd, scale, sums, shift, training=training)
         dy = _block_backward(C[name], dy, G, name, need_dx=lvl > 1, tail_bwd=pooled)
     return G
-
-
-class _SegNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        with ops.precision(net.precision):
-            prob, C = segnet_forward(net, x, save=True)
-        ctx.C, ctx.net = C, net
-        return prob
-
-    @staticmethod
-    def backward(ctx, dprob):
-        if ctx.C is None:
-            raise RuntimeError("SegNet backward called twice (activations were released after the first pass)")
-        net = ctx.net
-        with ops.precision(net.precision), ops.wgrad_side_stream():
-            G = segnet_backward(net, ctx.C, dprob.contiguous())
-        ctx.C = None
-        named = list(net.named_parameters())
-        out = [G[k].permute(3, 2, 0, 1) if G[k].dim() == 4 else G[k] for k, _ in named]     # physical HWIO -> logical OIHW
-        ops.deliver_grads(net, [p for _, p in named], out)      # fixed addresses, assigned here (not returned to autograd)
-        return (None, None) + (None,) * len(out)

@@ -6,7 +6,7 @@ BatchNorm2d, ReLU), upconv4..1 = ConvTranspose2d(k2, s2), final = Conv2d(64, n_c
 logits [N, n_classes, H, W]; trained with nn.CrossEntropyLoss on int64 masks (:304) - `ops.cross_entropy` is the fused equivalent.
 
 Built from the Robust U-Net path's kernels: 3x3 convolutions (Winograd / implicit GEMM / bf16), BatchNorm +
-ReLU, 2x2 max-pool, k2-s2 transposed convolution.  As there, the whole network is ONE autograd node with an explicit backward;
+ReLU, 2x2 max-pool, k2-s2 transposed convolution.  As there, the whole network is ONE autograd node with an explicit backward (baseline.py);
 `torch.cat([upsampled, skip])` is never materialised: the encoder block writes its output straight into the right half of the
 decoder's input buffer and the transposed convolution into the left half.
 """
@@ -18,7 +18,8 @@ import torch.nn as nn
 from . import blocks as B
 from . import ops
 from ._lib import check, lib
-from .model import BatchNorm2d, Conv2d, ConvTranspose2d, _Act, _logical, _require_cuda
+from .baseline import FusedNet
+from .model import BatchNorm2d, Conv2d, ConvTranspose2d, _Act
 
 CH = (64, 128, 256, 512)
 
@@ -37,7 +38,9 @@ class _Pool(nn.Module):
         return MaxPool2d(2)(x)
 
 
-class UNet(nn.Module):
+class UNet(FusedNet):
+    PRECISIONS = ops.PRECISIONS
+
     def __init__(self, n_channels=3, n_classes=2):
         super().__init__()
         if not 1 <= n_classes <= 4:
@@ -60,31 +63,13 @@ class UNet(nn.Module):
         self.dec1 = _conv_block(128, 64)
         self.final = Conv2d(64, n_classes, 1)
         self.pool = _Pool()
-        self.precision = "f32"
 
-    def __setattr__(self, name, value):
-        # ddp.GradAllReducer(sync_bn=True) / set_sync_bn(True) install a cross-rank BatchNorm hook on the model; this model's blocks use
-        # per-rank statistics only - refuse loudly instead of silently training a different function than the caller asked for
-        if name == "sync_bn_hook" and value is not None:
-            raise NotImplementedError("the plain UNet has no SyncBatchNorm path (per-rank BatchNorm statistics only): "
-                                      "construct GradAllReducer(sync_bn=False)")
-        super().__setattr__(name, value)
-
-    def set_precision(self, mode):
-        if mode not in ops.PRECISIONS:
-            raise ValueError(f"precision must be one of {ops.PRECISIONS}")
-        self.precision = mode
-        return self
-
-    def forward(self, x):
-        _require_cuda(x)
-        if x.shape[2] % 16 or x.shape[3] % 16:
+    def _check_input(self, x):
+        if x.shape[2] % 16 or x.shape[3] % 16:                # no channel check: n_channels is a constructor argument
             raise ValueError("H and W must be multiples of 16 (four 2x2 poolings)")
-        params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _UNetFn.apply(x, self, *params)
-        with ops.precision(self.precision):
-            return unet_forward(self, x, save=False)[0]
+
+    def _passes(self):
+        return unet_forward, unet_backward
 
 
 # ------------------------------------------------------------------------------------------------------------ blocks
@@ -125,15 +110,11 @@ def _block_backward(c, dout, G, pre, need_dx=True, tail_bwd=None):
     """Backward of _block_forward: parameter gradients (physical layouts) into G under `pre`.  tail_bwd(dout, t, mean, invstd, scale, sums,
     shift, training) -> dt replaces the last BatchNorm + ReLU backward when the forward fused its consumer."""
     dev = dout.device
-
-    def vec(n):
-        return torch.empty(n, device=dev, dtype=torch.float32)
-
     k = c["k"]
     d = dout
     for i in range(k, 0, -1):
         cout = c[f"w{i}"].shape[3]
-        sums = vec(2 * cout)
+        sums = B.vec(2 * cout, dev)
         if i == k and tail_bwd is not None:
             dt = tail_bwd(d, c[f"t{i}"], c[f"mean{i}"], c[f"invstd{i}"], c[f"s{i}"], sums, c[f"h{i}"], c["training"])
         elif i == k:
@@ -143,12 +124,12 @@ def _block_backward(c, dout, G, pre, need_dx=True, tail_bwd=None):
         G[f"{pre}.{3 * i - 2}.weight"], G[f"{pre}.{3 * i - 2}.bias"] = sums[:cout], sums[cout:]
         if i > 1:
             G[f"{pre}.{3 * i - 3}.weight"] = ops.conv_wgrad(c[f"a{i - 1}"], dt, 3, 3)
-            G[f"{pre}.{3 * i - 3}.bias"] = B.chan_sum(dt, vec(cout))
+            G[f"{pre}.{3 * i - 3}.bias"] = B.chan_sum(dt, B.vec(cout, dev))
             d = ops.conv_dgrad(dt, c[f"w{i}"])
             del dt
         else:
             G[f"{pre}.0.weight"] = ops.conv_wgrad(c["x"], dt, 3, 3, cin_w=c["cin_w"], on_side=need_dx)
-            G[f"{pre}.0.bias"] = B.chan_sum(dt, vec(cout))
+            G[f"{pre}.0.bias"] = B.chan_sum(dt, B.vec(cout, dev))
             return ops.conv_dgrad(dt, c["w1"]) if need_dx else None
 
 
@@ -218,7 +199,7 @@ def unet_backward(net: UNet, C, dlogits):
     k = net.n_classes
     dz4 = B.to_nhwc_pad(dlogits.contiguous(), 4)
     G["final.weight"] = ops.conv_wgrad(y, dz4, 1, 1, on_side=False)[..., :k].contiguous()
-    G["final.bias"] = B.chan_sum(dz4, torch.empty(4, device=dev, dtype=torch.float32))[:k]
+    G["final.bias"] = B.chan_sum(dz4, B.vec(4, dev))[:k]
     dy = ops.conv_dgrad(dz4, w4)
     dskip = {}
     for lvl in (1, 2, 3, 4):
@@ -227,38 +208,10 @@ def unet_backward(net: UNet, C, dlogits):
         dup, dskip[lvl] = dcat[..., :ch], dcat[..., ch:]
         yin, wup = C[f"up{lvl}"]
         G[f"upconv{lvl}.weight"] = ops.convt_wgrad(yin, dup)
-        G[f"upconv{lvl}.bias"] = B.chan_sum(dup, torch.empty(ch, device=dev, dtype=torch.float32))
+        G[f"upconv{lvl}.bias"] = B.chan_sum(dup, B.vec(ch, dev))
         dy = ops.convt_dgrad(dup, wup)
     dcur = _block_backward(C["bottleneck"], dy, G, "bottleneck")
     for lvl in (4, 3, 2, 1):
         B.maxpool_backward(dcur, C[f"pool{lvl}"], dx=dskip[lvl])          # adds the pooled path's gradient to the skip's
         dcur = _block_backward(C[f"enc{lvl}"], dskip[lvl], G, f"enc{lvl}", need_dx=lvl > 1)
     return G
-
-
-class _UNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        with ops.precision(net.precision):
-            logits, C = unet_forward(net, x, save=True)
-        ctx.C, ctx.net = C, net
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.C is None:
-            raise RuntimeError("UNet backward called twice (activations were released after the first pass)")
-        net = ctx.net
-        with ops.precision(net.precision), ops.wgrad_side_stream():
-            G = unet_backward(net, ctx.C, dlogits)
-        ctx.C = None
-        out = []
-        for name, p in net.named_parameters():
-            g = G[name]
-            if name.startswith("upconv") and name.endswith("weight"):
-                g = g.permute(2, 3, 0, 1)                  # physical [2, 2, cin, cout] -> logical [cin, cout, 2, 2]
-            elif g.dim() == 4:
-                g = g.permute(3, 2, 0, 1)                  # physical HWIO -> logical OIHW
-            out.append(g)
-        ops.deliver_grads(net, [p for _, p in net.named_parameters()], out)      # fixed addresses, assigned here (not returned to autograd)
-        return (None, None) + (None,) * len(out)

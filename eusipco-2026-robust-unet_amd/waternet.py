@@ -7,7 +7,7 @@ Drop-in for the reference's `WaterIndexModule` and `WaterNet` (trained there by 
 ChannelAttention on the bottleneck), `up3..1` (ConvTranspose2d k2 s2) with cat([up, skip]) into `dec3..1`, `outc` (Conv2d 1x1 64 -> 1,
 Sigmoid).  forward(x [N, 3, H, W]) -> sigmoid probabilities [N, 1, H, W].
 
-One autograd node with an explicit backward, NHWC inside, as unet.py / hrnet.py:
+One autograd node with an explicit backward, NHWC inside (baseline.py):
   front end     blocks.water_index_forward (csrc/water_index.hip): the image -> the 8-channel buffer [R, G, B, s0..s3, 0] in one pass, the
                 16-channel tensors of the index branch recomputed per pixel in registers; backward runet_water_index_bwd_reduce / _bwd_apply
                 from the gradient of channels 3..6 alone (no input gradient: the input is the image)
@@ -34,7 +34,8 @@ import torch.nn as nn
 
 from . import blocks as B
 from . import ops
-from .model import BatchNorm2d, ChannelAttention, Conv2d, ConvTranspose2d, _Act, _Holder, _require_cuda
+from .baseline import FusedNet, MaxPool2d, ReLU, Sigmoid, check_image, conv_bn_relu
+from .model import BatchNorm2d, ChannelAttention, Conv2d, ConvTranspose2d, _require_cuda
 
 CH = (64, 128, 256)
 BOTTLENECK = 512
@@ -45,26 +46,8 @@ PAIRS = (("enc1", CAT_IN, 64), ("enc2", 64, 128), ("enc3", 128, 256), ("bottlene
          ("dec1", 128, 64))
 
 
-class _ReLU(_Act):
-    def __init__(self, inplace=True):
-        super().__init__()
-        self.inplace = inplace
-
-
-class _Sigmoid(_Act):
-    pass
-
-
-class _MaxPool2d(_Holder):
-    """nn.MaxPool2d(2) stand-in (no parameters; the network's forward runs the pool kernel)."""
-
-    def __init__(self, kernel_size=2):
-        super().__init__()
-        self.kernel_size, self.stride = kernel_size, kernel_size
-
-
 def _pair(cin, cout):
-    return nn.Sequential(Conv2d(cin, cout, 3, padding=1), BatchNorm2d(cout), _ReLU(), Conv2d(cout, cout, 3, padding=1), BatchNorm2d(cout), _ReLU())
+    return nn.Sequential(Conv2d(cin, cout, 3, padding=1), BatchNorm2d(cout), ReLU(), Conv2d(cout, cout, 3, padding=1), BatchNorm2d(cout), ReLU())
 
 
 class WaterIndexModule(nn.Module):
@@ -75,7 +58,7 @@ class WaterIndexModule(nn.Module):
         super().__init__()
         if in_channels != 3:
             raise ValueError("the fused front end reads an RGB image (in_channels = 3, the reference's only use)")
-        self.index_conv = nn.Sequential(Conv2d(in_channels, INDEX_MID, 1), BatchNorm2d(INDEX_MID), _ReLU(), Conv2d(INDEX_MID, N_INDEX, 1), _Sigmoid())
+        self.index_conv = nn.Sequential(Conv2d(in_channels, INDEX_MID, 1), BatchNorm2d(INDEX_MID), ReLU(), Conv2d(INDEX_MID, N_INDEX, 1), Sigmoid())
 
     def handles(self):
         s = self.index_conv
@@ -89,64 +72,36 @@ class WaterIndexModule(nn.Module):
         return buf[..., 3:3 + N_INDEX].permute(0, 3, 1, 2)
 
 
-class WaterNet(nn.Module):
+class WaterNet(FusedNet):
+    FP32_ONLY = "the front-end kernels are fp32"
+
     def __init__(self, n_classes=1):
         super().__init__()
         if n_classes != 1:
             raise ValueError("the fused head implements the reference's n_classes=1 sigmoid head")
         self.n_classes = n_classes
         self.water_index = WaterIndexModule(3)
-        self.enc1, self.pool1 = _pair(CAT_IN, 64), _MaxPool2d(2)
-        self.enc2, self.pool2 = _pair(64, 128), _MaxPool2d(2)
-        self.enc3, self.pool3 = _pair(128, 256), _MaxPool2d(2)
+        self.enc1, self.pool1 = _pair(CAT_IN, 64), MaxPool2d(2)
+        self.enc2, self.pool2 = _pair(64, 128), MaxPool2d(2)
+        self.enc3, self.pool3 = _pair(128, 256), MaxPool2d(2)
         self.bottleneck = _pair(256, BOTTLENECK)
         self.water_attention = ChannelAttention(BOTTLENECK)
         self.up3, self.dec3 = ConvTranspose2d(512, 256, 2, stride=2), _pair(512, 256)
         self.up2, self.dec2 = ConvTranspose2d(256, 128, 2, stride=2), _pair(256, 128)
         self.up1, self.dec1 = ConvTranspose2d(128, 64, 2, stride=2), _pair(128, 64)
-        self.outc = nn.Sequential(Conv2d(64, n_classes, 1), _Sigmoid())
-        self.precision = "f32"
+        self.outc = nn.Sequential(Conv2d(64, n_classes, 1), Sigmoid())
 
-    def __setattr__(self, name, value):
-        # as HRNetWater: a cross-rank BatchNorm hook (ddp.GradAllReducer(sync_bn=True)) would silently train a different function
-        if name == "sync_bn_hook" and value is not None:
-            raise NotImplementedError("WaterNet has no SyncBatchNorm path (per-rank BatchNorm statistics only): construct GradAllReducer(sync_bn=False)")
-        super().__setattr__(name, value)
+    def _check_input(self, x):
+        check_image(x, 8, "three 2x2 poolings whose skips are concatenated with the upsampled path", fp32=True)
 
-    def set_precision(self, mode):
-        if mode != "f32":
-            raise ValueError("WaterNet runs in fp32 only (the front-end kernels are fp32)")
-        self.precision = mode
-        return self
-
-    def forward(self, x):
-        _require_cuda(x)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected x [N, 3, H, W]")
-        if x.shape[2] % 8 or x.shape[3] % 8:
-            raise ValueError("H and W must be multiples of 8 (three 2x2 poolings whose skips are concatenated with the upsampled path)")
-        if x.dtype != torch.float32:
-            raise TypeError("WaterNet computes in fp32")
-        params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _WaterNetFn.apply(x, self, *params)
-        with ops.precision("f32"):
-            return waternet_forward(self, x, save=False)[0]
+    def _passes(self):
+        return waternet_forward, waternet_backward
 
 
 def _pair_forward(seq, x, key, tr, sm, C, out=None):
     """Conv2d 3x3 -> BatchNorm2d -> ReLU, twice; the last activation goes to `out` (a concat half) when given"""
-    cur = x
-    for i in (0, 3):
-        conv, bn = seq[i], seq[i + 1]
-        w = ops.hwio(conv.weight)
-        fs = {} if tr else None
-        t = ops.conv_fwd(cur, w, conv.bias, stats=fs)
-        s, h, mean, invstd, _ = B.bn_coeff(t, bn.state(), tr, sm, fused=fs)
-        if C is not None:
-            C[f"{key}.{i}"] = dict(x=cur, w=w, t=t, s=s, h=h, mean=mean, invstd=invstd)
-        cur = B.bn_apply(t, s, h, None, relu=True, out=out if i == 3 else None)
-    return cur
+    a = conv_bn_relu(seq, 0, x, tr, sm, C, f"{key}.0")
+    return conv_bn_relu(seq, 3, a, tr, sm, C, f"{key}.3", out=out)
 
 
 def waternet_forward(net: WaterNet, x, save=True):
@@ -189,27 +144,16 @@ def waternet_backward(net: WaterNet, C, dprob):
     sink = B.DictSink(dev)
     G = sink.g
 
-    def vec(k):
-        return torch.empty(k, device=dev, dtype=torch.float32)
-
-    def conv_bn_relu_back(key, dy, out=None):
-        """gradient of a Conv2d -> BatchNorm2d -> ReLU activation -> (ctx, gradient of the convolution's output); parameter gradients into G"""
-        cx = C[key]
-        seq, i = key.rsplit(".", 1)
-        c = cx["t"].shape[3]
-        sums = vec(2 * c)
-        dt = B.bn_backward(dy, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, relu_shift=cx["h"], out=out, training=tr)
-        G[f"{seq}.{int(i) + 1}.weight"], G[f"{seq}.{int(i) + 1}.bias"] = sums[:c], sums[c:]
-        G[f"{key}.weight"] = ops.conv_wgrad(cx["x"], dt, 3, 3, cin_w=cx["w"].shape[2])
-        G[f"{key}.bias"] = B.chan_sum(dt, vec(c))
-        return cx, dt
+    def conv_bn_relu_back(seq, i, dy, out=None):
+        cx = C[f"{seq}.{i}"]
+        return cx, B.conv_bn_relu_backward(cx, dy, G, seq, i, tr, out=out)
 
     def pair_back(seq, dy):
         """backward of a two-convolution Sequential -> (ctx of its first convolution, gradient of that convolution's output)"""
-        cx, dt = conv_bn_relu_back(f"{seq}.3", dy)
+        cx, dt = conv_bn_relu_back(seq, 3, dy)
         da = ops.conv_dgrad(dt, cx["w"])
         del dt
-        return conv_bn_relu_back(f"{seq}.0", da, out=da)
+        return conv_bn_relu_back(seq, 0, da, out=da)
 
     y, wo, prob = C["head"]
     dy = B.outc_backward(dprob, prob, y, wo, sink, pre="outc.0.")
@@ -222,7 +166,7 @@ def waternet_backward(net: WaterNet, C, dprob):
         dup, dskip[lvl] = dcat[..., :ch], dcat[..., ch:]
         yin, wup = C["ups"][lvl]
         G[f"up{lvl}.weight"] = ops.convt_wgrad(yin, dup)
-        G[f"up{lvl}.bias"] = B.chan_sum(dup, vec(ch))
+        G[f"up{lvl}.bias"] = B.chan_sum(dup, B.vec(ch, dev))
         dy = ops.convt_dgrad(dup, wup)
     dy = B.ca_backward(C["ca"], dy, sink, pre="water_attention.")
     cx, dt = pair_back("bottleneck", dy)
@@ -243,30 +187,3 @@ def waternet_backward(net: WaterNet, C, dprob):
     G[pre + "3.weight"], G[pre + "3.bias"] = red[2 * INDEX_MID:k].view(1, 1, INDEX_MID, N_INDEX), red[k:]
     G[pre + "0.weight"], G[pre + "0.bias"] = app[:3 * INDEX_MID].view(1, 1, 3, INDEX_MID), app[3 * INDEX_MID:]
     return G
-
-
-class _WaterNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        with ops.precision("f32"):
-            prob, C = waternet_forward(net, x, save=True)
-        ctx.C, ctx.net = C, net
-        return prob
-
-    @staticmethod
-    def backward(ctx, dprob):
-        if ctx.C is None:
-            raise RuntimeError("WaterNet backward called twice (activations were released after the first pass)")
-        net = ctx.net
-        with ops.precision("f32"), ops.wgrad_side_stream():
-            G = waternet_backward(net, ctx.C, dprob.contiguous())
-        ctx.C = None
-        named = list(net.named_parameters())
-        out = []
-        for name, _ in named:
-            g = G[name]
-            if g.dim() == 4:                                   # physical -> logical: [2, 2, cin, cout] -> [cin, cout, 2, 2], HWIO -> OIHW
-                g = g.permute(2, 3, 0, 1) if name.startswith("up") else g.permute(3, 2, 0, 1)
-            out.append(g)
-        ops.deliver_grads(net, [p for _, p in named], out)      # fixed addresses, assigned here (not returned to autograd)
-        return (None, None) + (None,) * len(named)

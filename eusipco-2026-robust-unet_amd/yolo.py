@@ -6,7 +6,7 @@ LeakyReLU(0.1) triples in four stages, each ending in MaxPool2d(2, 2) (3x3 convo
 `seg_head` is four ConvTranspose2d(k4, s2, p1) -> BatchNorm2d -> LeakyReLU(0.1) triples and Conv2d(16, n_classes, 3).
 forward(x [N, 3, H, W]) -> sigmoid probabilities [N, 1, H, W].
 
-One autograd node with an explicit backward, NHWC inside, as segnet.py:
+One autograd node with an explicit backward, NHWC inside (baseline.py):
   stage end     the last BatchNorm + LeakyReLU and the pool that is its only consumer in one pass (runet_bn_leaky_maxpool2_fwd): the
                 full-resolution activation is never written; backward through the pooled-gradient BatchNorm kernels
                 (runet_bn_bwd_reduce_pooled_leaky / _apply_pooled_leaky), so its full-resolution gradient never exists either
@@ -30,8 +30,9 @@ import torch.nn as nn
 from . import blocks as B
 from . import ops
 from ._lib import check, lib
+from .baseline import FusedNet, MaxPool2d, check_image
 from .deeplab import ConvTranspose2dK4
-from .model import BatchNorm2d, Conv2d, _Act, _Holder, _require_cuda
+from .model import BatchNorm2d, Conv2d, _Act
 
 SLOPE = 0.1         # nn.LeakyReLU(0.1) (Main_Final.py:447 etc.)
 
@@ -46,14 +47,6 @@ class _LeakyReLU(_Act):
     def __init__(self, negative_slope=SLOPE, inplace=True):
         super().__init__()
         self.negative_slope, self.inplace = negative_slope, inplace
-
-
-class _MaxPool2d(_Holder):
-    """nn.MaxPool2d(2, stride=2) stand-in."""
-
-    def __init__(self):
-        super().__init__()
-        self.kernel_size, self.stride = 2, 2
 
 
 def _layout():
@@ -72,7 +65,9 @@ def _layout():
 LAYOUT = _layout()
 
 
-class YOLOSeg(nn.Module):
+class YOLOSeg(FusedNet):
+    FP32_ONLY = "the k4 transposed convolution has no bf16 / fp16 kernels"
+
     def __init__(self, n_classes=1):
         super().__init__()
         if n_classes != 1:
@@ -82,38 +77,19 @@ class YOLOSeg(nn.Module):
         for convs in STAGES:
             for cin, cout, k in convs:
                 mods += [Conv2d(cin, cout, k, padding=k // 2), BatchNorm2d(cout), _LeakyReLU()]
-            mods.append(_MaxPool2d())
+            mods.append(MaxPool2d(2))
         self.backbone = nn.Sequential(*mods)
         head = []
         for cin, cout in DEC:
             head += [ConvTranspose2dK4(cin, cout), BatchNorm2d(cout), _LeakyReLU()]
         head.append(Conv2d(16, n_classes, 3, padding=1))
         self.seg_head = nn.Sequential(*head)
-        self.precision = "f32"
 
-    def __setattr__(self, name, value):
-        # as SegNet: a cross-rank BatchNorm hook (ddp.GradAllReducer(sync_bn=True)) would silently train a different function
-        if name == "sync_bn_hook" and value is not None:
-            raise NotImplementedError("YOLOSeg has no SyncBatchNorm path (per-rank BatchNorm statistics only): construct GradAllReducer(sync_bn=False)")
-        super().__setattr__(name, value)
+    def _check_input(self, x):
+        check_image(x, 16, "four 2x2 poolings")
 
-    def set_precision(self, mode):
-        if mode != "f32":
-            raise ValueError("YOLOSeg runs in fp32 only (the k4 transposed convolution has no bf16 / fp16 kernels)")
-        self.precision = mode
-        return self
-
-    def forward(self, x):
-        _require_cuda(x)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected x [N, 3, H, W]")
-        if x.shape[2] % 16 or x.shape[3] % 16:
-            raise ValueError("H and W must be multiples of 16 (four 2x2 poolings)")
-        params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _YOLOSegFn.apply(x, self, *params)
-        with ops.precision("f32"):
-            return yolo_forward(self, x, save=False)[0]
+    def _passes(self):
+        return yolo_forward, yolo_backward
 
 
 def yolo_forward(net: YOLOSeg, x, save=True):
@@ -130,18 +106,16 @@ def yolo_forward(net: YOLOSeg, x, save=True):
     for si, (layers, _) in enumerate(LAYOUT):
         for li, (ci, bi) in enumerate(layers):
             conv, bn = bb[ci], bb[bi]
-            w = ops.hwio(conv.weight)
-            fs = {} if tr else None
-            t = ops.conv_fwd(cur, w, conv.bias, stats=fs)
-            s, h, mean, invstd, _ = B.bn_coeff(t, bn.state(), tr, sm, fused=fs)
+            t, s, h, cx = B.conv_bn_coeff(cur, ops.hwio(conv.weight), conv.bias, bn.state(), tr, sm, save=save)
             if save:
-                C[ci] = dict(x=cur, w=w, t=t, s=s, h=h, mean=mean, invstd=invstd, cin_w=w.shape[2])
+                C[ci] = cx
+                cx["cin_w"] = cx["w"].shape[2]
             if li + 1 < len(layers):
                 cur = B.bn_apply_leaky(t, s, h, SLOPE)
             else:
                 cur, idx = B.bn_leaky_maxpool_forward(t, s, h, SLOPE)
                 if save:
-                    C[ci]["idx"] = idx
+                    cx["idx"] = idx
     sh = net.seg_head
     for i in range(len(DEC)):
         ct, bn = sh[3 * i], sh[3 * i + 1]
@@ -164,32 +138,28 @@ def yolo_forward(net: YOLOSeg, x, save=True):
 
 
 def yolo_backward(net: YOLOSeg, C, dprob):
-    """-> {parameter name: gradient with the parameter's logical shape}"""
+    """-> {parameter name: gradient in the parameter's PHYSICAL layout (conv weights HWIO, transposed-conv weights [4, 4, cin, cout])}"""
     G = {}
     dev = dprob.device
     tr = C["training"]
-
-    def vec(k):
-        return torch.empty(k, device=dev, dtype=torch.float32)
-
     y, wh, prob = C["head"]
     n, hh, ww, c = y.shape
     dy = ops.empty_nhwc(n, hh, ww, c, y)
-    dwdb = vec(9 * c + 1)
+    dwdb = B.vec(9 * c + 1, dev)
     wsb = B.scratch(lib.runet_head3x3_bwd_workspace_floats(n, hh, ww, c), dev)
     check(lib.runet_head3x3_bwd(dprob.data_ptr(), prob.data_ptr(), y.data_ptr(), ops.ld(y), wh.data_ptr(), dy.data_ptr(), ops.ld(dy), wsb.data_ptr(),
                                 dwdb.data_ptr(), n, hh, ww, c, ops.stream()))
     hi = 3 * len(DEC)
-    G[f"seg_head.{hi}.weight"] = dwdb[:9 * c].view(3, 3, c, 1).permute(3, 2, 0, 1)
+    G[f"seg_head.{hi}.weight"] = dwdb[:9 * c].view(3, 3, c, 1)
     G[f"seg_head.{hi}.bias"] = dwdb[9 * c:]
     for i in reversed(range(len(DEC))):
         cx = C[f"dec{i}"]
         cout = cx["t"].shape[3]
-        sums = vec(2 * cout)
+        sums = B.vec(2 * cout, dev)
         draw = B.bn_backward_leaky(dy, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, cx["h"], SLOPE, training=tr)
         G[f"seg_head.{3 * i + 1}.weight"], G[f"seg_head.{3 * i + 1}.bias"] = sums[:cout], sums[cout:]
-        G[f"seg_head.{3 * i}.weight"] = ops.convt4_wgrad(cx["x"], draw).permute(2, 3, 0, 1)
-        G[f"seg_head.{3 * i}.bias"] = B.chan_sum(draw, vec(cout))
+        G[f"seg_head.{3 * i}.weight"] = ops.convt4_wgrad(cx["x"], draw)
+        G[f"seg_head.{3 * i}.bias"] = B.chan_sum(draw, B.vec(cout, dev))
         dy = ops.convt4_dgrad(draw, cx["w"])
         del draw
     for si in reversed(range(len(LAYOUT))):
@@ -198,7 +168,7 @@ def yolo_backward(net: YOLOSeg, C, dprob):
             ci, bi = layers[li]
             cx = C[ci]
             cout = cx["t"].shape[3]
-            sums = vec(2 * cout)
+            sums = B.vec(2 * cout, dev)
             if li + 1 == len(layers):
                 dt = B.bn_backward_pooled_leaky(dy, cx["idx"], cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, cx["h"], SLOPE, training=tr)
             else:
@@ -206,30 +176,9 @@ def yolo_backward(net: YOLOSeg, C, dprob):
             G[f"backbone.{bi}.weight"], G[f"backbone.{bi}.bias"] = sums[:cout], sums[cout:]
             first = si == 0 and li == 0
             k = cx["w"].shape[0]
-            G[f"backbone.{ci}.weight"] = ops.conv_wgrad(cx["x"], dt, k, k, cin_w=cx["cin_w"], on_side=not first).permute(3, 2, 0, 1)
-            G[f"backbone.{ci}.bias"] = B.chan_sum(dt, vec(cout))
+            G[f"backbone.{ci}.weight"] = ops.conv_wgrad(cx["x"], dt, k, k, cin_w=cx["cin_w"], on_side=not first)
+            G[f"backbone.{ci}.bias"] = B.chan_sum(dt, B.vec(cout, dev))
             if not first:
                 dy = ops.conv_dgrad(dt, cx["w"])
             del dt
     return G
-
-
-class _YOLOSegFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        with ops.precision("f32"):
-            prob, C = yolo_forward(net, x, save=True)
-        ctx.C, ctx.net = C, net
-        return prob
-
-    @staticmethod
-    def backward(ctx, dprob):
-        if ctx.C is None:
-            raise RuntimeError("YOLOSeg backward called twice (activations were released after the first pass)")
-        net = ctx.net
-        with ops.precision("f32"), ops.wgrad_side_stream():
-            G = yolo_backward(net, ctx.C, dprob.contiguous())
-        ctx.C = None
-        named = list(net.named_parameters())
-        ops.deliver_grads(net, [p for _, p in named], [G[k] for k, _ in named])      # fixed addresses, assigned here (not returned to autograd)
-        return (None, None) + (None,) * len(named)
