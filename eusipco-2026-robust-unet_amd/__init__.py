@@ -8,7 +8,8 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   CoastalDataset, prepare_dataset, ModelEvaluator;  DeepLabV3Plus (baseline);  UNet (train_water_segmentation.py's 2-class model);
   SegNet (comne.py's baseline);  YOLOSeg (Main_Final.py's YOLO-style baseline);  SegFormerLite (Extended_Baseline_Comparison.py's
   transformer baseline);  HRNetWater (the same script's multi-resolution baseline);  WaterNet / WaterIndexModule (its water-index U-Net baseline);
-  MSWNet / MultiScaleBlock (its multi-scale baseline);
+  MSWNet / MultiScaleBlock (its multi-scale baseline);  FastSCNN with DepthwiseSeparableConv, LearningToDownsample, PyramidPoolingFastSCNN,
+  GlobalFeatureExtractor, FeatureFusionModule and Classifier (comne.py's depthwise-separable baseline);
   CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
@@ -37,6 +38,8 @@ _LAZY = {
     "TrainStep": "trainer", "fit": "trainer", "UNet": "unet", "cross_entropy": "ops", "bilinear_resize": "ops",
     "SegNet": "segnet", "YOLOSeg": "yolo", "SegFormerLite": "segformer", "CoastlineExtractor": "predict",
     "HRNetWater": "hrnet", "WaterNet": "waternet", "WaterIndexModule": "waternet", "MSWNet": "mswnet", "MultiScaleBlock": "mswnet",
+    "FastSCNN": "fastscnn", "DepthwiseSeparableConv": "fastscnn", "LearningToDownsample": "fastscnn", "PyramidPoolingFastSCNN": "fastscnn",
+    "GlobalFeatureExtractor": "fastscnn", "FeatureFusionModule": "fastscnn", "Classifier": "fastscnn",
 }
 
 

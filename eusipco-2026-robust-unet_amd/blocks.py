@@ -1377,3 +1377,241 @@ def ms_stem_backward(ctx, de, G, pre="", want_dt=False):
     xp, _ = maxpool3s1_forward(x4, want_idx=False)
     _ms_param_grads(x4, xp, dt, p, G, pre)
     return dt if want_dt else None
+
+
+# =============================================================================== Fast-SCNN (csrc/fastscnn.hip, csrc/dwsep.hip)
+# DepthwiseSeparableConv (comne.py:305-320): depthwise 3x3 (stride 1 | 2, no bias) -> pointwise 1x1 (no bias) -> BatchNorm2d -> ReLU.  Default:
+# runet_dw3_fwd, then the shared 1x1 convolution and its weight gradient on the kept depthwise tensor.  RUNET_FUSED_DWSEP=1 (opt-in):
+# runet_dwsep_fwd / runet_dwsep_wgrad_pw, the depthwise tensor exists in neither pass - measured SLOWER kernel by kernel at the 16 x 256^2 step's
+# shapes (forward 29 / 16 / 30 us against 21 / 16 / 20, weight gradient 102 / 37 / 36 against 32 / 17 / 19; two step A/B runs disagree: the
+# layers are so small that the fused kernels run 64 - 1024 blocks of one 64-pixel tile each behind a 6 - 64 KB weight load, DESIGN.md
+# section 3.14), so it is the opt-in and the partner the default; RUNET_NO_FUSED_DWSEP=1 forces the partner whatever else is set.  Both share the
+# rest of the backward: the pointwise data gradient through the shared 1x1 dgrad, runet_dw3_wgrad / runet_dw3_dgrad behind it.
+# FeatureFusionModule (:403-427): RUNET_NO_FUSED_FFM=1 builds relu(bn(low) + upsample(bn(high))) from runet_bn_apply, runet_bn_bilinear_nhwc_fwd
+# / runet_bilinear_nhwc_fwd and runet_add_inplace instead of runet_ffm_fwd.  Read like FUSED_MS_STEM.
+FUSED_DWSEP = os.environ.get("RUNET_FUSED_DWSEP", "0") == "1" and os.environ.get("RUNET_NO_FUSED_DWSEP", "0") != "1"
+FUSED_FFM = os.environ.get("RUNET_NO_FUSED_FFM", "0") != "1"
+PYR_BINS = (1, 2, 3, 6)
+PYR_OFF = (0, 1, 5, 14)      # cells of the branches in front of branch j, per image
+PYR_ROWS = 50
+
+
+def _out_hw(h, w, stride):
+    return (h + stride - 1) // stride, (w + stride - 1) // stride
+
+
+def dw3_forward(x, wd, stride, out=None):
+    """x [n, h, w, c], wd [3, 3, 1, c] (HWIO) -> dwconv3x3(x), padding 1, [n, ceil(h / stride), ceil(w / stride), c]"""
+    n, h, w, c = x.shape
+    ho, wo = _out_hw(h, w, stride)
+    if out is None:
+        out = ops.empty_nhwc(n, ho, wo, c, x)
+    check(lib.runet_dw3_fwd(x.data_ptr(), ops.ld(x), wd.data_ptr(), out.data_ptr(), ops.ld(out), n, h, w, c, stride, ops.stream()))
+    return out
+
+
+def dw3_wgrad(x, dy, stride):
+    """-> the depthwise weight's gradient [3, 3, 1, c]"""
+    n, h, w, c = x.shape
+    ws = scratch(lib.runet_dw3_wgrad_workspace_floats(n, h, w, c, stride), x.device)
+    dw = torch.empty((3, 3, 1, c), device=x.device, dtype=torch.float32)
+    check(lib.runet_dw3_wgrad(x.data_ptr(), ops.ld(x), dy.data_ptr(), ops.ld(dy), ws.data_ptr(), ws.numel(), dw.data_ptr(), n, h, w, c, stride,
+                              ops.stream()))
+    return dw
+
+
+def dw3_dgrad(dy, wd, h, w, stride, out=None):
+    """dy [n, ceil(h / stride), ceil(w / stride), c] -> dx [n, h, w, c]"""
+    n, _, _, c = dy.shape
+    if out is None:
+        out = ops.empty_nhwc(n, h, w, c, dy)
+    check(lib.runet_dw3_dgrad(dy.data_ptr(), ops.ld(dy), wd.data_ptr(), out.data_ptr(), ops.ld(out), n, h, w, c, stride, ops.stream()))
+    return out
+
+
+class DWSepParams:
+    """wd [3, 3, 1, cin] / wp [1, 1, cin, cout]: the depthwise and pointwise weights in their physical (HWIO) layout; bn: BNState"""
+    __slots__ = ("wd", "wp", "bn", "stride")
+
+    def __init__(self, wd, wp, bn, stride):
+        self.wd, self.wp, self.bn, self.stride = wd, wp, bn, stride
+
+
+def dwsep_fusable(cin, cout):
+    return cin % 16 == 0 and cout % 16 == 0 and 16 <= cin <= 128 and 16 <= cout <= 128
+
+
+def dwsep_conv(x, p: DWSepParams, want_stats, fused=None):
+    """-> (t = pointwise(depthwise(x)), the depthwise tensor or None where it was never written, the BatchNorm statistics partials or None)"""
+    n, h, w, cin = x.shape
+    cout = p.wp.shape[3]
+    if (FUSED_DWSEP if fused is None else fused) and dwsep_fusable(cin, cout):
+        ho, wo = _out_hw(h, w, p.stride)
+        t = ops.empty_nhwc(n, ho, wo, cout, x)
+        nparts = lib.runet_dwsep_parts(n, h, w, p.stride)
+        part = torch.empty(nparts * cout * 3, device=x.device, dtype=torch.float32)
+        check(lib.runet_dwsep_fwd(x.data_ptr(), ops.ld(x), p.wd.data_ptr(), p.wp.data_ptr(), t.data_ptr(), ops.ld(t), part.data_ptr(), n, h, w, cin,
+                                  cout, p.stride, ops.stream()))
+        return t, None, dict(part=part, nparts=nparts)
+    d = dw3_forward(x, p.wd, p.stride)
+    fs = {} if want_stats else None
+    return ops.conv_fwd(d, p.wp, None, stats=fs), d, fs
+
+
+def dwsep_forward(x, p: DWSepParams, training, sm: Small, out=None, save=True, fused=None):
+    """-> (relu(bn(pointwise(depthwise(x)))), written to `out` - a concat slice - when given; context or None)"""
+    t, d, fs = dwsep_conv(x, p, training, fused)
+    s, h, mean, invstd, _ = bn_coeff(t, p.bn, training, sm, fused=fs if training else None)
+    a = bn_apply(t, s, h, None, relu=True, out=out)
+    return a, (dict(x=x, d=d, t=t, s=s, h=h, mean=mean, invstd=invstd, p=p) if save else None)
+
+
+def dwsep_wgrad_pw(x, wd, dt, stride):
+    """the pointwise weight's gradient [1, 1, cin, cout] = d^T dt with d = dwconv(x) recomputed"""
+    n, h, w, cin = x.shape
+    cout = dt.shape[3]
+    ws = scratch(lib.runet_dwsep_wgrad_pw_workspace_floats(n, h, w, cin, cout, stride), x.device)
+    dwp = torch.empty((1, 1, cin, cout), device=x.device, dtype=torch.float32)
+    check(lib.runet_dwsep_wgrad_pw(x.data_ptr(), ops.ld(x), wd.data_ptr(), dt.data_ptr(), ops.ld(dt), ws.data_ptr(), ws.numel(), dwp.data_ptr(), n, h,
+                                   w, cin, cout, stride, ops.stream()))
+    return dwp
+
+
+def dwsep_backward(cx, da, G, pre, training, need_dx=True):
+    """da: gradient of the activation.  G receives {pre}depthwise.weight, {pre}pointwise.weight, {pre}bn.weight / .bias (physical layouts).
+    -> the gradient of the layer's input (None unless need_dx)"""
+    p, x = cx["p"], cx["x"]
+    n, h, w, cin = x.shape
+    cout = p.wp.shape[3]
+    sums = vec(2 * cout, da.device)
+    dt = bn_backward(da, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, relu_shift=cx["h"], training=training)
+    G[pre + "bn.weight"], G[pre + "bn.bias"] = sums[:cout], sums[cout:]
+    if cx["d"] is None:
+        G[pre + "pointwise.weight"] = dwsep_wgrad_pw(x, p.wd, dt, p.stride)
+    else:
+        G[pre + "pointwise.weight"] = ops.conv_wgrad(cx["d"], dt, 1, 1)
+    dd = ops.conv_dgrad(dt, p.wp)
+    G[pre + "depthwise.weight"] = dw3_wgrad(x, dd, p.stride)
+    return dw3_dgrad(dd, p.wd, h, w, p.stride) if need_dx else None
+
+
+class PPMParams:
+    """ws [4] x [1, 1, c, c // 4] (HWIO), bs [4] x [c // 4], bns [4] x BNState: the four branches' Conv2d 1x1 and BatchNorm2d, bins 1 / 2 / 3 / 6"""
+    __slots__ = ("ws", "bs", "bns")
+
+    def __init__(self, ws, bs, bns):
+        self.ws, self.bs, self.bns = ws, bs, bns
+
+
+def _pyr_view(buf, j, n):
+    b = PYR_BINS[j]
+    return buf[n * PYR_OFF[j]:n * (PYR_OFF[j] + b * b)].view(n, b, b, buf.shape[1])
+
+
+def ppm_forward(cat, p: PPMParams, training, sm: Small, save=True):
+    """PyramidPoolingFastSCNN (comne.py:343-371).  cat [n, h, w, 2c]: channels [0, c) hold the module's input (written there by its producer),
+    channels [c, 2c) receive the four resized branches - the reference's torch.cat without a copy.  -> context or None"""
+    n, h, w, c2 = cat.shape
+    c = c2 // 2
+    cq = c // 4
+    x = cat[..., :c]
+    st = ops.stream()
+    pooled = torch.empty((PYR_ROWS * n, c), device=cat.device, dtype=torch.float32)
+    check(lib.runet_pyramid_pool_fwd(x.data_ptr(), ops.ld(x), pooled.data_ptr(), c, n, h, w, c, st))
+    acts = torch.empty((PYR_ROWS * n, cq), device=cat.device, dtype=torch.float32)
+    br = []
+    for j in range(4):
+        pj = _pyr_view(pooled, j, n)
+        fs = {} if training else None
+        t = ops.conv_fwd(pj, p.ws[j], p.bs[j], stats=fs)
+        s, hh, mean, invstd, _ = bn_coeff(t, p.bns[j], training, sm, fused=fs)
+        bn_apply(t, s, hh, None, relu=True, out=_pyr_view(acts, j, n))
+        br.append(dict(x=pj, w=p.ws[j], t=t, s=s, h=hh, mean=mean, invstd=invstd))
+    up = cat[..., c:]
+    check(lib.runet_pyramid_upsample_fwd(acts.data_ptr(), cq, up.data_ptr(), ops.ld(up), n, h, w, cq, st))
+    return dict(br=br, acts=acts, shape=(n, h, w, c)) if save else None
+
+
+def ppm_backward(cx, dcat, G, pre, training):
+    """dcat [n, h, w, 2c]: the gradient of the concat.  G receives {pre}convs.{j}.1.weight / .bias (the 1x1 convolutions) and
+    {pre}convs.{j}.2.weight / .bias (the BatchNorms).  -> the gradient of the module's input [n, h, w, c]"""
+    n, h, w, c = cx["shape"]
+    cq = c // 4
+    dev = dcat.device
+    st = ops.stream()
+    dup = dcat[..., c:]
+    dacts = torch.empty((PYR_ROWS * n, cq), device=dev, dtype=torch.float32)
+    check(lib.runet_pyramid_upsample_bwd(dup.data_ptr(), ops.ld(dup), dacts.data_ptr(), cq, n, h, w, cq, st))
+    dpooled = torch.empty((PYR_ROWS * n, c), device=dev, dtype=torch.float32)
+    for j, b in enumerate(cx["br"]):
+        sums = vec(2 * cq, dev)
+        dt = bn_backward(_pyr_view(dacts, j, n), b["t"], b["mean"], b["invstd"], b["s"], sums, relu_shift=b["h"], training=training)
+        G[f"{pre}convs.{j}.2.weight"], G[f"{pre}convs.{j}.2.bias"] = sums[:cq], sums[cq:]
+        G[f"{pre}convs.{j}.1.weight"] = ops.conv_wgrad(b["x"], dt, 1, 1)
+        G[f"{pre}convs.{j}.1.bias"] = chan_sum(dt, vec(cq, dev))
+        ops.conv_dgrad(dt, b["w"], out=_pyr_view(dpooled, j, n))
+    direct = dcat[..., :c]
+    dx = ops.empty_nhwc(n, h, w, c, dcat)
+    check(lib.runet_pyramid_pool_bwd(dpooled.data_ptr(), c, direct.data_ptr(), ops.ld(direct), dx.data_ptr(), ops.ld(dx), n, h, w, c, st))
+    return dx
+
+
+_ones_vec = {}
+
+
+def _ones(n, device):
+    buf = _ones_vec.get(device.index)
+    if buf is None or buf.numel() < n:
+        buf = torch.ones(max(int(n), 4096), device=device, dtype=torch.float32)
+        _ones_vec[device.index] = buf
+    return buf
+
+
+def ffm_forward(t_low, coef_low, t_high, coef_high, s, fused=None):
+    """FeatureFusionModule.forward (comne.py:421-427) behind its two 1x1 convolutions: t_low [n, s h, s w, c] and t_high [n, h, w, c] are their
+    raw outputs, coef_* = (scale, shift) of the BatchNorms.  -> y = relu(bn(t_low) + upsample_s(bn(t_high)))"""
+    n, h, w, c = t_high.shape
+    if tuple(t_low.shape) != (n, s * h, s * w, c):
+        raise ValueError(f"ffm_forward: t_low {tuple(t_low.shape)} is not {s} x {tuple(t_high.shape)}")
+    (sl, hl), (sh, hh) = coef_low, coef_high
+    if FUSED_FFM if fused is None else fused:
+        y = ops.empty_nhwc(n, s * h, s * w, c, t_low)
+        check(lib.runet_ffm_fwd(t_low.data_ptr(), ops.ld(t_low), t_high.data_ptr(), ops.ld(t_high), sl.data_ptr(), hl.data_ptr(), sh.data_ptr(),
+                                hh.data_ptr(), y.data_ptr(), ops.ld(y), n, h, w, s, c, ops.stream()))
+        return y
+    y = bn_apply(t_low, sl, hl)
+    up = ops.empty_nhwc(n, s * h, s * w, c, t_low)
+    if s in (2, 4):
+        bn_bilinear_forward(t_high, sh, hh, up, s, fused=True)
+    else:
+        _bilinear_nhwc(bn_apply(t_high, sh, hh), up)
+    check(lib.runet_add_inplace(y.data_ptr(), up.data_ptr(), y.numel(), ops.stream()))
+    return bn_apply(y, _ones(c, y.device), zeros(c, y.device), None, relu=True, out=y)
+
+
+def ffm_backward(dy, y, t_low, st_low, t_high, st_high, s, sums_low, sums_high, training=True):
+    """st_* = (mean, invstd, scale) of the two BatchNorms, sums_* [2c] receive their (dgamma | dbeta).
+    -> (dt_low [n, s h, s w, c], dt_high [n, h, w, c]): the gradients of the two 1x1 convolutions' outputs"""
+    n, ho, wo, c = y.shape
+    g = ops.empty_nhwc(n, ho, wo, c, y)
+    check(lib.runet_relu_mask_nhwc(dy.data_ptr(), ops.ld(dy), y.data_ptr(), ops.ld(y), g.data_ptr(), ops.ld(g), n * ho * wo, c, ops.stream()))
+    ml, il, sl = st_low
+    mh, ih, sh = st_high
+    dt_high = bn_bilinear_backward(g, t_high, mh, ih, sh, sums_high, s, training=training, fused=s in (2, 4))
+    dt_low = bn_backward(g, t_low, ml, il, sl, sums_low, out=g, training=training)
+    return dt_low, dt_high
+
+
+def up_sigmoid_forward(z, s):
+    """z [n, h, w] (the logit plane) -> sigmoid(upsample_s(z)) [n, 1, s h, s w]"""
+    n, h, w = z.shape
+    prob = torch.empty((n, 1, s * h, s * w), device=z.device, dtype=torch.float32)
+    check(lib.runet_up_sigmoid_fwd(z.data_ptr(), prob.data_ptr(), n, h, w, s, ops.stream()))
+    return prob
+
+
+def up_sigmoid_backward(dprob, prob, s):
+    n, _, ho, wo = prob.shape
+    dz = torch.empty((n, ho // s, wo // s), device=prob.device, dtype=torch.float32)
+    check(lib.runet_up_sigmoid_bwd(dprob.data_ptr(), prob.data_ptr(), dz.data_ptr(), n, ho // s, wo // s, s, ops.stream()))
+    return dz

@@ -829,7 +829,8 @@ __global__ __launch_bounds__(TPB) void outc_fwd_kernel(const float* __restrict__
         }
     }
 }
-// dx[p][c] = dl*w[c];  partial dw[c] = sum dl*x[p][c], db = sum dl;  dl = dprob*prob*(1-prob)
+// dx[p][c] = dl*w[c];  partial dw[c] = sum dl*x[p][c], db = sum dl;  dl = dprob*prob*(1-prob), or dprob itself when prob is NULL (the caller
+// hands the logit's gradient: Fast-SCNN's head, whose sigmoid sits behind an upsampling)
 __global__ __launch_bounds__(TPB) void outc_bwd_partial(const float* __restrict__ dprob, const float* __restrict__ prob,
                                                         const float* __restrict__ x, int ld, const float* __restrict__ w,
                                                         float* __restrict__ dx, int lddx, long P, int C, long pix_per_chunk,
@@ -843,8 +844,11 @@ __global__ __launch_bounds__(TPB) void outc_bwd_partial(const float* __restrict_
     if (row < rows) {
         const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col * 4);
         for (long p = p0 + row; p < p1; p += rows) {
-            const float pr = prob[p];
-            const float dl = dprob[p] * pr * (1.f - pr);
+            float dl = dprob[p];
+            if (prob) {
+                const float pr = prob[p];
+                dl = dl * pr * (1.f - pr);
+            }
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + p * ld + col * 4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) sw[q] += dl * v[q];
@@ -1210,7 +1214,7 @@ extern "C" int runet_outc_fwd(const float* x, int ld, const float* w, const floa
 
 extern "C" int runet_outc_bwd(const float* dprob, const float* prob, const float* x, int ld, const float* w, float* dx, int lddx,
                               float* workspace, float* dw_db, long pixels, int c, void* stream) {
-    RUNET_REQUIRE(dprob && prob && x && w && dx && workspace && dw_db, "null pointer");
+    RUNET_REQUIRE(dprob && x && w && dx && workspace && dw_db, "null pointer");
     REQ_C4(c);
     hipStream_t st = (hipStream_t)stream;
     long chunks, ppc;

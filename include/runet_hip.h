@@ -215,7 +215,8 @@ int runet_ag_bwd2_bn(const float* ds, const float* g1, int ldg, const float* x1,
                      float* dpre, int ldp, float* workspace, long workspace_floats, float* dwpsi_db, float* sums_g, float* sums_x, long pixels, int f,
                      void* stream);
 
-/* ---- outc: Conv2d(C, 1, 1) + Sigmoid (Main_Final.py:274-277) ---- */
+/* ---- outc: Conv2d(C, 1, 1) + Sigmoid (Main_Final.py:274-277) ----
+ * runet_outc_bwd: prob NULL = `dprob` is already the logit's gradient (a head whose sigmoid sits behind an upsampling: runet_up_sigmoid_bwd) */
 int runet_outc_fwd(const float* x, int ld, const float* w, const float* b, float* logit, float* prob, long pixels, int c, void* stream);
 int runet_outc_bwd(const float* dprob, const float* prob, const float* x, int ld, const float* w, float* dx, int lddx, float* workspace,
                    float* dw_db, long pixels, int c, void* stream);
@@ -683,6 +684,56 @@ int runet_ms_stem_bwd_apply(const float* x, long sn, long sc, long sh, long sw, 
                             const float* w5, const float* w4, const float* b1, const float* b3, const float* b5, const float* b4,
                             const float* scale, const float* shift, const float* de, int ldde, const float* mean, const float* invstd,
                             const float* sums, long m_total, float* dt, int lddt, void* stream);
+
+/* ---- Fast-SCNN baseline (comne.py:305-476; csrc/fastscnn.hip, csrc/dwsep.hip).  Its stem (3x3 stride 2 through runet_conv2d_general), 1x1
+ *      convolutions and their gradients, BatchNorm + ReLU, runet_outc_* and runet_bilinear_nhwc_bwd_sums are shared; these are the pieces
+ *      nothing else expresses.  NHWC fp32, pixel strides multiples of 4 floats that cover the channels (sources and destinations may be channel
+ *      slices of wider buffers), tensors 16-byte aligned.  No float atomics: every sum has a fixed order, two runs give identical bits.
+ * Depthwise 3x3, padding 1, stride 1 | 2, no bias (DepthwiseSeparableConv.depthwise, :310-311).  h, w_: the INPUT size, the output is
+ *   ceil(h / stride) x ceil(w_ / stride); w [3][3][c] (the HWIO memory of the [c, 1, 3, 3] parameter); c a multiple of 4, at most 1024.
+ *   runet_dw3_fwd: y = dwconv(x), taps in (r, s) order, one FMA per tap.
+ *   runet_dw3_wgrad: dw [3][3][c] from x and dy (chunk partials in `workspace`, runet_dw3_wgrad_workspace_floats floats - -1: bad shape -,
+ *     added in index order).  runet_dw3_dgrad: dx (input size) = the adjoint taps of dy, a gather.
+ * Depthwise -> pointwise (:316-318) without the depthwise tensor, cin and cout multiples of 16, at most 128; wd [3][3][cin], wp [cin][cout] (the
+ *   HWIO memory of the 1x1 weight):
+ *   runet_dwsep_fwd: t = (dwconv(x)) wp, the product on the exact f32-input MFMA, and part [runet_dwsep_parts(n_img, h, w_, stride)][cout][3]
+ *     = (count, mean, M2) of t per block of 64 output pixels, the layout runet_bn_stats_finalize consumes.
+ *   runet_dwsep_wgrad_pw: dwp [cin][cout] = d^T dt with d = dwconv(x) recomputed by the forward's arithmetic (bit-equal); workspace:
+ *     runet_dwsep_wgrad_pw_workspace_floats floats (-1: bad shape).
+ * Pyramid pooling (PyramidPoolingFastSCNN, :343-371), bins 1 / 2 / 3 / 6.  The branch-major buffers hold [n * 1 | n * 4 | n * 9 | n * 36] rows
+ *   (50 n rows), each branch a dense [n, b, b] image:
+ *   runet_pyramid_pool_fwd: the four nn.AdaptiveAvgPool2d (:354) of x [n, h, w_, c] in one launch, ATen's windows
+ *     [floor(i h / b), ceil((i + 1) h / b)).  runet_pyramid_pool_bwd: dx = direct (may be NULL; the concat's own slice of x, :364,371) + the four
+ *     levels' dpooled / window area, a gather.
+ *   runet_pyramid_upsample_fwd: the four F.interpolate(..., size=(h, w_), bilinear, align_corners=False) (:368) of a [50 n][cq] into the
+ *     channel slices [j cq, (j + 1) cq) of y [n, h, w_, 4 cq] (runet_bilinear_nhwc_fwd's source-index rule); _bwd: the gather adjoint.
+ * runet_ffm_fwd (FeatureFusionModule.forward, :421-427): y [n, s h, s w_, c] = relu((t_low * scale_low + shift_low) + (bilinear_s(t_high) *
+ *   scale_high + shift_high)), t_high [n, h, w_, c] the raw convolution output of the high branch (the BatchNorm affine commutes with the
+ *   interpolation), s an integer factor in 1..32.  runet_relu_mask_nhwc: g = dy where y > 0, else 0 (the ReLU's backward in front of the two
+ *   branches' BatchNorm backward: the high one gathers it first, runet_bilinear_nhwc_bwd_sums takes no mask).
+ * runet_up_sigmoid_fwd / _bwd (FastSCNN.forward, :474-476): prob [n, s h, s w_] = sigmoid(bilinear_s(z)) of the one-channel logit plane
+ *   z [n, h, w_] and its gather adjoint, s in 1..32 (runet_up2_sigmoid_* is the s = 2 form with 16-byte stores). */
+int runet_dw3_fwd(const float* x, int ldx, const float* w, float* y, int ldy, int n_img, int h, int w_, int c, int stride, void* stream);
+long runet_dw3_wgrad_workspace_floats(int n_img, int h, int w_, int c, int stride);
+int runet_dw3_wgrad(const float* x, int ldx, const float* dy, int lddy, float* workspace, long workspace_floats, float* dw, int n_img, int h,
+                    int w_, int c, int stride, void* stream);
+int runet_dw3_dgrad(const float* dy, int lddy, const float* w, float* dx, int lddx, int n_img, int h, int w_, int c, int stride, void* stream);
+int runet_dwsep_parts(int n_img, int h, int w_, int stride);
+int runet_dwsep_fwd(const float* x, int ldx, const float* wd, const float* wp, float* t, int ldt, float* part, int n_img, int h, int w_, int cin,
+                    int cout, int stride, void* stream);
+long runet_dwsep_wgrad_pw_workspace_floats(int n_img, int h, int w_, int cin, int cout, int stride);
+int runet_dwsep_wgrad_pw(const float* x, int ldx, const float* wd, const float* dt, int lddt, float* workspace, long workspace_floats, float* dwp,
+                         int n_img, int h, int w_, int cin, int cout, int stride, void* stream);
+int runet_pyramid_pool_fwd(const float* x, int ldx, float* pooled, int ldp, int n_img, int h, int w_, int c, void* stream);
+int runet_pyramid_pool_bwd(const float* dpooled, int ldp, const float* direct, int ldd, float* dx, int lddx, int n_img, int h, int w_, int c,
+                           void* stream);
+int runet_pyramid_upsample_fwd(const float* a, int lda, float* y, int ldy, int n_img, int h, int w_, int cq, void* stream);
+int runet_pyramid_upsample_bwd(const float* dy, int lddy, float* da, int lda, int n_img, int h, int w_, int cq, void* stream);
+int runet_ffm_fwd(const float* t_low, int ldl, const float* t_high, int ldh, const float* scale_low, const float* shift_low,
+                  const float* scale_high, const float* shift_high, float* y, int ldy, int n_img, int h, int w_, int s, int c, void* stream);
+int runet_relu_mask_nhwc(const float* dy, int lddy, const float* y, int ldy, float* g, int ldg, long pixels, int c, void* stream);
+int runet_up_sigmoid_fwd(const float* z, float* prob, int n_img, int h, int w_, int s, void* stream);
+int runet_up_sigmoid_bwd(const float* dprob, const float* prob, float* dz, int n_img, int h, int w_, int s, void* stream);
 
 /* ---- prediction: CoastlineExtractor (predict_coastline.py:336-618), everything between the uint8 upload and the two result masks
  *      (csrc/coastline.hip).  Masks are dense uint8 [h][w]; tile origins are device int32 [n_tiles][2] = (y0, x0), may be negative or overhang.
