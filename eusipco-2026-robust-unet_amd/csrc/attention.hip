@@ -873,12 +873,6 @@ inline int px_grid(long P) {
     if (b < 1) b = 1;
     return (int)b;
 }
-inline int ew_grid(long total_vec) {
-    long b = (total_vec + TPB - 1) / TPB;
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 inline int stream_chunks(int HW, int C, int& ppc) {
     const int rows = TPB / (C / 4);
     long per_img = ((long)HW * C + 16383) / 16384;

@@ -4,8 +4,8 @@
 //
 //   forward      z = b + dwconv(x), a = GELU(z); z is written only when the caller keeps it
 //   wgrad        g = da * GELU'(z), written (g may be da itself: each element is read and then written by the same lane), and the per-chunk
-//                partial sums of dw [3][3][C] and db [C]; a second kernel adds the chunks in order (fixed order, no atomics).  z is read,
-//                or (z NULL) recomputed from the nine neighbours of x that the dw sums read anyway, with the forward's arithmetic
+//                partial sums of dw [3][3][C] and db [C]; sum_parts<32> (runet_common.h) adds the chunks in order (fixed order, no atomics).
+//                z is read, or (z NULL) recomputed from the nine neighbours of x that the dw sums read anyway, with the forward's arithmetic
 //                (dwconv_z).  Keeping z measured faster: the model keeps it, the operator-level op recomputes
 //   data grad    dx = the adjoint taps of g (a gather: each dx element sums its nine neighbours of g in a fixed order)
 #include "runet_common.h"
@@ -13,15 +13,6 @@
 
 namespace {
 constexpr int TPB = 256;
-
-inline int ew_grid(long total) {
-    long b = (total + TPB - 1) / TPB;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // z = b + sum over the in-image taps of w[tap] * x[neighbour], taps in (r, s) order: the forward and the backward's recomputation share it
 __device__ __forceinline__ f32x4 dwconv_z(const float* __restrict__ x, int ldx, const float* __restrict__ w, const float* __restrict__ b,
@@ -54,11 +45,11 @@ __global__ __launch_bounds__(TPB) void dw3_gelu_fwd_kernel(const float* __restri
         const int yh = (int)(t % H);
         const long img = (t / H) * H * W;
         const f32x4 acc = dwconv_z(x, ldx, w, b, img, yh, xw, H, W, C, c);
-        if (z) *reinterpret_cast<f32x4*>(z + p * ldz + c) = acc;
+        if (z) st4(z + p * ldz + c, acc);
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = gelu_f(acc[e]);
-        *reinterpret_cast<f32x4*>(a + p * lda + c) = o;
+        st4(a + p * lda + c, o);
     }
 }
 
@@ -87,7 +78,7 @@ __global__ __launch_bounds__(TPB) void dw3_gelu_wgrad_kernel(const float* __rest
             f32x4 gv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) gv[e] = gelu_grad(dv[e], zv[e]);
-            *reinterpret_cast<f32x4*>(g + p * ldg + c) = gv;
+            st4(g + p * ldg + c, gv);
             acc[9] += gv;
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
@@ -102,34 +93,9 @@ __global__ __launch_bounds__(TPB) void dw3_gelu_wgrad_kernel(const float* __rest
             }
         }
 #pragma unroll
-        for (int k = 0; k < 10; ++k) *reinterpret_cast<f32x4*>(sm + (row * 10 + k) * C + c) = acc[k];
+        for (int k = 0; k < 10; ++k) st4(sm + (row * 10 + k) * C + c, acc[k]);
     }
-    __syncthreads();
-    for (int u = tid; u < 10 * C; u += TPB) {
-        double s = 0;
-        for (int r = 0; r < rows; ++r) s += sm[r * 10 * C + u];
-        part[(long)blockIdx.x * 10 * C + u] = (float)s;
-    }
-}
-
-// block = FCW consecutive outputs x FPL part-lanes: lane pl sums the chunks pl, pl + FPL, ... (coalesced rows of FCW floats), then an LDS pass
-// adds the FPL lane sums in lane order (fixed order)
-constexpr int FCW = 32, FPL = TPB / FCW;
-__global__ __launch_bounds__(TPB) void dw3_wgrad_final_kernel(const float* __restrict__ part, int nparts, int n10c, float* __restrict__ dwdb) {
-    __shared__ double red[TPB];
-    const int cl = threadIdx.x % FCW, pl = threadIdx.x / FCW;
-    const int u = blockIdx.x * FCW + cl;
-    double s = 0;
-    if (u < n10c) {
-#pragma unroll 8
-        for (int k = pl; k < nparts; k += FPL) s += part[(long)k * n10c + u];
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (pl == 0 && u < n10c) {
-        for (int j = 1; j < FPL; ++j) s += red[j * FCW + cl];
-        dwdb[u] = (float)s;
-    }
+    block_rows_to_part(sm, rows, 10 * C, part);
 }
 
 __global__ __launch_bounds__(TPB) void dw3_dgrad_kernel(const float* __restrict__ g, int ldg, const float* __restrict__ w, float* __restrict__ dx,
@@ -155,7 +121,7 @@ __global__ __launch_bounds__(TPB) void dw3_dgrad_kernel(const float* __restrict_
                 acc += ld4(w + (r * 3 + s) * C + c) * ld4(g + (img + (long)oh * W + ow) * ldg + c);
             }
         }
-        *reinterpret_cast<f32x4*>(dx + p * lddx + c) = acc;
+        st4(dx + p * lddx + c, acc);
     }
 }
 
@@ -168,17 +134,16 @@ int wgrad_chunks(long P, int C) {
 
 #define DW_REQ_SHAPE(n, h, w, c)                                                                                             \
     RUNET_REQUIRE((n) > 0 && (h) > 0 && (w) > 0 && (c) >= 4 && (c) % 4 == 0 && (c) <= 1024, "bad shape (c a multiple of 4, at most 1024)")
-#define DW_REQ_LD(ld, c, p) RUNET_REQUIRE((ld) >= (c) && (ld) % 4 == 0 && ((uintptr_t)(p) % 16) == 0, "pixel strides must be multiples of 4 floats that cover the channels, tensors 16-byte aligned")
 
 extern "C" int runet_dwconv3x3_gelu_fwd(const float* x, int ldx, const float* w, const float* b, float* z, int ldz, float* a, int lda, int n_img,
                                         int h, int w_, int c, void* stream) {
     RUNET_REQUIRE(x && w && b && a, "null pointer");
     DW_REQ_SHAPE(n_img, h, w_, c);
-    DW_REQ_LD(ldx, c, x);
-    DW_REQ_LD(lda, c, a);
-    if (z) DW_REQ_LD(ldz, c, z);
+    RUNET_REQ_LD(ldx, c, x);
+    RUNET_REQ_LD(lda, c, a);
+    if (z) RUNET_REQ_LD(ldz, c, z);
     RUNET_REQUIRE(((uintptr_t)w % 16) == 0 && ((uintptr_t)b % 16) == 0, "w and b must be 16-byte aligned");
-    hipLaunchKernelGGL(dw3_gelu_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, x, ldx, w, b, z, ldz,
+    hipLaunchKernelGGL(dw3_gelu_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, w, b, z, ldz,
                        a, lda, n_img, h, w_, c);
     RUNET_CHECK_LAUNCH();
 }
@@ -193,11 +158,11 @@ extern "C" int runet_dwconv3x3_gelu_bwd_wgrad(const float* x, int ldx, const flo
                                               int w_, int c, void* stream) {
     RUNET_REQUIRE(x && w && b && da && g && workspace && dwdb, "null pointer");
     DW_REQ_SHAPE(n_img, h, w_, c);
-    DW_REQ_LD(ldx, c, x);
-    DW_REQ_LD(ldda, c, da);
-    if (z) DW_REQ_LD(ldz, c, z);
+    RUNET_REQ_LD(ldx, c, x);
+    RUNET_REQ_LD(ldda, c, da);
+    if (z) RUNET_REQ_LD(ldz, c, z);
     RUNET_REQUIRE(((uintptr_t)w % 16) == 0 && ((uintptr_t)b % 16) == 0, "w and b must be 16-byte aligned");
-    DW_REQ_LD(ldg, c, g);
+    RUNET_REQ_LD(ldg, c, g);
     RUNET_REQUIRE(g == da ? ldg == ldda : true, "g may alias da only with the same pixel stride");
     const long P = (long)n_img * h * w_;
     const int chunks = wgrad_chunks(P, c);
@@ -207,17 +172,17 @@ extern "C" int runet_dwconv3x3_gelu_bwd_wgrad(const float* x, int ldx, const flo
     const size_t lds = (size_t)(TPB / (c / 4)) * 10 * c * sizeof(float);
     hipLaunchKernelGGL(dw3_gelu_wgrad_kernel, dim3(chunks), dim3(TPB), lds, st, x, ldx, w, b, da, ldda, z, ldz, g, ldg, workspace, n_img, h, w_, c,
                        ppc);
-    hipLaunchKernelGGL(dw3_wgrad_final_kernel, dim3(cdiv(10 * c, FCW)), dim3(TPB), 0, st, workspace, chunks, 10 * c, dwdb);
+    sum_parts<32>(workspace, chunks, 10 * c, dwdb, st);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_dwconv3x3_bwd_data(const float* g, int ldg, const float* w, float* dx, int lddx, int n_img, int h, int w_, int c, void* stream) {
     RUNET_REQUIRE(g && w && dx, "null pointer");
     DW_REQ_SHAPE(n_img, h, w_, c);
-    DW_REQ_LD(ldg, c, g);
-    DW_REQ_LD(lddx, c, dx);
+    RUNET_REQ_LD(ldg, c, g);
+    RUNET_REQ_LD(lddx, c, dx);
     RUNET_REQUIRE(((uintptr_t)w % 16) == 0, "w must be 16-byte aligned");
-    hipLaunchKernelGGL(dw3_dgrad_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, g, ldg, w, dx, lddx,
+    hipLaunchKernelGGL(dw3_dgrad_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, g, ldg, w, dx, lddx,
                        n_img, h, w_, c);
     RUNET_CHECK_LAUNCH();
 }

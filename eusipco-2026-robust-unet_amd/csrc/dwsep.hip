@@ -9,7 +9,7 @@
 //                          leaves through an LDS tile with 16-byte stores, and the tile's BatchNorm partials (count, mean, M2) per channel are
 //                          taken from that tile in pixel order - the layout runet_bn_stats_finalize consumes.
 //   runet_dwsep_wgrad_pw   dWp [cin][cout] = d^T dt over chunks of pixel tiles: d recomputed by the same dw3_point (bit-equal to the
-//                          forward's), dt staged beside it, the chunk partials added in index order by a second kernel.
+//                          forward's), dt staged beside it, the chunk partials added in index order by sum_parts<32> (runet_common.h).
 //
 // LDS rows are padded so that the four k-rows an MFMA operand load touches fall on disjoint banks.  No float atomics, fixed summation order
 // everywhere: two runs give the same bits.
@@ -22,9 +22,6 @@ constexpr int MAXC = 128;
 constexpr int MAX_CHUNKS = 128;
 
 __host__ __device__ inline int pad16(int c) { return (c % 32 == 16) ? c : c + 16; }      // row stride = 16 mod 32 floats
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, const f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // the depthwise output of output pixel p (over all images), channels c..c+3
 __device__ __forceinline__ f32x4 dw_at(const float* __restrict__ x, int ldx, const float* __restrict__ wd, long p, int c, int H, int W, int Ho, int Wo,
@@ -158,23 +155,6 @@ __global__ __launch_bounds__(TPB) void dwsep_wgrad_pw_kernel(const float* __rest
         }
 }
 
-// out[u] = sum_k part[k][u] in a fixed order (FCW consecutive outputs x FPL part-lanes per block, the lanes added in order)
-constexpr int FCW = 32, FPL = TPB / FCW;
-__global__ __launch_bounds__(TPB) void dwsep_sum_parts_kernel(const float* __restrict__ part, int nparts, int width, float* __restrict__ out) {
-    __shared__ double red[TPB];
-    const int cl = threadIdx.x % FCW, pl = threadIdx.x / FCW;
-    const int u = blockIdx.x * FCW + cl;
-    double s = 0;
-    if (u < width)
-        for (int k = pl; k < nparts; k += FPL) s += part[(long)k * width + u];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (pl == 0 && u < width) {
-        for (int j = 1; j < FPL; ++j) s += red[j * FCW + cl];
-        out[u] = (float)s;
-    }
-}
-
 inline size_t fwd_lds(int cin, int cout) { return (size_t)(cin * pad16(cout) + cin * ALD + TM * (cout + 4)) * sizeof(float); }
 inline size_t wgrad_lds(int cin, int cout) { return (size_t)TM * (pad16(cin) + pad16(cout)) * sizeof(float); }
 
@@ -198,7 +178,6 @@ inline int wgrad_chunks(int tiles, int& tpc) {
     RUNET_REQUIRE((n) > 0 && (h) > 0 && (w) > 0 && (cin) >= 16 && (cin) % 16 == 0 && (cin) <= MAXC && (cout) >= 16 && (cout) % 16 == 0 && \
                       (cout) <= MAXC && ((stride) == 1 || (stride) == 2) && (long)(n) * (h) * (w) < (1L << 31) * TM,                       \
                   "bad shape (cin and cout multiples of 16, at most 128; stride 1 or 2)")
-#define DS_REQ_LD(ld, c, p) RUNET_REQUIRE((ld) >= (c) && (ld) % 4 == 0 && ((uintptr_t)(p) % 16) == 0, "pixel strides must be multiples of 4 floats that cover the channels, tensors 16-byte aligned")
 
 extern "C" int runet_dwsep_parts(int n_img, int h, int w_, int stride) {
     if (n_img <= 0 || h <= 0 || w_ <= 0 || (stride != 1 && stride != 2)) return -1;
@@ -212,8 +191,8 @@ extern "C" int runet_dwsep_fwd(const float* x, int ldx, const float* wd, const f
                                int cin, int cout, int stride, void* stream) {
     RUNET_REQUIRE(x && wd && wp && t && part, "null pointer");
     DS_REQ_SHAPE(n_img, h, w_, cin, cout, stride);
-    DS_REQ_LD(ldx, cin, x);
-    DS_REQ_LD(ldt, cout, t);
+    RUNET_REQ_LD(ldx, cin, x);
+    RUNET_REQ_LD(ldt, cout, t);
     RUNET_REQUIRE(((uintptr_t)wd % 16) == 0 && ((uintptr_t)wp % 16) == 0, "weights must be 16-byte aligned");
     static bool lds_ok = false;
     RUNET_REQUIRE(allow_lds(dwsep_fwd_kernel, fwd_lds(MAXC, MAXC), lds_ok), "the device refused the kernel's LDS size");
@@ -236,8 +215,8 @@ extern "C" int runet_dwsep_wgrad_pw(const float* x, int ldx, const float* wd, co
                                     float* dwp, int n_img, int h, int w_, int cin, int cout, int stride, void* stream) {
     RUNET_REQUIRE(x && wd && dt && workspace && dwp, "null pointer");
     DS_REQ_SHAPE(n_img, h, w_, cin, cout, stride);
-    DS_REQ_LD(ldx, cin, x);
-    DS_REQ_LD(lddt, cout, dt);
+    RUNET_REQ_LD(ldx, cin, x);
+    RUNET_REQ_LD(lddt, cout, dt);
     RUNET_REQUIRE(((uintptr_t)wd % 16) == 0 && ((uintptr_t)workspace % 16) == 0, "wd and the workspace must be 16-byte aligned");
     int ho, wo, tpc;
     out_hw(h, w_, stride, ho, wo);
@@ -250,6 +229,6 @@ extern "C" int runet_dwsep_wgrad_pw(const float* x, int ldx, const float* wd, co
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(dwsep_wgrad_pw_kernel, dim3(chunks), dim3(TPB), wgrad_lds(cin, cout), st, x, ldx, wd, dt, lddt, workspace, P, h, w_, ho, wo, cin,
                        cout, stride, tiles, tpc);
-    hipLaunchKernelGGL(dwsep_sum_parts_kernel, dim3(cdiv((long)cin * cout, FCW)), dim3(TPB), 0, st, workspace, chunks, cin * cout, dwp);
+    sum_parts<32>(workspace, chunks, cin * cout, dwp, st);
     RUNET_CHECK_LAUNCH();
 }

@@ -1,7 +1,7 @@
 // Fast-SCNN baseline (the reference's comne.py:305-476): what the shared kernels cannot express.
 //
 //   depthwise      nn.Conv2d(c, c, 3, stride 1 | 2, padding 1, groups=c, bias=False) (:310-311): forward, weight gradient (chunk partials
-//                  plus an ordered final pass) and data gradient (a stride-aware gather).  dw3_common.h holds the per-pixel arithmetic.
+//                  plus the ordered final pass sum_parts<32>) and data gradient (a stride-aware gather).  dw3_common.h holds the per-pixel arithmetic.
 //   pyramid        PyramidPoolingFastSCNN (:343-371): AdaptiveAvgPool2d to 1 / 2 / 3 / 6 bins in one pass over x, written branch-major as
 //                  [n * 1 | n * 4 | n * 9 | n * 36] rows of c floats, so each branch is a dense [n, b, b, c] image for the shared 1x1
 //                  convolution and BatchNorm; the gather adjoint (with the concat's direct slice added); the four F.interpolate calls into
@@ -18,16 +18,6 @@
 
 namespace {
 constexpr int TPB = 256;
-
-inline int ew_grid(long total) {
-    long b = (total + TPB - 1) / TPB;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, const f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // ---------------------------------------------------------------------------------------------------------------- depthwise 3x3
 __global__ __launch_bounds__(TPB) void dw3_fwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w, float* __restrict__ y,
@@ -82,30 +72,7 @@ __global__ __launch_bounds__(TPB) void dw3_wgrad_kernel(const float* __restrict_
 #pragma unroll
         for (int k = 0; k < 9; ++k) st4(sm + (row * 9 + k) * C + c, acc[k]);
     }
-    __syncthreads();
-    for (int u = tid; u < 9 * C; u += TPB) {
-        double s = 0;
-        for (int r = 0; r < rows; ++r) s += sm[r * 9 * C + u];
-        part[(long)blockIdx.x * 9 * C + u] = (float)s;
-    }
-}
-
-// out[u] = sum_k part[k][u]: FCW consecutive outputs x FPL part-lanes per block, lane pl sums the partials pl, pl + FPL, ..., then an LDS pass
-// adds the FPL lane sums in lane order (fixed order)
-constexpr int FCW = 32, FPL = TPB / FCW;
-__global__ __launch_bounds__(TPB) void sum_parts_kernel(const float* __restrict__ part, int nparts, int width, float* __restrict__ out) {
-    __shared__ double red[TPB];
-    const int cl = threadIdx.x % FCW, pl = threadIdx.x / FCW;
-    const int u = blockIdx.x * FCW + cl;
-    double s = 0;
-    if (u < width)
-        for (int k = pl; k < nparts; k += FPL) s += part[(long)k * width + u];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (pl == 0 && u < width) {
-        for (int j = 1; j < FPL; ++j) s += red[j * FCW + cl];
-        out[u] = (float)s;
-    }
+    block_rows_to_part(sm, rows, 9 * C, part);
 }
 
 // dx[ih][iw] = sum over the taps (r, s), in that order, of w[r][s] * dy[oh][ow] for the outputs with oh * stride + r - 1 == ih (a gather)
@@ -273,17 +240,11 @@ __global__ __launch_bounds__(TPB) void pyramid_upsample_bwd_kernel(const float* 
         bilin_adj_range(bx, sw, W, ox_lo, ox_hi);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            int y0, y1;
-            float ly0, ly1;
-            bilin_src(oy, sh, b, y0, y1, ly0, ly1);
-            const float wy = (y0 == by ? ly0 : 0.f) + (y1 == by ? ly1 : 0.f);
+            const float wy = bilin_tap_weight(oy, sh, b, by);
             if (wy == 0.f) continue;
             f32x4 r = {0.f, 0.f, 0.f, 0.f};
             for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                int x0, x1;
-                float lx0, lx1;
-                bilin_src(ox, sw, b, x0, x1, lx0, lx1);
-                const float wx = (x0 == bx ? lx0 : 0.f) + (x1 == bx ? lx1 : 0.f);
+                const float wx = bilin_tap_weight(ox, sw, b, bx);
                 if (wx != 0.f) r += wx * ld4(gp + ((long)oy * W + ox) * lddy);
             }
             acc += wy * r;
@@ -369,24 +330,16 @@ __global__ __launch_bounds__(TPB) void up_sigmoid_bwd_kernel(const float* __rest
         const long r = i / W;
         const int iy = (int)(r % H);
         const long plane = (r / H) * Ho * Wo;
-        // src = (o + 0.5) / S - 0.5 in [i - 1, i + 1)  <=>  S i - S / 2 <= o <= S i + 3 S / 2 - 1 for an even S (hrnet.hip's adj_range); an odd S
-        // takes the wider S i - S .. S i + 2 S.  Taps outside the exact range get weight 0 below, so both give the same sum.
-        const int lo = (S & 1) ? S : S / 2, hi = (S & 1) ? 2 * S : 3 * S / 2 - 1;
-        const int oy_lo = max(0, S * iy - lo), oy_hi = min(Ho - 1, S * iy + hi);
-        const int ox_lo = max(0, S * ix - lo), ox_hi = min(Wo - 1, S * ix + hi);
+        int oy_lo, oy_hi, ox_lo, ox_hi;
+        upsample_adj_range(iy, S, Ho, oy_lo, oy_hi);
+        upsample_adj_range(ix, S, Wo, ox_lo, ox_hi);
         float acc = 0.f;
         for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            int y0, y1;
-            float ly0, ly1;
-            bilin_src(oy, inv, H, y0, y1, ly0, ly1);
-            const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
+            const float wy = bilin_tap_weight(oy, inv, H, iy);
             if (wy == 0.f) continue;
             float row = 0.f;
             for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                int x0, x1;
-                float lx0, lx1;
-                bilin_src(ox, inv, W, x0, x1, lx0, lx1);
-                const float wx = (x0 == ix ? lx0 : 0.f) + (x1 == ix ? lx1 : 0.f);
+                const float wx = bilin_tap_weight(ox, inv, W, ix);
                 if (wx != 0.f) {
                     const long q = plane + (long)oy * Wo + ox;
                     const float pr = prob[q];
@@ -402,7 +355,6 @@ __global__ __launch_bounds__(TPB) void up_sigmoid_bwd_kernel(const float* __rest
 
 #define FS_REQ_SHAPE(n, h, w, c)                                                                                             \
     RUNET_REQUIRE((n) > 0 && (h) > 0 && (w) > 0 && (c) >= 4 && (c) % 4 == 0 && (c) <= 1024, "bad shape (c a multiple of 4, at most 1024)")
-#define FS_REQ_LD(ld, c, p) RUNET_REQUIRE((ld) >= (c) && (ld) % 4 == 0 && ((uintptr_t)(p) % 16) == 0, "pixel strides must be multiples of 4 floats that cover the channels, tensors 16-byte aligned")
 #define FS_REQ_STRIDE(s) RUNET_REQUIRE((s) == 1 || (s) == 2, "stride must be 1 or 2")
 #define FS_REQ_PLANE(n, h, w, s) RUNET_REQUIRE((n) > 0 && (h) > 0 && (w) > 0 && (s) >= 1 && (s) <= 32 && (long)(n) * (h) * (w) * (s) * (s) < (1L << 40), "bad shape (factor s in 1..32)")
 
@@ -410,11 +362,11 @@ extern "C" int runet_dw3_fwd(const float* x, int ldx, const float* w, float* y, 
     RUNET_REQUIRE(x && w && y, "null pointer");
     FS_REQ_SHAPE(n_img, h, w_, c);
     FS_REQ_STRIDE(stride);
-    FS_REQ_LD(ldx, c, x);
-    FS_REQ_LD(ldy, c, y);
+    RUNET_REQ_LD(ldx, c, x);
+    RUNET_REQ_LD(ldy, c, y);
     RUNET_REQUIRE(((uintptr_t)w % 16) == 0, "w must be 16-byte aligned");
     const int ho = (h + stride - 1) / stride, wo = (w_ + stride - 1) / stride;
-    hipLaunchKernelGGL(dw3_fwd_kernel, dim3(ew_grid((long)n_img * ho * wo * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, x, ldx, w, y, ldy, n_img, h,
+    hipLaunchKernelGGL(dw3_fwd_kernel, dim3(ew_grid((long)n_img * ho * wo * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, w, y, ldy, n_img, h,
                        w_, ho, wo, c, stride);
     RUNET_CHECK_LAUNCH();
 }
@@ -430,8 +382,8 @@ extern "C" int runet_dw3_wgrad(const float* x, int ldx, const float* dy, int ldd
     RUNET_REQUIRE(x && dy && workspace && dw, "null pointer");
     FS_REQ_SHAPE(n_img, h, w_, c);
     FS_REQ_STRIDE(stride);
-    FS_REQ_LD(ldx, c, x);
-    FS_REQ_LD(lddy, c, dy);
+    RUNET_REQ_LD(ldx, c, x);
+    RUNET_REQ_LD(lddy, c, dy);
     const int ho = (h + stride - 1) / stride, wo = (w_ + stride - 1) / stride;
     const long P = (long)n_img * ho * wo;
     const int chunks = dw3_chunks(P, c);
@@ -440,7 +392,7 @@ extern "C" int runet_dw3_wgrad(const float* x, int ldx, const float* dy, int ldd
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)(TPB / (c / 4)) * 9 * c * sizeof(float);
     hipLaunchKernelGGL(dw3_wgrad_kernel, dim3(chunks), dim3(TPB), lds, st, x, ldx, dy, lddy, workspace, n_img, h, w_, ho, wo, c, stride, ppc);
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(cdiv(9 * c, FCW)), dim3(TPB), 0, st, workspace, chunks, 9 * c, dw);
+    sum_parts<32>(workspace, chunks, 9 * c, dw, st);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -449,11 +401,11 @@ extern "C" int runet_dw3_dgrad(const float* dy, int lddy, const float* w, float*
     RUNET_REQUIRE(dy && w && dx, "null pointer");
     FS_REQ_SHAPE(n_img, h, w_, c);
     FS_REQ_STRIDE(stride);
-    FS_REQ_LD(lddy, c, dy);
-    FS_REQ_LD(lddx, c, dx);
+    RUNET_REQ_LD(lddy, c, dy);
+    RUNET_REQ_LD(lddx, c, dx);
     RUNET_REQUIRE(((uintptr_t)w % 16) == 0, "w must be 16-byte aligned");
     const int ho = (h + stride - 1) / stride, wo = (w_ + stride - 1) / stride;
-    hipLaunchKernelGGL(dw3_dgrad_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, w, dx, lddx,
+    hipLaunchKernelGGL(dw3_dgrad_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, w, dx, lddx,
                        n_img, h, w_, ho, wo, c, stride);
     RUNET_CHECK_LAUNCH();
 }
@@ -462,8 +414,8 @@ extern "C" int runet_pyramid_pool_fwd(const float* x, int ldx, float* pooled, in
     RUNET_REQUIRE(x && pooled, "null pointer");
     FS_REQ_SHAPE(n_img, h, w_, c);
     RUNET_REQUIRE((long)n_img * 50 < (1L << 31) && (long)h * w_ < (1L << 31), "shape too large");
-    FS_REQ_LD(ldx, c, x);
-    FS_REQ_LD(ldp, c, pooled);
+    RUNET_REQ_LD(ldx, c, x);
+    RUNET_REQ_LD(ldp, c, pooled);
     hipLaunchKernelGGL(pyramid_pool_fwd_kernel, dim3(n_img * 50), dim3(TPB), 0, (hipStream_t)stream, x, ldx, pooled, ldp, (long)n_img, h, w_, c);
     RUNET_CHECK_LAUNCH();
 }
@@ -472,10 +424,10 @@ extern "C" int runet_pyramid_pool_bwd(const float* dpooled, int ldp, const float
                                       int c, void* stream) {
     RUNET_REQUIRE(dpooled && dx, "null pointer");
     FS_REQ_SHAPE(n_img, h, w_, c);
-    FS_REQ_LD(ldp, c, dpooled);
-    FS_REQ_LD(lddx, c, dx);
-    if (direct) FS_REQ_LD(ldd, c, direct);
-    hipLaunchKernelGGL(pyramid_pool_bwd_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, dpooled, ldp, direct,
+    RUNET_REQ_LD(ldp, c, dpooled);
+    RUNET_REQ_LD(lddx, c, dx);
+    if (direct) RUNET_REQ_LD(ldd, c, direct);
+    hipLaunchKernelGGL(pyramid_pool_bwd_kernel, dim3(ew_grid((long)n_img * h * w_ * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, dpooled, ldp, direct,
                        ldd, dx, lddx, (long)n_img, h, w_, c);
     RUNET_CHECK_LAUNCH();
 }
@@ -483,9 +435,9 @@ extern "C" int runet_pyramid_pool_bwd(const float* dpooled, int ldp, const float
 extern "C" int runet_pyramid_upsample_fwd(const float* a, int lda, float* y, int ldy, int n_img, int h, int w_, int cq, void* stream) {
     RUNET_REQUIRE(a && y, "null pointer");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0 && cq >= 4 && cq % 4 == 0 && cq <= 256, "bad shape (cq a multiple of 4, at most 256)");
-    FS_REQ_LD(lda, cq, a);
-    FS_REQ_LD(ldy, 4 * cq, y);
-    hipLaunchKernelGGL(pyramid_upsample_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * cq)), dim3(TPB), 0, (hipStream_t)stream, a, lda, y, ldy,
+    RUNET_REQ_LD(lda, cq, a);
+    RUNET_REQ_LD(ldy, 4 * cq, y);
+    hipLaunchKernelGGL(pyramid_upsample_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * cq, 8192)), dim3(TPB), 0, (hipStream_t)stream, a, lda, y, ldy,
                        (long)n_img, h, w_, cq);
     RUNET_CHECK_LAUNCH();
 }
@@ -493,9 +445,9 @@ extern "C" int runet_pyramid_upsample_fwd(const float* a, int lda, float* y, int
 extern "C" int runet_pyramid_upsample_bwd(const float* dy, int lddy, float* da, int lda, int n_img, int h, int w_, int cq, void* stream) {
     RUNET_REQUIRE(dy && da, "null pointer");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0 && cq >= 4 && cq % 4 == 0 && cq <= 256, "bad shape (cq a multiple of 4, at most 256)");
-    FS_REQ_LD(lddy, 4 * cq, dy);
-    FS_REQ_LD(lda, cq, da);
-    hipLaunchKernelGGL(pyramid_upsample_bwd_kernel, dim3(ew_grid((long)n_img * 50 * (cq / 4))), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, da, lda,
+    RUNET_REQ_LD(lddy, 4 * cq, dy);
+    RUNET_REQ_LD(lda, cq, da);
+    hipLaunchKernelGGL(pyramid_upsample_bwd_kernel, dim3(ew_grid((long)n_img * 50 * (cq / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, da, lda,
                        (long)n_img, h, w_, cq);
     RUNET_CHECK_LAUNCH();
 }
@@ -506,12 +458,12 @@ extern "C" int runet_ffm_fwd(const float* t_low, int ldl, const float* t_high, i
     RUNET_REQUIRE(t_low && t_high && scale_low && shift_low && scale_high && shift_high && y, "null pointer");
     FS_REQ_SHAPE(n_img, h, w_, c);
     RUNET_REQUIRE(s >= 1 && s <= 32, "the factor s must be in 1..32");
-    FS_REQ_LD(ldl, c, t_low);
-    FS_REQ_LD(ldh, c, t_high);
-    FS_REQ_LD(ldy, c, y);
+    RUNET_REQ_LD(ldl, c, t_low);
+    RUNET_REQ_LD(ldh, c, t_high);
+    RUNET_REQ_LD(ldy, c, y);
     RUNET_REQUIRE(((uintptr_t)scale_low % 16) == 0 && ((uintptr_t)shift_low % 16) == 0 && ((uintptr_t)scale_high % 16) == 0 &&
                       ((uintptr_t)shift_high % 16) == 0, "coefficient vectors must be 16-byte aligned");
-    hipLaunchKernelGGL(ffm_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * s * s * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, t_low, ldl, t_high,
+    hipLaunchKernelGGL(ffm_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * s * s * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, t_low, ldl, t_high,
                        ldh, scale_low, shift_low, scale_high, shift_high, y, ldy, (long)n_img, h, w_, s, c);
     RUNET_CHECK_LAUNCH();
 }
@@ -519,17 +471,17 @@ extern "C" int runet_ffm_fwd(const float* t_low, int ldl, const float* t_high, i
 extern "C" int runet_relu_mask_nhwc(const float* dy, int lddy, const float* y, int ldy, float* g, int ldg, long pixels, int c, void* stream) {
     RUNET_REQUIRE(dy && y && g, "null pointer");
     RUNET_REQUIRE(pixels > 0 && c >= 4 && c % 4 == 0, "bad shape (c a positive multiple of 4)");
-    FS_REQ_LD(lddy, c, dy);
-    FS_REQ_LD(ldy, c, y);
-    FS_REQ_LD(ldg, c, g);
-    hipLaunchKernelGGL(relu_mask_kernel, dim3(ew_grid(pixels * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, y, ldy, g, ldg, pixels, c);
+    RUNET_REQ_LD(lddy, c, dy);
+    RUNET_REQ_LD(ldy, c, y);
+    RUNET_REQ_LD(ldg, c, g);
+    hipLaunchKernelGGL(relu_mask_kernel, dim3(ew_grid(pixels * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, y, ldy, g, ldg, pixels, c);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_up_sigmoid_fwd(const float* z, float* prob, int n_img, int h, int w_, int s, void* stream) {
     RUNET_REQUIRE(z && prob, "null pointer");
     FS_REQ_PLANE(n_img, h, w_, s);
-    hipLaunchKernelGGL(up_sigmoid_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * s * s)), dim3(TPB), 0, (hipStream_t)stream, z, prob, (long)n_img, h,
+    hipLaunchKernelGGL(up_sigmoid_fwd_kernel, dim3(ew_grid((long)n_img * h * w_ * s * s, 8192)), dim3(TPB), 0, (hipStream_t)stream, z, prob, (long)n_img, h,
                        w_, s);
     RUNET_CHECK_LAUNCH();
 }
@@ -537,7 +489,7 @@ extern "C" int runet_up_sigmoid_fwd(const float* z, float* prob, int n_img, int 
 extern "C" int runet_up_sigmoid_bwd(const float* dprob, const float* prob, float* dz, int n_img, int h, int w_, int s, void* stream) {
     RUNET_REQUIRE(dprob && prob && dz, "null pointer");
     FS_REQ_PLANE(n_img, h, w_, s);
-    hipLaunchKernelGGL(up_sigmoid_bwd_kernel, dim3(ew_grid((long)n_img * h * w_)), dim3(TPB), 0, (hipStream_t)stream, dprob, prob, dz, (long)n_img, h,
+    hipLaunchKernelGGL(up_sigmoid_bwd_kernel, dim3(ew_grid((long)n_img * h * w_, 8192)), dim3(TPB), 0, (hipStream_t)stream, dprob, prob, dz, (long)n_img, h,
                        w_, s);
     RUNET_CHECK_LAUNCH();
 }

@@ -22,12 +22,6 @@ namespace {
 constexpr int TPB = 256;
 constexpr int MAX_PARTS = 1024;      // blocks of a partial reduction (rows of the caller's workspace)
 
-inline int ew_grid(long total) {
-    long b = (total + TPB - 1) / TPB;
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 // blocks of a (channel quad x pixel row) streaming kernel over P pixels of C channels: ~`elems` elements per block, at most `cap` blocks
 inline int pixel_chunks(long P, int C, long elems, int cap, long& ppc) {
     long chunks = (P * C + elems - 1) / elems;
@@ -35,20 +29,6 @@ inline int pixel_chunks(long P, int C, long elems, int cap, long& ppc) {
     if (chunks < 1) chunks = 1;
     ppc = (P + chunks - 1) / chunks;
     return (int)((P + ppc - 1) / ppc);
-}
-
-// the outputs of an integer-factor-S resize whose two source taps can include input index i (index 0 also takes the clamped ones):
-// src = (o + 0.5) / S - 0.5 in [i - 1, i + 1)  <=>  S i - S / 2 <= o <= S i + 3 S / 2 - 1
-template <int S>
-__device__ __forceinline__ void adj_range(int i, int out, int& lo, int& hi) {
-    lo = max(0, S * i - S / 2);
-    hi = min(out - 1, S * i + 3 * S / 2 - 1);
-}
-__device__ __forceinline__ float tap_weight(int o, float scale, int in, int i) {
-    int i0, i1;
-    float l0, l1;
-    bilin_src(o, scale, in, i0, i1, l0, l1);
-    return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ head, forward
@@ -71,11 +51,11 @@ __global__ __launch_bounds__(TPB) void hr_head_fwd_kernel(const float* __restric
         float acc = 0.f;
         if (p < P && own) {
             const float* tp = t + p * ldt;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(tp + lane * 4);
+            const f32x4 v = ld4(tp + lane * 4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc = __builtin_fmaf(wv[q], fmaxf(bn_pre(v[q], sc[q], sh[q]), 0.f), acc);
             for (int j = lane + L; j < cv; j += L) {                                       // C > 256 only
-                const f32x4 u = *reinterpret_cast<const f32x4*>(tp + j * 4);
+                const f32x4 u = ld4(tp + j * 4);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc = __builtin_fmaf(w[j * 4 + q], fmaxf(bn_pre(u[q], scale[j * 4 + q], shift[j * 4 + q]), 0.f), acc);
             }
@@ -113,7 +93,7 @@ __global__ __launch_bounds__(TPB) void up2_sigmoid_fwd_kernel(const float* __res
         float* o = prob + r * Wo + 4 * g;
         if (vec) {
             const f32x4 s = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(o) = s;
+            st4(o, s);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -134,20 +114,20 @@ __global__ __launch_bounds__(TPB) void up2_sigmoid_bwd_kernel(const float* __res
         const int iy = (int)(r % H);
         const long plane = (r / H) * Ho * Wo;
         int oy_lo, oy_hi;
-        adj_range<2>(iy, Ho, oy_lo, oy_hi);
+        upsample_adj_range(iy, 2, Ho, oy_lo, oy_hi);
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int ix = min(4 * g + e, W - 1);
             int ox_lo, ox_hi;
-            adj_range<2>(ix, Wo, ox_lo, ox_hi);
+            upsample_adj_range(ix, 2, Wo, ox_lo, ox_hi);
             float acc = 0.f;
             for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-                const float wy = tap_weight(oy, 0.5f, H, iy);
+                const float wy = bilin_tap_weight(oy, 0.5f, H, iy);
                 if (wy == 0.f) continue;
                 float row = 0.f;
                 for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                    const float wx = tap_weight(ox, 0.5f, W, ix);
+                    const float wx = bilin_tap_weight(ox, 0.5f, W, ix);
                     if (wx != 0.f) {
                         const long q = plane + (long)oy * Wo + ox;
                         const float pr = prob[q];
@@ -161,7 +141,7 @@ __global__ __launch_bounds__(TPB) void up2_sigmoid_bwd_kernel(const float* __res
         float* o = dz + r * W + 4 * g;
         if (vec) {
             const f32x4 s = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(o) = s;
+            st4(o, s);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -207,11 +187,11 @@ __global__ __launch_bounds__(TPB) void hr_head_bwd_reduce_partial(const float* _
         long p = p0 + row;
         for (; p + rows < p1; p += 2 * rows) {               // two pixels' loads in flight per thread; same summation order
             const float d0 = dz[p], d1 = dz[p + rows];
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(t + p * ldt + col * 4);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(t + (p + rows) * ldt + col * 4);
+            const f32x4 v0 = ld4(t + p * ldt + col * 4);
+            const f32x4 v1 = ld4(t + (p + rows) * ldt + col * 4);
             take(d0, v0); take(d1, v1);
         }
-        for (; p < p1; p += rows) take(dz[p], *reinterpret_cast<const f32x4*>(t + p * ldt + col * 4));
+        for (; p < p1; p += rows) take(dz[p], ld4(t + p * ldt + col * 4));
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int c = col * 4 + q;
@@ -219,27 +199,7 @@ __global__ __launch_bounds__(TPB) void hr_head_bwd_reduce_partial(const float* _
         }
         if (col == 0) sm[row * width + 3 * C] = sd;
     }
-    __syncthreads();
-    for (int j = tid; j < width; j += TPB) {
-        double a = 0;
-        for (int r = 0; r < rows; ++r) a += sm[r * width + j];
-        part[(long)blockIdx.x * width + j] = (float)a;
-    }
-}
-// out[j] = sum_k part[k][j]: 16 outputs x 16 part-lanes per block, each lane strides over the partials, then the lanes in order
-__global__ __launch_bounds__(TPB) void sum_parts_kernel(const float* __restrict__ part, int nparts, int width, float* __restrict__ out) {
-    __shared__ double red[TPB];
-    const int ol = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    const int j = blockIdx.x * 16 + ol;
-    double a = 0;
-    if (j < width)
-        for (int k = pl; k < nparts; k += 16) a += part[(long)k * width + j];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    if (pl == 0 && j < width) {
-        for (int l = 1; l < 16; ++l) a += red[l * 16 + ol];
-        out[j] = (float)a;
-    }
+    block_rows_to_part(sm, rows, width, part);
 }
 // dt = BatchNorm backward (runet_bn_bwd_apply's formula) of g = dz * w * (y > 0), g recomputed; sums = (dgamma | dbeta) as the reduce left them
 __global__ __launch_bounds__(TPB) void hr_head_bwd_apply_kernel(const float* __restrict__ dz, const float* __restrict__ t, int ldt,
@@ -261,14 +221,14 @@ __global__ __launch_bounds__(TPB) void hr_head_bwd_apply_kernel(const float* __r
     }
     for (long p = p0 + row; p < p1; p += rows) {
         const float d = dz[p];
-        const f32x4 v = *reinterpret_cast<const f32x4*>(t + p * ldt + col * 4);
+        const f32x4 v = ld4(t + p * ldt + col * 4);
         f32x4 r;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float g = bn_pre(v[q], sc[q], sh[q]) > 0.f ? d * wv[q] : 0.f;
             r[q] = bn_bwd_dx(g, sc[q], v[q], ca[q], cb[q]);
         }
-        *reinterpret_cast<f32x4*>(dt + p * lddt + col * 4) = r;
+        st4(dt + p * lddt + col * 4, r);
     }
 }
 
@@ -292,17 +252,17 @@ __global__ __launch_bounds__(TPB) void bn_bilinear_nhwc_fwd_kernel(const float* 
         float ly0, ly1, lx0, lx1;
         bilin_src(oy, inv, H, y0, y1, ly0, ly1);
         bilin_src(ox, inv, W, x0, x1, lx0, lx1);
-        const f32x4 a = *reinterpret_cast<const f32x4*>(xp + ((long)y0 * W + x0) * ldx);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(xp + ((long)y0 * W + x1) * ldx);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(xp + ((long)y1 * W + x0) * ldx);
-        const f32x4 e = *reinterpret_cast<const f32x4*>(xp + ((long)y1 * W + x1) * ldx);
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c);
-        const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + c);
+        const f32x4 a = ld4(xp + ((long)y0 * W + x0) * ldx);
+        const f32x4 b = ld4(xp + ((long)y0 * W + x1) * ldx);
+        const f32x4 d = ld4(xp + ((long)y1 * W + x0) * ldx);
+        const f32x4 e = ld4(xp + ((long)y1 * W + x1) * ldx);
+        const f32x4 sc = ld4(scale + c);
+        const f32x4 sh = ld4(shift + c);
         const f32x4 v = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d + lx1 * e);
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] = bn_pre(v[q], sc[q], sh[q]);
-        *reinterpret_cast<f32x4*>(y + p * ldy + c) = o;
+        st4(y + p * ldy + c, o);
     }
 }
 // g[n][h][w][0:C] = the adjoint (gather form, fixed order) of the slice gradient dy [n][S h][S w][0:C], and in the same pass the
@@ -330,22 +290,22 @@ __global__ __launch_bounds__(TPB) void bilinear_nhwc_bwd_sums_partial(const floa
             const long r = p / W;
             const int iy = (int)(r % H);
             const float* gp = dy + (r / H) * Ho * Wo * (long)lddy + col * 4;
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p * ldx + col * 4);
+            const f32x4 xv = ld4(x + p * ldx + col * 4);
             int oy_lo, oy_hi, ox_lo, ox_hi;
-            adj_range<S>(iy, Ho, oy_lo, oy_hi);
-            adj_range<S>(ix, Wo, ox_lo, ox_hi);
+            upsample_adj_range(iy, S, Ho, oy_lo, oy_hi);
+            upsample_adj_range(ix, S, Wo, ox_lo, ox_hi);
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-                const float wy = tap_weight(oy, inv, H, iy);
+                const float wy = bilin_tap_weight(oy, inv, H, iy);
                 if (wy == 0.f) continue;
                 f32x4 rsum = {0.f, 0.f, 0.f, 0.f};
                 for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                    const float wx = tap_weight(ox, inv, W, ix);
-                    if (wx != 0.f) rsum += wx * *reinterpret_cast<const f32x4*>(gp + ((long)oy * Wo + ox) * lddy);
+                    const float wx = bilin_tap_weight(ox, inv, W, ix);
+                    if (wx != 0.f) rsum += wx * ld4(gp + ((long)oy * Wo + ox) * lddy);
                 }
                 acc += wy * rsum;
             }
-            *reinterpret_cast<f32x4*>(g + p * ldg + col * 4) = acc;
+            st4(g + p * ldg + col * 4, acc);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 sg[q] += acc[q];
@@ -358,24 +318,18 @@ __global__ __launch_bounds__(TPB) void bilinear_nhwc_bwd_sums_partial(const floa
             sm[row * 2 * C + C + col * 4 + q] = sg[q];
         }
     }
-    __syncthreads();
-    for (int j = tid; j < 2 * C; j += TPB) {
-        double a = 0;
-        for (int r = 0; r < rows; ++r) a += sm[r * 2 * C + j];
-        part[(long)blockIdx.x * 2 * C + j] = (float)a;
-    }
+    block_rows_to_part(sm, rows, 2 * C, part);
 }
 }  // namespace
 
 #define REQ_HR_C(C) RUNET_REQUIRE((C) >= 4 && (C) <= 1024 && (C) % 4 == 0, "channels must be a multiple of 4, at most 1024")
-#define ALIGNED16(p) (((uintptr_t)(p) % 16) == 0)
 
 extern "C" int runet_hr_head_fwd(const float* t, int ldt, const float* scale, const float* shift, const float* w, const float* b, float* z, int n_img,
                                  int h, int w_, int c, void* stream) {
     RUNET_REQUIRE(t && scale && shift && w && b && z, "null pointer");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
     REQ_HR_C(c);
-    RUNET_REQUIRE(ldt >= c && ldt % 4 == 0 && ALIGNED16(t), "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
+    RUNET_REQUIRE(ldt >= c && ldt % 4 == 0 && RUNET_ALIGNED16(t), "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
     int L = 1;
     while (L < c / 4 && L < 64) L <<= 1;
     const long P = (long)n_img * h * w_;
@@ -388,8 +342,8 @@ extern "C" int runet_hr_head_fwd(const float* t, int ldt, const float* scale, co
 extern "C" int runet_up2_sigmoid_fwd(const float* z, float* prob, int n_img, int h, int w_, void* stream) {
     RUNET_REQUIRE(z && prob, "null pointer");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
-    RUNET_REQUIRE(ALIGNED16(prob), "pointers 16-byte aligned");
-    hipLaunchKernelGGL(up2_sigmoid_fwd_kernel, dim3(ew_grid((long)n_img * 2 * h * ((2 * w_ + 3) / 4))), dim3(TPB), 0, (hipStream_t)stream, z, prob,
+    RUNET_REQUIRE(RUNET_ALIGNED16(prob), "pointers 16-byte aligned");
+    hipLaunchKernelGGL(up2_sigmoid_fwd_kernel, dim3(ew_grid((long)n_img * 2 * h * ((2 * w_ + 3) / 4), 4096)), dim3(TPB), 0, (hipStream_t)stream, z, prob,
                        (long)n_img, h, w_);
     RUNET_CHECK_LAUNCH();
 }
@@ -397,8 +351,8 @@ extern "C" int runet_up2_sigmoid_fwd(const float* z, float* prob, int n_img, int
 extern "C" int runet_up2_sigmoid_bwd(const float* dprob, const float* prob, float* dz, int n_img, int h, int w_, void* stream) {
     RUNET_REQUIRE(dprob && prob && dz, "null pointer");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
-    RUNET_REQUIRE(ALIGNED16(dz), "pointers 16-byte aligned");
-    hipLaunchKernelGGL(up2_sigmoid_bwd_kernel, dim3(ew_grid((long)n_img * h * ((w_ + 3) / 4))), dim3(TPB), 0, (hipStream_t)stream, dprob, prob, dz,
+    RUNET_REQUIRE(RUNET_ALIGNED16(dz), "pointers 16-byte aligned");
+    hipLaunchKernelGGL(up2_sigmoid_bwd_kernel, dim3(ew_grid((long)n_img * h * ((w_ + 3) / 4), 4096)), dim3(TPB), 0, (hipStream_t)stream, dprob, prob, dz,
                        (long)n_img, h, w_);
     RUNET_CHECK_LAUNCH();
 }
@@ -414,7 +368,7 @@ extern "C" int runet_hr_head_bwd_reduce(const float* dz, const float* t, int ldt
     RUNET_REQUIRE(dz && t && scale && shift && w && mean && invstd && workspace && out, "null pointer");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
     REQ_HR_C(c);
-    RUNET_REQUIRE(ldt >= c && ldt % 4 == 0 && ALIGNED16(t), "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
+    RUNET_REQUIRE(ldt >= c && ldt % 4 == 0 && RUNET_ALIGNED16(t), "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
     const int width = 3 * c + 1, rows = TPB / (c / 4);
     const long P = (long)n_img * h * w_;
     long ppc;
@@ -423,7 +377,7 @@ extern "C" int runet_hr_head_bwd_reduce(const float* dz, const float* t, int ldt
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(hr_head_bwd_reduce_partial, dim3(chunks), dim3(TPB), (size_t)rows * width * sizeof(float), st, dz, t, ldt, scale, shift, w, mean,
                        invstd, P, c, ppc, workspace);
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(cdiv(width, 16)), dim3(TPB), 0, st, workspace, chunks, width, out);
+    sum_parts<16>(workspace, chunks, width, out, st);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -433,7 +387,7 @@ extern "C" int runet_hr_head_bwd_apply(const float* dz, const float* t, int ldt,
     RUNET_REQUIRE(dz && t && w && dt && mean && invstd && scale && shift && sums, "null pointer");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
     REQ_HR_C(c);
-    RUNET_REQUIRE(ldt >= c && ldt % 4 == 0 && lddt >= c && lddt % 4 == 0 && ALIGNED16(t) && ALIGNED16(dt),
+    RUNET_REQUIRE(ldt >= c && ldt % 4 == 0 && lddt >= c && lddt % 4 == 0 && RUNET_ALIGNED16(t) && RUNET_ALIGNED16(dt),
                   "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
     const long P = (long)n_img * h * w_;
     const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : P);
@@ -450,9 +404,9 @@ extern "C" int runet_bn_bilinear_nhwc_fwd(const float* x, int ldx, float* y, int
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
     RUNET_REQUIRE(s == 2 || s == 4, "the scale factor must be 2 or 4");
     REQ_HR_C(c);
-    RUNET_REQUIRE(ldx >= c && ldy >= c && ldx % 4 == 0 && ldy % 4 == 0 && ALIGNED16(x) && ALIGNED16(y) && ALIGNED16(scale) && ALIGNED16(shift),
+    RUNET_REQUIRE(ldx >= c && ldy >= c && ldx % 4 == 0 && ldy % 4 == 0 && RUNET_ALIGNED16(x) && RUNET_ALIGNED16(y) && RUNET_ALIGNED16(scale) && RUNET_ALIGNED16(shift),
                   "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
-    const int grid = ew_grid((long)n_img * s * h * s * w_ * (c / 4));
+    const int grid = ew_grid((long)n_img * s * h * s * w_ * (c / 4), 4096);
     hipStream_t st = (hipStream_t)stream;
     if (s == 2) hipLaunchKernelGGL(bn_bilinear_nhwc_fwd_kernel<2>, dim3(grid), dim3(TPB), 0, st, x, ldx, y, ldy, scale, shift, (long)n_img, h, w_, c);
     else hipLaunchKernelGGL(bn_bilinear_nhwc_fwd_kernel<4>, dim3(grid), dim3(TPB), 0, st, x, ldx, y, ldy, scale, shift, (long)n_img, h, w_, c);
@@ -471,7 +425,7 @@ extern "C" int runet_bilinear_nhwc_bwd_sums(const float* dy, int lddy, const flo
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
     RUNET_REQUIRE(s == 2 || s == 4, "the scale factor must be 2 or 4");
     REQ_HR_C(c);
-    RUNET_REQUIRE(lddy >= c && ldx >= c && ldg >= c && lddy % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && ALIGNED16(dy) && ALIGNED16(x) && ALIGNED16(g),
+    RUNET_REQUIRE(lddy >= c && ldx >= c && ldg >= c && lddy % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && RUNET_ALIGNED16(dy) && RUNET_ALIGNED16(x) && RUNET_ALIGNED16(g),
                   "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
     const int rows = TPB / (c / 4);
     const long P = (long)n_img * h * w_;
@@ -482,6 +436,6 @@ extern "C" int runet_bilinear_nhwc_bwd_sums(const float* dy, int lddy, const flo
     const size_t lds = (size_t)rows * 2 * c * sizeof(float);
     if (s == 2) hipLaunchKernelGGL(bilinear_nhwc_bwd_sums_partial<2>, dim3(chunks), dim3(TPB), lds, st, dy, lddy, x, ldx, mean, invstd, g, ldg, P, h, w_, c, ppc, workspace);
     else hipLaunchKernelGGL(bilinear_nhwc_bwd_sums_partial<4>, dim3(chunks), dim3(TPB), lds, st, dy, lddy, x, ldx, mean, invstd, g, ldg, P, h, w_, c, ppc, workspace);
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(cdiv(2 * c, 16)), dim3(TPB), 0, st, workspace, chunks, 2 * c, sums);
+    sum_parts<16>(workspace, chunks, 2 * c, sums, st);
     RUNET_CHECK_LAUNCH();
 }

@@ -10,13 +10,6 @@
 namespace {
 constexpr int TPB = 256;
 
-inline int ew_grid(long total) {
-    long b = (total + TPB - 1) / TPB;
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // ---- 2x2 max pool; idx byte = position (0..3) of the first maximum in scan order (ATen tie rule: strict >, NaN wins)
 __global__ __launch_bounds__(TPB) void maxpool2_fwd_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
                                                            unsigned char* __restrict__ idx, int N, int Ho, int Wo, int C) {
@@ -265,7 +258,7 @@ extern "C" int runet_maxpool2_fwd(const float* x, int ldx, float* y, int ldy, un
     RUNET_REQUIRE(x && y && idx, "null pointer");
     RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
-    hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, n_img, h / 2, w / 2, c);
+    hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, n_img, h / 2, w / 2, c);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -274,7 +267,7 @@ extern "C" int runet_maxpool2_bwd(const float* dy, int lddy, const unsigned char
     RUNET_REQUIRE(dy && dx && idx, "null pointer");
     RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
-    hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, n_img, h / 2, w / 2, c, accumulate);
+    hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, n_img, h / 2, w / 2, c, accumulate);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -285,7 +278,7 @@ extern "C" int runet_bn_relu_maxpool2_fwd(const float* t, int ldt, const float* 
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ldt >= c && ldy >= c && ldt % 4 == 0 && ldy % 4 == 0, "bad shape");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
     // unit: the dropout factor bn_apply_kernel multiplies by when no mask is given, passed at run time so the product stays in the code
-    hipLaunchKernelGGL(bn_act_maxpool2_fwd_kernel<ACT_RELU>, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
+    hipLaunchKernelGGL(bn_act_maxpool2_fwd_kernel<ACT_RELU>, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
                        n_img, h / 2, w / 2, c, 1.0f);
     RUNET_CHECK_LAUNCH();
 }
@@ -297,7 +290,7 @@ extern "C" int runet_bn_leaky_maxpool2_fwd(const float* t, int ldt, const float*
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ldt >= c && ldy >= c && ldt % 4 == 0 && ldy % 4 == 0, "bad shape");
     RUNET_REQUIRE(((uintptr_t)t % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
-    hipLaunchKernelGGL(bn_act_maxpool2_fwd_kernel<ACT_LEAKY>, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
+    hipLaunchKernelGGL(bn_act_maxpool2_fwd_kernel<ACT_LEAKY>, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, t, ldt, scale, shift, y, ldy, idx,
                        n_img, h / 2, w / 2, c, slope);
     RUNET_CHECK_LAUNCH();
 }
@@ -308,14 +301,14 @@ extern "C" int runet_maxunpool2_bwd(const float* du, int lddu, const unsigned ch
     RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && lddu >= c && ldp >= c && lddu % 4 == 0 && ldp % 4 == 0, "bad shape");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
-    hipLaunchKernelGGL(maxunpool2_bwd_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, du, lddu, idx, dpool, ldp, n_img, h / 2,
+    hipLaunchKernelGGL(maxunpool2_bwd_kernel, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, du, lddu, idx, dpool, ldp, n_img, h / 2,
                        w / 2, c);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_to_nhwc_pad(const float* x, long sn, long sc, long sh, long sw, float* y, int n_img, int c, int h, int w, int c_pad, void* stream) {
     RUNET_REQUIRE(x && y && c > 0 && c_pad >= c, "bad arguments");
-    hipLaunchKernelGGL(to_nhwc_pad_kernel, dim3(ew_grid((long)n_img * h * w)), dim3(TPB), 0, (hipStream_t)stream, x, sn, sc, sh, sw, y, n_img, c, h, w, c_pad);
+    hipLaunchKernelGGL(to_nhwc_pad_kernel, dim3(ew_grid((long)n_img * h * w, 4096)), dim3(TPB), 0, (hipStream_t)stream, x, sn, sc, sh, sw, y, n_img, c, h, w, c_pad);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -331,7 +324,7 @@ extern "C" int runet_bce_fwd(const float* prob, const float* target, long n, dou
 
 extern "C" int runet_bce_bwd(const float* prob, const float* target, const float* grad_out, float* dprob, long n, void* stream) {
     RUNET_REQUIRE(prob && target && dprob && n > 0, "bad arguments");
-    hipLaunchKernelGGL(bce_bwd_kernel, dim3(ew_grid(n)), dim3(TPB), 0, (hipStream_t)stream, prob, target, grad_out, dprob, n);
+    hipLaunchKernelGGL(bce_bwd_kernel, dim3(ew_grid(n, 4096)), dim3(TPB), 0, (hipStream_t)stream, prob, target, grad_out, dprob, n);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -419,7 +412,7 @@ extern "C" int runet_nonfinite_flag(const float* buf, long n, int* flag2, void* 
     RUNET_REQUIRE(buf && flag2 && n > 0 && ((uintptr_t)buf % 16) == 0, "bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(flag2, 0, sizeof(int), st) != hipSuccess) { runet_set_error("runet_nonfinite_flag: memset failed"); return RUNET_ELAUNCH; }
-    hipLaunchKernelGGL(nonfinite_kernel, dim3(ew_grid(n / 4 + 1)), dim3(TPB), 0, st, buf, n, flag2);
+    hipLaunchKernelGGL(nonfinite_kernel, dim3(ew_grid(n / 4 + 1, 4096)), dim3(TPB), 0, st, buf, n, flag2);
     hipLaunchKernelGGL(nonfinite_count_kernel, dim3(1), dim3(1), 0, st, flag2);
     RUNET_CHECK_LAUNCH();
 }
@@ -619,24 +612,24 @@ __global__ void sum_rows_kernel(const float* __restrict__ part, int nrows, int n
 extern "C" int runet_maxpool3s2_fwd(const float* x, int ldx, float* y, int ldy, unsigned char* idx, int n_img, int h, int w, int c, void* stream) {
     RUNET_REQUIRE(x && y && idx && c % 4 == 0 && c > 0 && h > 0 && w > 0, "bad arguments");
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3s2_fwd_kernel, dim3(ew_grid((long)n_img * ho * wo * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, n_img, h, w, ho, wo, c);
+    hipLaunchKernelGGL(maxpool3s2_fwd_kernel, dim3(ew_grid((long)n_img * ho * wo * (c / 4), 4096)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, n_img, h, w, ho, wo, c);
     RUNET_CHECK_LAUNCH();
 }
 extern "C" int runet_maxpool3s2_bwd(const float* dy, int lddy, const unsigned char* idx, float* dx, int lddx, int n_img, int h, int w, int c, void* stream) {
     RUNET_REQUIRE(dy && dx && idx && c % 4 == 0 && c > 0, "bad arguments");
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3s2_bwd_kernel, dim3(ew_grid((long)n_img * h * w * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, n_img, h, w, ho, wo, c);
+    hipLaunchKernelGGL(maxpool3s2_bwd_kernel, dim3(ew_grid((long)n_img * h * w * (c / 4), 4096)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, n_img, h, w, ho, wo, c);
     RUNET_CHECK_LAUNCH();
 }
 extern "C" int runet_broadcast_nc(const float* v_nc, float* y, int ldy, int n_img, int hw, int c, void* stream) {
     RUNET_REQUIRE(v_nc && y && c % 4 == 0 && c > 0, "bad arguments");
     const long total = (long)n_img * hw * (c / 4);
-    hipLaunchKernelGGL(broadcast_nc_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, v_nc, y, ldy, hw, c, total);
+    hipLaunchKernelGGL(broadcast_nc_kernel, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, v_nc, y, ldy, hw, c, total);
     RUNET_CHECK_LAUNCH();
 }
 extern "C" int runet_head3x3_fwd(const float* x, int ld, const float* w, const float* b, float* prob, int n_img, int h, int w_, int c, void* stream) {
     RUNET_REQUIRE(x && w && b && prob && c % 4 == 0 && c > 0 && c <= 64, "bad arguments (c multiple of 4, <= 64)");
-    hipLaunchKernelGGL(head3x3_fwd_kernel, dim3(ew_grid((long)n_img * h * w_)), dim3(TPB), 9 * c * sizeof(float), (hipStream_t)stream, x, ld, w, b, prob, n_img, h, w_, c);
+    hipLaunchKernelGGL(head3x3_fwd_kernel, dim3(ew_grid((long)n_img * h * w_, 4096)), dim3(TPB), 9 * c * sizeof(float), (hipStream_t)stream, x, ld, w, b, prob, n_img, h, w_, c);
     RUNET_CHECK_LAUNCH();
 }
 extern "C" long runet_head3x3_bwd_workspace_floats(int n_img, int h, int w_, int c) { return 1024L * (9 * c + 1); }
@@ -661,7 +654,7 @@ __global__ __launch_bounds__(TPB) void add_inplace_kernel(float* __restrict__ ds
 }  // namespace
 extern "C" int runet_add_inplace(float* dst, const float* src, long n, void* stream) {
     RUNET_REQUIRE(dst && src && n > 0 && ((uintptr_t)dst % 16) == 0 && ((uintptr_t)src % 16) == 0, "bad arguments");
-    hipLaunchKernelGGL(add_inplace_kernel, dim3(ew_grid(n / 4 + 1)), dim3(TPB), 0, (hipStream_t)stream, dst, src, n);
+    hipLaunchKernelGGL(add_inplace_kernel, dim3(ew_grid(n / 4 + 1, 4096)), dim3(TPB), 0, (hipStream_t)stream, dst, src, n);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -699,17 +692,11 @@ __global__ __launch_bounds__(TPB) void bilinear_bwd_kernel(const float* __restri
         bilin_adj_range(ix, sw, Wo, ox_lo, ox_hi);
         float acc = 0.f;
         for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            int y0, y1;
-            float ly0, ly1;
-            bilin_src(oy, sh, H, y0, y1, ly0, ly1);
-            const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
+            const float wy = bilin_tap_weight(oy, sh, H, iy);
             if (wy == 0.f) continue;
             float row = 0.f;
             for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                int x0, x1;
-                float lx0, lx1;
-                bilin_src(ox, sw, W, x0, x1, lx0, lx1);
-                const float wx = (x0 == ix ? lx0 : 0.f) + (x1 == ix ? lx1 : 0.f);
+                const float wx = bilin_tap_weight(ox, sw, W, ix);
                 if (wx != 0.f) row += wx * gp[(long)oy * Wo + ox];
             }
             acc += wy * row;
@@ -758,17 +745,11 @@ __global__ __launch_bounds__(TPB) void bilinear_nhwc_bwd_kernel(const float* __r
         bilin_adj_range(ix, sw, Wo, ox_lo, ox_hi);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            int y0, y1;
-            float ly0, ly1;
-            bilin_src(oy, sh, H, y0, y1, ly0, ly1);
-            const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
+            const float wy = bilin_tap_weight(oy, sh, H, iy);
             if (wy == 0.f) continue;
             f32x4 row = {0.f, 0.f, 0.f, 0.f};
             for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                int x0, x1;
-                float lx0, lx1;
-                bilin_src(ox, sw, W, x0, x1, lx0, lx1);
-                const float wx = (x0 == ix ? lx0 : 0.f) + (x1 == ix ? lx1 : 0.f);
+                const float wx = bilin_tap_weight(ox, sw, W, ix);
                 if (wx != 0.f) row += wx * *reinterpret_cast<const f32x4*>(gp + ((long)oy * Wo + ox) * lddy);
             }
             acc += wy * row;
@@ -790,14 +771,14 @@ __global__ __launch_bounds__(TPB) void mul_pixel_kernel(const float* __restrict_
 
 extern "C" int runet_bilinear_fwd(const float* x, float* y, long planes, int h, int w, int ho, int wo, void* stream) {
     RUNET_REQUIRE(x && y && planes > 0 && h > 0 && w > 0 && ho > 0 && wo > 0, "bad arguments");
-    hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(ew_grid(planes * ho * wo)), dim3(TPB), 0, (hipStream_t)stream, x, y, planes, h, w, ho, wo,
+    hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(ew_grid(planes * ho * wo, 4096)), dim3(TPB), 0, (hipStream_t)stream, x, y, planes, h, w, ho, wo,
                        (float)h / (float)ho, (float)w / (float)wo);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_bilinear_bwd(const float* dy, float* dx, long planes, int h, int w, int ho, int wo, void* stream) {
     RUNET_REQUIRE(dy && dx && planes > 0 && h > 0 && w > 0 && ho > 0 && wo > 0, "bad arguments");
-    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(ew_grid(planes * h * w)), dim3(TPB), 0, (hipStream_t)stream, dy, dx, planes, h, w, ho, wo,
+    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(ew_grid(planes * h * w, 4096)), dim3(TPB), 0, (hipStream_t)stream, dy, dx, planes, h, w, ho, wo,
                        (float)h / (float)ho, (float)w / (float)wo);
     RUNET_CHECK_LAUNCH();
 }
@@ -807,7 +788,7 @@ extern "C" int runet_bilinear_nhwc_fwd(const float* x, int ldx, float* y, int ld
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ho > 0 && wo > 0 && c > 0 && c % 4 == 0, "bad shape (c must be a positive multiple of 4)");
     RUNET_REQUIRE(ldx >= c && ldy >= c && ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0,
                   "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
-    hipLaunchKernelGGL(bilinear_nhwc_fwd_kernel, dim3(ew_grid((long)n_img * ho * wo * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy,
+    hipLaunchKernelGGL(bilinear_nhwc_fwd_kernel, dim3(ew_grid((long)n_img * ho * wo * (c / 4), 4096)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy,
                        n_img, h, w, ho, wo, c, (float)h / (float)ho, (float)w / (float)wo);
     RUNET_CHECK_LAUNCH();
 }
@@ -817,14 +798,14 @@ extern "C" int runet_bilinear_nhwc_bwd(const float* dy, int lddy, float* dx, int
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ho > 0 && wo > 0 && c > 0 && c % 4 == 0, "bad shape (c must be a positive multiple of 4)");
     RUNET_REQUIRE(lddy >= c && lddx >= c && lddy % 4 == 0 && lddx % 4 == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dx % 16) == 0,
                   "pixel strides must be multiples of 4 floats that cover the channels, pointers 16-byte aligned");
-    hipLaunchKernelGGL(bilinear_nhwc_bwd_kernel, dim3(ew_grid((long)n_img * h * w * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, dx, lddx,
+    hipLaunchKernelGGL(bilinear_nhwc_bwd_kernel, dim3(ew_grid((long)n_img * h * w * (c / 4), 4096)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, dx, lddx,
                        n_img, h, w, ho, wo, c, (float)h / (float)ho, (float)w / (float)wo);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_mul_pixel(const float* x, int ldx, const float* s, float* y, int ldy, long pixels, int c, void* stream) {
     RUNET_REQUIRE(x && s && y && pixels > 0 && c > 0 && c % 4 == 0 && ldx >= c && ldy >= c, "bad arguments (c must be a multiple of 4)");
-    hipLaunchKernelGGL(mul_pixel_kernel, dim3(ew_grid(pixels * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, x, ldx, s, y, ldy, pixels, c);
+    hipLaunchKernelGGL(mul_pixel_kernel, dim3(ew_grid(pixels * (c / 4), 4096)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, s, y, ldy, pixels, c);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -905,7 +886,7 @@ __global__ __launch_bounds__(TPB) void ce_bwd_kernel(const float* __restrict__ z
 extern "C" int runet_nhwc_to_nchw(const float* x, int ld, float* y, int n_img, int c, long hw, void* stream) {
     RUNET_REQUIRE(x && y && n_img > 0 && c > 0 && hw > 0 && ld >= c, "bad arguments");
     const long total = (long)n_img * c * hw;
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ew_grid(total)), dim3(TPB), 0, (hipStream_t)stream, x, ld, y, c, hw, total);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, x, ld, y, c, hw, total);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -927,6 +908,6 @@ extern "C" int runet_ce_bwd(const float* logits_nchw, const long long* target, c
     RUNET_REQUIRE(logits_nchw && target && gout && dlogits_nchw && n_img > 0 && hw > 0, "bad arguments");
     RUNET_REQUIRE(classes >= 2 && classes <= CE_MAXC, "2..8 classes");
     const long P = (long)n_img * hw;
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3(ew_grid(P)), dim3(TPB), 0, (hipStream_t)stream, logits_nchw, target, gout, dlogits_nchw, classes, hw, P);
+    hipLaunchKernelGGL(ce_bwd_kernel, dim3(ew_grid(P, 4096)), dim3(TPB), 0, (hipStream_t)stream, logits_nchw, target, gout, dlogits_nchw, classes, hw, P);
     RUNET_CHECK_LAUNCH();
 }

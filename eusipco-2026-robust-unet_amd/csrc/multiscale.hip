@@ -124,13 +124,6 @@ __global__ __launch_bounds__(TPB) void mp3s1_bwd_kernel(const float* __restrict_
     }
 }
 
-inline int ew_grid(long total) {
-    long b = (total + TPB - 1) / TPB;
-    if (b > 16384) b = 16384;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-inline bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
 // =============================================================================================================== multi-scale stem
 constexpr int TH = 8, TW = 32;             // pixel tile of a block: thread t owns pixel (t / 32, t % 32)
@@ -426,22 +419,6 @@ __global__ __launch_bounds__(TPB) void ms_bwd_apply_kernel(const Src src, const 
     apply_branch<3>(s, tl, pool, de, ldde, dt, lddt);
 }
 
-// out[j] = sum_k part[k][j]: 16 outputs x 16 part-lanes per block, each lane strides over the partial rows, then the lanes in order
-__global__ __launch_bounds__(TPB) void ms_sum_parts_kernel(const float* __restrict__ part, const int nparts, const int width, float* __restrict__ out) {
-    __shared__ double red[TPB];
-    const int ol = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    const int j = blockIdx.x * 16 + ol;
-    double a = 0;
-    if (j < width)
-        for (int q = pl; q < nparts; q += 16) a += part[(long)q * width + j];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    if (pl == 0 && j < width) {
-        for (int l = 1; l < 16; ++l) a += red[l * 16 + ol];
-        out[j] = (float)a;
-    }
-}
-
 inline long n_tiles(int n, int h, int w) { return (long)n * cdiv(h, TH) * cdiv(w, TW); }
 inline bool shape_ok(int n, int h, int w) {
     return n > 0 && h > 0 && w > 0 && (long)h * w <= 0x7fffffffL && n_tiles(n, h, w) <= 0x7fffffffL / (NB * CB * 3);
@@ -456,10 +433,10 @@ extern "C" int runet_maxpool3s1_fwd(const float* x, int ldx, float* y, int ldy, 
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && c > 0 && (long)h * w <= 0x7fffffffL, "empty shape");
     RUNET_REQUIRE(ldx >= c && ldy >= c, "a pixel stride below the channel count");
     const long P = (long)n_img * h * w;
-    if (c % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y))
-        hipLaunchKernelGGL(mp3s1_fwd_kernel<4>, dim3(ew_grid(P * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, P, h, w, c);
+    if (c % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && RUNET_ALIGNED16(x) && RUNET_ALIGNED16(y))
+        hipLaunchKernelGGL(mp3s1_fwd_kernel<4>, dim3(ew_grid(P * (c / 4), 16384)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, P, h, w, c);
     else
-        hipLaunchKernelGGL(mp3s1_fwd_kernel<1>, dim3(ew_grid(P * c)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, P, h, w, c);
+        hipLaunchKernelGGL(mp3s1_fwd_kernel<1>, dim3(ew_grid(P * c, 16384)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, P, h, w, c);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -469,11 +446,11 @@ extern "C" int runet_maxpool3s1_bwd(const float* dy, int lddy, const unsigned ch
     RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && c > 0 && (long)h * w <= 0x7fffffffL, "empty shape");
     RUNET_REQUIRE(lddy >= c && lddx >= c, "a pixel stride below the channel count");
     const long P = (long)n_img * h * w;
-    if (c % 4 == 0 && lddy % 4 == 0 && al16(dy) && ((uintptr_t)idx % 4) == 0)
-        hipLaunchKernelGGL(mp3s1_bwd_kernel<4>, dim3(ew_grid(P * (c / 4))), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, P, h, w, c,
+    if (c % 4 == 0 && lddy % 4 == 0 && RUNET_ALIGNED16(dy) && ((uintptr_t)idx % 4) == 0)
+        hipLaunchKernelGGL(mp3s1_bwd_kernel<4>, dim3(ew_grid(P * (c / 4), 16384)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, P, h, w, c,
                            accumulate);
     else
-        hipLaunchKernelGGL(mp3s1_bwd_kernel<1>, dim3(ew_grid(P * c)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, P, h, w, c, accumulate);
+        hipLaunchKernelGGL(mp3s1_bwd_kernel<1>, dim3(ew_grid(P * c, 16384)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, P, h, w, c, accumulate);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -504,7 +481,7 @@ extern "C" int runet_ms_stem_fwd(const float* x, long sn, long sc, long sh, long
                                  const float* scale, const float* shift, float* e, int lde, void* stream) {
     RUNET_REQUIRE(x && MS_WTS_OK && scale && shift && e, "null pointer");
     RUNET_REQUIRE(shape_ok(n_img, h, w_), "empty shape");
-    RUNET_REQUIRE(lde >= CT && lde % 4 == 0 && al16(e), "the output's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
+    RUNET_REQUIRE(lde >= CT && lde % 4 == 0 && RUNET_ALIGNED16(e), "the output's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
     hipLaunchKernelGGL(ms_fwd_kernel, dim3((unsigned)n_tiles(n_img, h, w_)), dim3(TPB), 0, (hipStream_t)stream, make_src(x, sn, sc, sh, sw, h, w_),
                        Wts{w1, w3, w5, w4, b1, b3, b5, b4}, scale, shift, e, lde);
     RUNET_CHECK_LAUNCH();
@@ -516,13 +493,13 @@ extern "C" int runet_ms_stem_bwd_reduce(const float* x, long sn, long sc, long s
                                         float* workspace, long workspace_floats, float* sums, void* stream) {
     RUNET_REQUIRE(x && MS_WTS_OK && scale && shift && de && mean && invstd && workspace && sums, "null pointer");
     RUNET_REQUIRE(shape_ok(n_img, h, w_), "empty shape");
-    RUNET_REQUIRE(ldde >= CT && ldde % 4 == 0 && al16(de), "the gradient's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
+    RUNET_REQUIRE(ldde >= CT && ldde % 4 == 0 && RUNET_ALIGNED16(de), "the gradient's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
     const long nb = n_tiles(n_img, h, w_);
     RUNET_REQUIRE(workspace_floats >= nb * 2 * CT, "workspace too small (runet_ms_stem_workspace_floats)");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ms_bwd_reduce_kernel, dim3((unsigned)nb), dim3(TPB), 0, st, make_src(x, sn, sc, sh, sw, h, w_),
                        Wts{w1, w3, w5, w4, b1, b3, b5, b4}, scale, shift, de, ldde, mean, invstd, workspace);
-    hipLaunchKernelGGL(ms_sum_parts_kernel, dim3(cdiv(2 * CT, 16)), dim3(TPB), 0, st, workspace, (int)nb, 2 * CT, sums);
+    sum_parts<16>(workspace, (int)nb, 2 * CT, sums, st);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -532,8 +509,8 @@ extern "C" int runet_ms_stem_bwd_apply(const float* x, long sn, long sc, long sh
                                        const float* sums, long m_total, float* dt, int lddt, void* stream) {
     RUNET_REQUIRE(x && MS_WTS_OK && scale && shift && de && mean && invstd && sums && dt, "null pointer");
     RUNET_REQUIRE(shape_ok(n_img, h, w_), "empty shape");
-    RUNET_REQUIRE(ldde >= CT && ldde % 4 == 0 && al16(de), "the gradient's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
-    RUNET_REQUIRE(lddt >= CT && lddt % 4 == 0 && al16(dt), "the output's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
+    RUNET_REQUIRE(ldde >= CT && ldde % 4 == 0 && RUNET_ALIGNED16(de), "the gradient's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
+    RUNET_REQUIRE(lddt >= CT && lddt % 4 == 0 && RUNET_ALIGNED16(dt), "the output's pixel stride must be a multiple of 4 floats, at least 64, its pointer 16-byte aligned");
     const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : (long)n_img * h * w_);
     hipLaunchKernelGGL(ms_bwd_apply_kernel, dim3((unsigned)n_tiles(n_img, h, w_)), dim3(TPB), 0, (hipStream_t)stream, make_src(x, sn, sc, sh, sw, h, w_),
                        Wts{w1, w3, w5, w4, b1, b3, b5, b4}, scale, shift, de, ldde, mean, invstd, sums, inv_m, dt, lddt);

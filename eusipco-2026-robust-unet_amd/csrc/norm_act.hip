@@ -614,12 +614,6 @@ inline int stream_chunks(int N, int HW, int C, int rows, int& ppc) {
     ppc = (int)((HW + per_img - 1) / per_img);
     return (int)((HW + ppc - 1) / ppc);
 }
-inline int ew_grid(long total_vec) {
-    long b = (total_vec + TPB - 1) / TPB;
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 }  // namespace
 

@@ -37,6 +37,23 @@ extern "C" void runet_set_error(const char* msg);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Threads per block of the helpers below that fix a block shape (ew_grid, sum_parts, block_rows_to_part); every kernel file's own TPB.
+constexpr int RUNET_TPB = 256;
+// blocks of a grid-stride element-wise kernel over `total` work items, at most `cap`
+static inline int ew_grid(long total, int cap) {
+    long b = (total + RUNET_TPB - 1) / RUNET_TPB;
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+// NHWC view checks of the entry points: a pixel stride that covers c channels in whole 16-byte groups, and a 16-byte aligned base.  The
+// condition is spelled out in RUNET_REQ_LD because RUNET_REQUIRE echoes its text in the error message.
+#define RUNET_ALIGNED16(p) (((uintptr_t)(p) % 16) == 0)
+#define RUNET_REQ_LD(ld, c, p)                                                        \
+    RUNET_REQUIRE((ld) >= (c) && (ld) % 4 == 0 && ((uintptr_t)(p) % 16) == 0,         \
+                  "pixel strides must be multiples of 4 floats that cover the channels, tensors 16-byte aligned")
+
 // gemm.hip (internal launchers behind runet_gemm_batched / runet_gemm_tn_batched)
 int runet_gemm_nn_launch(const float* a, int lda, long sa, const float* b, long sb, float* c, int ldc, long sc, int batch, int rows, int k, int n,
                          hipStream_t st);
@@ -62,6 +79,49 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// 16-byte access to four consecutive floats (p 16-byte aligned)
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, const f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+
+// ---- the two ordered passes of a two-stage reduction (no float atomics: these few lines fix the summation order, so the bits) ----
+// In-block row pass: sm holds [rows][width] floats, one row of sums per thread row of the block.  After the barrier thread u adds column u
+// over the rows in row order, in double, and writes part[block][u].
+__device__ __forceinline__ void block_rows_to_part(const float* sm, int rows, int width, float* __restrict__ part) {
+    __syncthreads();
+    for (int u = threadIdx.x; u < width; u += RUNET_TPB) {
+        double s = 0;
+        for (int r = 0; r < rows; ++r) s += sm[r * width + u];
+        part[(long)blockIdx.x * width + u] = (float)s;
+    }
+}
+// Final pass, out[u] = sum_k part[k][u]: a block takes CW consecutive outputs x RUNET_TPB / CW part-lanes.  Lane pl adds the partial rows
+// pl, pl + lanes, ... in that order, then the lane sums are added in lane order through LDS; double throughout, one cast to float.  The lane
+// count is part of the order: a caller that changes its CW changes its bits.  Unnamed namespace: every translation unit keeps its own copy.
+namespace {
+template <int CW>
+__global__ __launch_bounds__(RUNET_TPB) void sum_parts_kernel(const float* __restrict__ part, int nparts, int width, float* __restrict__ out) {
+    constexpr int PL = RUNET_TPB / CW;
+    __shared__ double red[RUNET_TPB];
+    const int cl = threadIdx.x % CW, pl = threadIdx.x / CW;
+    const int u = blockIdx.x * CW + cl;
+    double s = 0;
+    if (u < width) {
+#pragma unroll 8                             // eight loads in flight per lane; the adds stay serial, in k order
+        for (int k = pl; k < nparts; k += PL) s += part[(long)k * width + u];
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (pl == 0 && u < width) {
+        for (int j = 1; j < PL; ++j) s += red[j * CW + cl];
+        out[u] = (float)s;
+    }
+}
+template <int CW>
+inline void sum_parts(const float* part, int nparts, int width, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(sum_parts_kernel<CW>, dim3(cdiv(width, CW)), dim3(RUNET_TPB), 0, st, part, nparts, width, out);
+}
+}  // namespace
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // BatchNorm pieces that several kernels must evaluate BIT-IDENTICALLY (bn_apply_kernel, the backward kernels that recompute the ReLU mask from
@@ -123,8 +183,22 @@ __device__ __forceinline__ void bilin_src(int o, float scale, int in, int& i0, i
     l1 = src - (float)i0;
     l0 = 1.f - l1;
 }
+// the weight with which output o reads input index i (0 when neither tap is i): the tap weight of the gather adjoints
+__device__ __forceinline__ float bilin_tap_weight(int o, float scale, int in, int i) {
+    int i0, i1;
+    float l0, l1;
+    bilin_src(o, scale, in, i0, i1, l0, l1);
+    return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
+}
 // adjoint (gather) range: the outputs whose two source taps can include input index i lie in [lo, hi] (index 0 also takes the clamped ones)
 __device__ __forceinline__ void bilin_adj_range(int i, float scale, int out, int& lo, int& hi) {
     lo = i == 0 ? 0 : max(0, (int)floorf(((float)i - 0.5f) / scale - 0.5f) - 1);
     hi = min(out - 1, (int)ceilf(((float)i + 1.5f) / scale - 0.5f) + 1);
+}
+// the same for an integer factor S (scale = 1 / S, out = S * in), in integers: src = (o + 0.5) / S - 0.5 in [i - 1, i + 1)  <=>
+// S i - S / 2 <= o <= S i + 3 S / 2 - 1 for an even S; an odd S takes the wider S i - S .. S i + 2 S.  Outputs of the range that do not read i
+// have tap weight 0, so a wider range gives the same sum.
+__device__ __forceinline__ void upsample_adj_range(int i, int S, int out, int& lo, int& hi) {
+    lo = max(0, S * i - ((S & 1) ? S : S / 2));
+    hi = min(out - 1, S * i + ((S & 1) ? 2 * S : 3 * S / 2 - 1));
 }

@@ -12,7 +12,7 @@
 // Weights in their physical (HWIO) layouts: w1 [3][16], w2 [16][4]; the gradients come back in the same layouts.
 // A block owns PPB consecutive pixels (pixel index = (n * h + y) * w + x), a thread every TPB-th of them: neighbouring lanes read neighbouring
 // addresses of each colour plane.  Sums: per-thread serial, in-wave butterfly, the block's four waves in order through LDS, the blocks'
-// partial rows in index order (wi_sum_parts_kernel).  No float atomics; the block count depends on the shape only: bitwise reproducible.
+// partial rows in index order (sum_parts<16> of runet_common.h).  No float atomics; the block count depends on the shape only: bitwise reproducible.
 #include "runet_common.h"
 #include "../../include/runet_hip.h"
 
@@ -258,22 +258,6 @@ __global__ __launch_bounds__(TPB) void wi_bwd_apply_kernel(const Src src, const 
     block_sum_store<W_APP>(acc, red, part + (long)blockIdx.x * W_APP);
 }
 
-// out[j] = sum_k part[k][j]: 16 outputs x 16 part-lanes per block, each lane strides over the partial rows, then the lanes in order
-__global__ __launch_bounds__(TPB) void wi_sum_parts_kernel(const float* __restrict__ part, const int nparts, const int width, float* __restrict__ out) {
-    __shared__ double red[TPB];
-    const int ol = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    const int j = blockIdx.x * 16 + ol;
-    double a = 0;
-    if (j < width)
-        for (int q = pl; q < nparts; q += 16) a += part[(long)q * width + j];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    if (pl == 0 && j < width) {
-        for (int l = 1; l < 16; ++l) a += red[l * 16 + ol];
-        out[j] = (float)a;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------ unfused partner
 // The element-wise steps of the reference's order that no shared kernel offers (RUNET_NO_FUSED_WATER_INDEX=1): a sigmoid and its backward
 // over c channels of NHWC views, and a channel-slice copy.  Views may start at any channel (4-byte accesses).
@@ -302,18 +286,9 @@ __global__ __launch_bounds__(TPB) void copy_nhwc_kernel(const float* __restrict_
         y[p * ldy + c] = x[p * ldx + c];
     }
 }
-inline int ew_grid(long total) {
-    long b = (total + TPB - 1) / TPB;
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 inline long n_blocks(long P) { return (P + PPB - 1) / PPB; }
 inline bool shape_ok(int n, int h, int w) { return n > 0 && h > 0 && w > 0 && (long)h * w <= 0x7fffffffL && n_blocks((long)n * h * w) <= 0x7fffffffL / W_RED; }
 }  // namespace
-
-#define ALIGNED16(p) (((uintptr_t)(p) % 16) == 0)
 
 extern "C" int runet_water_index_parts(int n_img, int h, int w_) {
     if (!shape_ok(n_img, h, w_)) return -1;
@@ -340,7 +315,7 @@ extern "C" int runet_water_index_fwd(const float* x, long sn, long sc, long sh, 
                                      const float* scale, const float* shift, const float* w2, const float* b2, float* out, int ldo, void* stream) {
     RUNET_REQUIRE(x && w1 && b1 && scale && shift && w2 && b2 && out, "null pointer");
     RUNET_REQUIRE(shape_ok(n_img, h, w_), "empty shape");
-    RUNET_REQUIRE(ldo >= 8 && ldo % 4 == 0 && ALIGNED16(out), "the output's pixel stride must be a multiple of 4 floats, at least 8, its pointer 16-byte aligned");
+    RUNET_REQUIRE(ldo >= 8 && ldo % 4 == 0 && RUNET_ALIGNED16(out), "the output's pixel stride must be a multiple of 4 floats, at least 8, its pointer 16-byte aligned");
     const long P = (long)n_img * h * w_;
     long blocks = (P + TPB - 1) / TPB;
     if (blocks > 8192) blocks = 8192;
@@ -361,7 +336,7 @@ extern "C" int runet_water_index_bwd_reduce(const float* x, long sn, long sc, lo
     hipStream_t st = (hipStream_t)stream;
     const Src src{x, sn, sc, sh, sw, h * w_, w_};
     hipLaunchKernelGGL(wi_bwd_reduce_kernel, dim3((unsigned)nb), dim3(TPB), 0, st, src, P, g, ldg, w1, b1, scale, shift, w2, b2, mean, invstd, workspace);
-    hipLaunchKernelGGL(wi_sum_parts_kernel, dim3(cdiv(W_RED, 16)), dim3(TPB), 0, st, workspace, (int)nb, W_RED, out);
+    sum_parts<16>(workspace, (int)nb, W_RED, out, st);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -379,27 +354,27 @@ extern "C" int runet_water_index_bwd_apply(const float* x, long sn, long sc, lon
     const Src src{x, sn, sc, sh, sw, h * w_, w_};
     hipLaunchKernelGGL(wi_bwd_apply_kernel, dim3((unsigned)nb), dim3(TPB), 0, st, src, P, g, ldg, w1, b1, scale, shift, w2, b2, mean, invstd, sums, inv_m,
                        workspace);
-    hipLaunchKernelGGL(wi_sum_parts_kernel, dim3(cdiv(W_APP, 16)), dim3(TPB), 0, st, workspace, (int)nb, W_APP, out);
+    sum_parts<16>(workspace, (int)nb, W_APP, out, st);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_sigmoid_nhwc_fwd(const float* u, int ldu, float* y, int ldy, long pixels, int c, void* stream) {
     RUNET_REQUIRE(u && y, "null pointer");
     RUNET_REQUIRE(pixels > 0 && c > 0 && ldu >= c && ldy >= c, "empty shape, or a pixel stride below the channel count");
-    hipLaunchKernelGGL(sigmoid_nhwc_fwd_kernel, dim3(ew_grid(pixels * c)), dim3(TPB), 0, (hipStream_t)stream, u, ldu, y, ldy, pixels, c);
+    hipLaunchKernelGGL(sigmoid_nhwc_fwd_kernel, dim3(ew_grid(pixels * c, 4096)), dim3(TPB), 0, (hipStream_t)stream, u, ldu, y, ldy, pixels, c);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_sigmoid_nhwc_bwd(const float* dy, int lddy, const float* y, int ldy, float* du, int lddu, long pixels, int c, void* stream) {
     RUNET_REQUIRE(dy && y && du, "null pointer");
     RUNET_REQUIRE(pixels > 0 && c > 0 && lddy >= c && ldy >= c && lddu >= c, "empty shape, or a pixel stride below the channel count");
-    hipLaunchKernelGGL(sigmoid_nhwc_bwd_kernel, dim3(ew_grid(pixels * c)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, y, ldy, du, lddu, pixels, c);
+    hipLaunchKernelGGL(sigmoid_nhwc_bwd_kernel, dim3(ew_grid(pixels * c, 4096)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, y, ldy, du, lddu, pixels, c);
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" int runet_copy_nhwc(const float* x, int ldx, float* y, int ldy, long pixels, int c, void* stream) {
     RUNET_REQUIRE(x && y, "null pointer");
     RUNET_REQUIRE(pixels > 0 && c > 0 && ldx >= c && ldy >= c, "empty shape, or a pixel stride below the channel count");
-    hipLaunchKernelGGL(copy_nhwc_kernel, dim3(ew_grid(pixels * c)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, pixels, c);
+    hipLaunchKernelGGL(copy_nhwc_kernel, dim3(ew_grid(pixels * c, 4096)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, pixels, c);
     RUNET_CHECK_LAUNCH();
 }
