@@ -8,6 +8,19 @@
 //
 // Algorithmic HBM bytes per element: chan_stats 4 (read), bn_apply 8 (read+write), bn_bwd_reduce 8-12,
 // bn_bwd_apply 12-16.
+//
+// Layout of the file: one body per pass, one launcher per family, one entry point per instance.
+//   device helpers   chan_combine, minmax_merge<TIE_LOW>, put_part, bn_running_update / bn_coeffs / bn_batch_coeffs (each the one copy of
+//                    its rule; load_vec / store_vec, bn_pre, bn_bwd_coef, bn_bwd_dx, pooled_grad4 come from runet_common.h).  The gradient
+//                    through the activation is spelled out in both backward kernels (take, and bn_bwd_apply_kernel's loop): every shared
+//                    function form of it changed those kernels' code and measured slower, so keep the two chains word for word alike.
+//   kernels          chan_stats_partial -> chan_stats_combine -> bn_finalize_kernel, or -> chan_stats_finalize_kernel (one launch);
+//                    bn_apply_body<VEC, ACT>; bn_bwd_reduce_partial<VEC, POOL, ACT> -> bn_bwd_reduce_final; bn_bwd_apply_kernel<VEC, POOL, ACT>;
+//                    chan_sum_partial -> chan_sum_final
+//   launchers        reduce_geom / stream_geom, launch_stats_partial, launch_bn_apply<ACT>, (each picks its VEC instance once)
+//                    launch_bn_bwd_reduce<POOL, ACT>, launch_bn_bwd_apply<POOL, ACT>
+//   extern "C"       every entry point checks its own arguments (RUNET_REQUIRE prints the function name and the condition), then calls a
+//                    launcher.  A new activation is one ACT value, its branch in bn_apply_body and in the two gradient chains, and three short entry points.
 #include "runet_common.h"
 #include "../../include/runet_hip.h"
 #include <float.h>
@@ -17,8 +30,6 @@ namespace {
 constexpr int TPB = 256;
 constexpr int STATS_GROUPS = 16;      // chan_stats_partial: threads per channel in the row combine when there are few channels
 
-struct Welf { float n, mean, m2; };
-
 __device__ __forceinline__ void chan_combine(double& n, double& mean, double& m2, double nb, double mb, double m2b) {
     if (nb == 0.0) return;
     const double nt = n + nb;
@@ -26,6 +37,22 @@ __device__ __forceinline__ void chan_combine(double& n, double& mean, double& m2
     mean += d * (nb / nt);
     m2 += m2b + d * d * (n * nb / nt);
     n = nt;
+}
+// Merge a (max, min, their first pixel indices) candidate into the running one.  Two tie rules, a compile-time choice per site: candidates that
+// arrive in pixel order (a thread's own pixels; chunks, then chunk-lanes, in chan_stats_combine) keep the first occurrence by strict
+// comparisons; the thread rows of a block interleave their pixels, so there (TIE_LOW) an equal value with a smaller index wins.
+template <bool TIE_LOW>
+__device__ __forceinline__ void minmax_merge(float& bmx, float& bmn, int& bimx, int& bimn, const float mx, const float mn, const int imx,
+                                             const int imn) {
+    if (mx > bmx || (TIE_LOW && mx == bmx && imx < bimx)) { bmx = mx; bimx = imx; }
+    if (mn < bmn || (TIE_LOW && mn == bmn && imn < bimn)) { bmn = mn; bimn = imn; }
+}
+// one partial record: (n, mean, M2) and, with MINMAX, (max, min, first indices as float bits)
+template <bool MINMAX>
+__device__ __forceinline__ void put_part(float* o, const float n, const float mean, const float m2, const float mx, const float mn, const int imx,
+                                         const int imn) {
+    o[0] = n; o[1] = mean; o[2] = m2;
+    if constexpr (MINMAX) { o[3] = mx; o[4] = mn; o[5] = __int_as_float(imx); o[6] = __int_as_float(imn); }
 }
 
 // grid (chunks, N); thread owns VEC consecutive channels and every `rows`-th pixel of its chunk.
@@ -49,14 +76,7 @@ __global__ __launch_bounds__(TPB) void chan_stats_partial(const float* __restric
     for (int v = 0; v < VEC; ++v) { K[v] = 0.f; s1[v] = 0.f; s2[v] = 0.f; mx[v] = -FLT_MAX; mn[v] = FLT_MAX; imx[v] = 0; imn[v] = 0; }
     if (active) {
         const float* base = x + ((long)n * HW) * ld + col * VEC;
-        auto fetch = [&](int p, float (&v)[VEC]) {
-            if constexpr (VEC == 4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(base + (long)p * ld);
-                v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-            } else {
-                v[0] = base[(long)p * ld];
-            }
-        };
+        auto fetch = [&](int p, float (&v)[VEC]) { load_vec<VEC>(base + (long)p * ld, v); };
         auto take = [&](int p, const float (&v)[VEC]) {
             if (cnt == 0) {
 #pragma unroll
@@ -67,10 +87,7 @@ __global__ __launch_bounds__(TPB) void chan_stats_partial(const float* __restric
                 const float d = v[q] - K[q];
                 s1[q] += d;
                 s2[q] += d * d;
-                if constexpr (MINMAX) {
-                    if (v[q] > mx[q]) { mx[q] = v[q]; imx[q] = p; }
-                    if (v[q] < mn[q]) { mn[q] = v[q]; imn[q] = p; }
-                }
+                if constexpr (MINMAX) minmax_merge<false>(mx[q], mn[q], imx[q], imn[q], v[q], v[q], p, p);
             }
             ++cnt;
         };
@@ -106,25 +123,21 @@ __global__ __launch_bounds__(TPB) void chan_stats_partial(const float* __restric
         }
     }
     __syncthreads();
-    // rows r0, r0 + rstep, ... of channel c -> (n, mean, M2[, max, min, first indices])
+    // rows r0 .. r1 - 1 of channel c -> (n, mean, M2[, max, min, first indices])
     auto combine_rows = [&](int c, int r0, int r1, double& n_, double& mean, double& m2, float& bmx, float& bmn, int& bimx, int& bimn) {
         for (int r = r0; r < r1; ++r) {
             const float* d = w3 + (r * C + c) * 3;
             chan_combine(n_, mean, m2, d[0], d[1], d[2]);
             if constexpr (MINMAX) {
                 const float* e = wm + (r * C + c) * 4;
-                if (d[0] > 0.f) {
-                    const int i1 = __float_as_int(e[2]), i2 = __float_as_int(e[3]);
-                    if (e[0] > bmx || (e[0] == bmx && i1 < bimx)) { bmx = e[0]; bimx = i1; }
-                    if (e[1] < bmn || (e[1] == bmn && i2 < bimn)) { bmn = e[1]; bimn = i2; }
-                }
+                if (d[0] > 0.f) minmax_merge<true>(bmx, bmn, bimx, bimn, e[0], e[1], __float_as_int(e[2]), __float_as_int(e[3]));
             }
         }
     };
     if (C * STATS_GROUPS <= TPB && rows >= 2 * STATS_GROUPS) {
         // few channels (the attention gates' single-channel maps: rows = 256): one thread combining all the rows in double precision is
         // a 256-step serial chain per workgroup (12 us); STATS_GROUPS threads per channel take contiguous row ranges, then one combines them
-        float* g3 = sm + rows * C * (MINMAX ? 7 : 3);            // [group][C][7]
+        float* g3 = sm + rows * C * (MINMAX ? 7 : 3);            // [group][C][7], all seven written in both forms
         const int c = tid % C, grp = tid / C;
         if (grp < STATS_GROUPS) {
             const int per = (rows + STATS_GROUPS - 1) / STATS_GROUPS;
@@ -132,8 +145,7 @@ __global__ __launch_bounds__(TPB) void chan_stats_partial(const float* __restric
             float bmx = -FLT_MAX, bmn = FLT_MAX;
             int bimx = 0, bimn = 0;
             combine_rows(c, grp * per, min(rows, grp * per + per), n_, mean, m2, bmx, bmn, bimx, bimn);
-            float* o = g3 + (grp * C + c) * 7;
-            o[0] = (float)n_; o[1] = (float)mean; o[2] = (float)m2; o[3] = bmx; o[4] = bmn; o[5] = __int_as_float(bimx); o[6] = __int_as_float(bimn);
+            put_part<true>(g3 + (grp * C + c) * 7, (float)n_, (float)mean, (float)m2, bmx, bmn, bimx, bimn);
         }
         __syncthreads();
         if (tid < C) {
@@ -144,16 +156,10 @@ __global__ __launch_bounds__(TPB) void chan_stats_partial(const float* __restric
                 const float* d = g3 + (q * C + tid) * 7;
                 chan_combine(n_, mean, m2, d[0], d[1], d[2]);
                 if constexpr (MINMAX) {
-                    if (d[0] > 0.f) {
-                        const int i1 = __float_as_int(d[5]), i2 = __float_as_int(d[6]);
-                        if (d[3] > bmx || (d[3] == bmx && i1 < bimx)) { bmx = d[3]; bimx = i1; }
-                        if (d[4] < bmn || (d[4] == bmn && i2 < bimn)) { bmn = d[4]; bimn = i2; }
-                    }
+                    if (d[0] > 0.f) minmax_merge<true>(bmx, bmn, bimx, bimn, d[3], d[4], __float_as_int(d[5]), __float_as_int(d[6]));
                 }
             }
-            float* o = part + (((long)n * nchunks + chunk) * C + tid) * (MINMAX ? 7 : 3);
-            o[0] = (float)n_; o[1] = (float)mean; o[2] = (float)m2;
-            if constexpr (MINMAX) { o[3] = bmx; o[4] = bmn; o[5] = __int_as_float(bimx); o[6] = __int_as_float(bimn); }
+            put_part<MINMAX>(part + (((long)n * nchunks + chunk) * C + tid) * (MINMAX ? 7 : 3), (float)n_, (float)mean, (float)m2, bmx, bmn, bimx, bimn);
         }
         return;
     }
@@ -162,9 +168,7 @@ __global__ __launch_bounds__(TPB) void chan_stats_partial(const float* __restric
         float bmx = -FLT_MAX, bmn = FLT_MAX;
         int bimx = 0, bimn = 0;
         combine_rows(c, 0, rows, n_, mean, m2, bmx, bmn, bimx, bimn);
-        float* o = part + (((long)n * nchunks + chunk) * C + c) * (MINMAX ? 7 : 3);
-        o[0] = (float)n_; o[1] = (float)mean; o[2] = (float)m2;
-        if constexpr (MINMAX) { o[3] = bmx; o[4] = bmn; o[5] = __int_as_float(bimx); o[6] = __int_as_float(bimn); }
+        put_part<MINMAX>(part + (((long)n * nchunks + chunk) * C + c) * (MINMAX ? 7 : 3), (float)n_, (float)mean, (float)m2, bmx, bmn, bimx, bimn);
     }
 }
 
@@ -193,10 +197,7 @@ __global__ __launch_bounds__(TPB) void chan_stats_combine(const float* __restric
             const float* o = part + (((long)n * nchunks + k) * C + c) * S;
             chan_combine(n_, mean, m2, o[0], o[1], o[2]);
             if constexpr (MINMAX) {
-                if (o[0] > 0.f) {
-                    if (o[3] > bmx) { bmx = o[3]; bimx = __float_as_int(o[5]); }
-                    if (o[4] < bmn) { bmn = o[4]; bimn = __float_as_int(o[6]); }
-                }
+                if (o[0] > 0.f) minmax_merge<false>(bmx, bmn, bimx, bimn, o[3], o[4], __float_as_int(o[5]), __float_as_int(o[6]));
             }
         }
     }
@@ -208,10 +209,7 @@ __global__ __launch_bounds__(TPB) void chan_stats_combine(const float* __restric
             const int t = j * CW + cl;
             chan_combine(n_, mean, m2, sd[0][t], sd[1][t], sd[2][t]);
             if constexpr (MINMAX) {
-                if (sd[0][t] > 0.0) {
-                    if (sf[0][t] > bmx) { bmx = sf[0][t]; bimx = si[0][t]; }
-                    if (sf[1][t] < bmn) { bmn = sf[1][t]; bimn = si[1][t]; }
-                }
+                if (sd[0][t] > 0.0) minmax_merge<false>(bmx, bmn, bimx, bimn, sf[0][t], sf[1][t], si[0][t], si[1][t]);
             }
         }
         const int i = n * C + c;
@@ -219,6 +217,33 @@ __global__ __launch_bounds__(TPB) void chan_stats_combine(const float* __restric
         m2_nc[i] = (float)m2;
         if constexpr (MINMAX) { max_nc[i] = bmx; min_nc[i] = bmn; imax_nc[i] = bimx; imin_nc[i] = bimn; }
     }
+}
+
+// (mean, var) of a channel -> the BatchNorm coefficients y = x * scale + shift and the statistics the backward reads; double up to the stores
+__device__ __forceinline__ void bn_coeffs(const int c, const double mean, const double var, const float* gamma, const float* beta, const float eps,
+                                          float* scale, float* shift, float* save_mean, float* save_invstd) {
+    const double invstd = 1.0 / sqrt(var + (double)eps);
+    const double g = gamma ? gamma[c] : 1.0, b = beta ? beta[c] : 0.0;
+    scale[c] = (float)(g * invstd);
+    shift[c] = (float)(b - mean * g * invstd);
+    if (save_mean) { save_mean[c] = (float)mean; save_invstd[c] = (float)invstd; }
+}
+// training mode: (mean, M2, n) of a channel's batch -> running statistics update with the unbiased variance; returns the biased one
+__device__ __forceinline__ double bn_running_update(const int c, const double mean, const double m2, const double n, float* run_mean, float* run_var,
+                                                    const float momentum) {
+    const double var = m2 / n;
+    if (run_mean) {
+        run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mean);
+        run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * (m2 / (n - 1.0)));
+    }
+    return var;
+}
+// the two together: what training-mode BatchNorm derives from a channel's batch
+__device__ __forceinline__ void bn_batch_coeffs(const int c, const double mean, const double m2, const double n, float* run_mean, float* run_var,
+                                                const float momentum, const float* gamma, const float* beta, const float eps, float* scale,
+                                                float* shift, float* save_mean, float* save_invstd) {
+    const double var = bn_running_update(c, mean, m2, n, run_mean, run_var, momentum);
+    bn_coeffs(c, mean, var, gamma, beta, eps, scale, shift, save_mean, save_invstd);
 }
 
 __global__ void bn_finalize_kernel(const float* __restrict__ mean_nc, const float* __restrict__ m2_nc, int N, int C, long HW,
@@ -234,20 +259,12 @@ __global__ void bn_finalize_kernel(const float* __restrict__ mean_nc, const floa
         double n_ = 0, m = 0, m2 = 0;
         for (int n = 0; n < N; ++n) chan_combine(n_, m, m2, (double)HW, mean_nc[n * C + c], m2_nc[n * C + c]);
         mean = m;
-        var = m2 / n_;
-        if (run_mean) {
-            run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mean);
-            run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * (m2 / (n_ - 1.0)));
-        }
+        var = bn_running_update(c, m, m2, n_, run_mean, run_var, momentum);
     } else {
         mean = run_mean[c];
         var = run_var[c];
     }
-    const double invstd = 1.0 / sqrt(var + (double)eps);
-    const double g = gamma ? gamma[c] : 1.0, b = beta ? beta[c] : 0.0;
-    scale[c] = (float)(g * invstd);
-    shift[c] = (float)(b - mean * g * invstd);
-    if (save_mean) { save_mean[c] = (float)mean; save_invstd[c] = (float)invstd; }
+    bn_coeffs(c, mean, var, gamma, beta, eps, scale, shift, save_mean, save_invstd);
 }
 
 // Batch statistics straight from the per-chunk partials + the BatchNorm coefficients, in ONE launch (training mode, no per-image outputs
@@ -283,24 +300,13 @@ __global__ __launch_bounds__(TPB) void chan_stats_finalize_kernel(const float* _
         }
         __syncthreads();
     }
-    if (t == 0) {
-        const double var = m2 / n_;
-        if (run_mean) {
-            run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mean);
-            run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * (m2 / (n_ - 1.0)));
-        }
-        const double invstd = 1.0 / sqrt(var + (double)eps);
-        const double g = gamma ? gamma[c] : 1.0, b = beta ? beta[c] : 0.0;
-        scale[c] = (float)(g * invstd);
-        shift[c] = (float)(b - mean * g * invstd);
-        if (save_mean) { save_mean[c] = (float)mean; save_invstd[c] = (float)invstd; }
-    }
+    if (t == 0) bn_batch_coeffs(c, mean, m2, n_, run_mean, run_var, momentum, gamma, beta, eps, scale, shift, save_mean, save_invstd);
 }
 
 // Streaming kernels use a division-free layout: grid (chunks, images); a thread owns VEC consecutive channels (its per-channel
 // coefficients live in registers) and every `rows`-th pixel of its chunk, so the inner loop is loads, FMAs and one pointer add.
 // The activation behind a BatchNorm is a compile-time choice: ACT_RELU (the U-Net family: ReLU, optionally times a Dropout2d factor) or
-// ACT_LEAKY (YOLOSeg: LeakyReLU with a run-time slope).  The ACT_RELU forms are the kernels as they were (same code).  LeakyReLU is NOT ReLU
+// ACT_LEAKY (YOLOSeg: LeakyReLU with a run-time slope).  LeakyReLU is NOT ReLU
 // with slope 0 (that gives -0.0 for negative inputs): leaky_act is aten's expression z > 0 ? z : z * slope (the product in fp32, the slope
 // a float) and leaky_grad its backward g * (z > 0 ? 1 : slope), z always bn_pre's, so the backward's decision is the forward's.
 // ACT_GELU (SegFormer-Lite's patch embeddings): nn.GELU() (erf form, gelu_f / gelu_grad of runet_common.h), z recomputed the same way.
@@ -330,10 +336,7 @@ __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, int l
     const long ib = (long)n * HW;
     for (int p = p0 + row; p < p1; p += rows) {
         float v[VEC];
-        if constexpr (VEC == 4) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(x + (ib + p) * ldx + col * 4);
-            v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-        } else v[0] = x[(ib + p) * ldx + col];
+        load_vec<VEC>(x + (ib + p) * ldx + col * VEC, v);
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
             float r = bn_pre(v[q], sc[q], sh[q]);
@@ -346,10 +349,7 @@ __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, int l
                 v[q] = r * mk[q];
             }
         }
-        if constexpr (VEC == 4) {
-            f32x4 t = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(y + (ib + p) * ldy + col * 4) = t;
-        } else y[(ib + p) * ldy + col] = v[0];
+        store_vec<VEC>(y + (ib + p) * ldy + col * VEC, v);
     }
 }
 
@@ -411,21 +411,12 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
     if (row < rows) {
         const long ib = (long)n * HW;
         auto fetch = [&](int p, float (&g)[VEC], float (&xv)[VEC], float (&av)[VEC]) {
-            if constexpr (VEC == 4) {
-                f32x4 t;
-                if constexpr (POOL) t = pooled_grad4(dy, lddy, pidx, W, C, n, HW, p, col * 4);
-                else t = *reinterpret_cast<const f32x4*>(dy + (ib + p) * lddy + col * 4);
-                const f32x4 u = *reinterpret_cast<const f32x4*>(x + (ib + p) * ldx + col * 4);
+            if constexpr (POOL) {
+                const f32x4 t = pooled_grad4(dy, lddy, pidx, W, C, n, HW, p, col * 4);
                 g[0] = t[0]; g[1] = t[1]; g[2] = t[2]; g[3] = t[3];
-                xv[0] = u[0]; xv[1] = u[1]; xv[2] = u[2]; xv[3] = u[3];
-                if (act) {
-                    const f32x4 a = *reinterpret_cast<const f32x4*>(act + (ib + p) * ldact + col * 4);
-                    av[0] = a[0]; av[1] = a[1]; av[2] = a[2]; av[3] = a[3];
-                }
-            } else {
-                g[0] = dy[(ib + p) * lddy + col]; xv[0] = x[(ib + p) * ldx + col];
-                if (act) av[0] = act[(ib + p) * ldact + col];
-            }
+            } else load_vec<VEC>(dy + (ib + p) * lddy + col * VEC, g);
+            load_vec<VEC>(x + (ib + p) * ldx + col * VEC, xv);
+            if (act) load_vec<VEC>(act + (ib + p) * ldact + col * VEC, av);
         };
         auto take = [&](const float (&g)[VEC], const float (&xv)[VEC], const float (&av)[VEC]) {
 #pragma unroll
@@ -512,36 +503,23 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
     }
     const long ib = (long)n * HW;
     for (int p = p0 + row; p < p1; p += rows) {
-        float g[VEC], xv[VEC], av[VEC];
-        if constexpr (VEC == 4) {
-            f32x4 t;
-            if constexpr (POOL) t = pooled_grad4(dy, lddy, pidx, W, C, n, HW, p, col * 4);
-            else t = *reinterpret_cast<const f32x4*>(dy + (ib + p) * lddy + col * 4);
-            const f32x4 u = *reinterpret_cast<const f32x4*>(x + (ib + p) * ldx + col * 4);
+        float g[VEC], xv[VEC], av[VEC], r[VEC];
+        if constexpr (POOL) {
+            const f32x4 t = pooled_grad4(dy, lddy, pidx, W, C, n, HW, p, col * 4);
             g[0] = t[0]; g[1] = t[1]; g[2] = t[2]; g[3] = t[3];
-            xv[0] = u[0]; xv[1] = u[1]; xv[2] = u[2]; xv[3] = u[3];
-            if (act) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(act + (ib + p) * ldact + col * 4);
-                av[0] = a[0]; av[1] = a[1]; av[2] = a[2]; av[3] = a[3];
-            }
-        } else {
-            g[0] = dy[(ib + p) * lddy + col]; xv[0] = x[(ib + p) * ldx + col];
-            if (act) av[0] = act[(ib + p) * ldact + col];
-        }
-        float r[VEC];
+        } else load_vec<VEC>(dy + (ib + p) * lddy + col * VEC, g);
+        load_vec<VEC>(x + (ib + p) * ldx + col * VEC, xv);
+        if (act) load_vec<VEC>(act + (ib + p) * ldact + col * VEC, av);
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
-            float gg = g[q];
+            float gg = g[q];                    // the same chain as in bn_bwd_reduce_partial::take, with the forward scale in sc
             if constexpr (ACT == ACT_LEAKY) gg = leaky_grad(gg, bn_pre(xv[q], sc[q], fh[q]), mask);
             else if constexpr (ACT == ACT_GELU) gg = gelu_grad(gg, bn_pre(xv[q], sc[q], fh[q]));
             else if (act) gg = (av[q] > 0.f) ? gg * mk[q] : 0.f;
             else if (recompute) gg = (bn_pre(xv[q], sc[q], fh[q]) > 0.f) ? gg * mk[q] : 0.f;
             r[q] = bn_bwd_dx(gg, sc[q], xv[q], ca[q], cb[q]);
         }
-        if constexpr (VEC == 4) {
-            f32x4 t = {r[0], r[1], r[2], r[3]};
-            *reinterpret_cast<f32x4*>(dx + (ib + p) * lddx + col * 4) = t;
-        } else dx[(ib + p) * lddx + col] = r[0];
+        store_vec<VEC>(dx + (ib + p) * lddx + col * VEC, r);
     }
 }
 
@@ -559,10 +537,10 @@ __global__ __launch_bounds__(TPB) void chan_sum_partial(const float* __restrict_
     for (int q = 0; q < VEC; ++q) s[q] = 0.f;
     if (row < rows) {
         for (long p = p0 + row; p < p1; p += rows) {
-            if constexpr (VEC == 4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(x + p * ld + col * 4);
-                s[0] += t[0]; s[1] += t[1]; s[2] += t[2]; s[3] += t[3];
-            } else s[0] += x[p * ld + col];
+            float v[VEC];
+            load_vec<VEC>(x + p * ld + col * VEC, v);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) s[q] += v[q];
         }
 #pragma unroll
         for (int q = 0; q < VEC; ++q) sm[row * C + col * VEC + q] = s[q];
@@ -615,6 +593,80 @@ inline int stream_chunks(int N, int HW, int C, int rows, int& ppc) {
     return (int)((HW + ppc - 1) / ppc);
 }
 
+// ---- launchers behind the extern "C" entry points (which validate, then call these) ----
+// Launch geometry of an [n_img, hw, c] tensor: grid (chunks, n_img); a thread owns vec channels and every rows-th pixel of its chunk's ppc.
+struct Geom { int vec, rows, chunks, ppc; };
+inline Geom reduce_geom(int n_img, int hw, int c) {            // the partial reductions
+    Geom g = {(c % 4 == 0) ? 4 : 1, 0, 0, 0};
+    g.rows = TPB / (c / g.vec);
+    g.chunks = pick_chunks(n_img, hw, c, g.rows);
+    g.ppc = (hw + g.chunks - 1) / g.chunks;
+    return g;
+}
+inline Geom stream_geom(int n_img, int hw, int c) {            // the streaming kernels
+    Geom g = {(c % 4 == 0) ? 4 : 1, 0, 0, 0};
+    g.rows = TPB / (c / g.vec);
+    g.chunks = stream_chunks(n_img, hw, c, g.rows, g.ppc);
+    return g;
+}
+
+// LDS bytes of chan_stats_partial: [rows][c][3 or 7] floats plus the grouped combine's [STATS_GROUPS][c][7] for few channels
+inline size_t stats_lds(const Geom& g, int c, bool minmax) {
+    return ((size_t)g.rows * c * (minmax ? 7 : 3) + (c * STATS_GROUPS <= TPB ? STATS_GROUPS * c * 7 : 0)) * sizeof(float);
+}
+void launch_stats_partial(bool minmax, const Geom& g, size_t lds, const float* x, int ld, int n_img, int hw, int c, float* part, hipStream_t st) {
+    auto kernel = g.vec == 4 ? (minmax ? chan_stats_partial<4, true> : chan_stats_partial<4, false>)
+                             : (minmax ? chan_stats_partial<1, true> : chan_stats_partial<1, false>);
+    hipLaunchKernelGGL(kernel, dim3(g.chunks, n_img), dim3(TPB), lds, st, x, ld, hw, c, g.ppc, part);
+}
+
+// ACT_RELU takes mask / relu as runet_bn_apply does, ACT_LEAKY the slope, ACT_GELU none of the three
+template <int ACT>
+void launch_bn_apply(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale, const float* shift, void* stream,
+                     float slope = 0.f, const float* mask = nullptr, int relu = 0) {
+    hipStream_t st = (hipStream_t)stream;
+    const int nimg = (int)(pixels / hw);
+    const Geom g = stream_geom(nimg, hw, c);
+    const dim3 grid(g.chunks, nimg);
+    const bool v4 = g.vec == 4;
+    if constexpr (ACT == ACT_LEAKY)
+        hipLaunchKernelGGL(v4 ? bn_apply_leaky_kernel<4> : bn_apply_leaky_kernel<1>, grid, dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, g.ppc, scale, shift, slope);
+    else if constexpr (ACT == ACT_GELU)
+        hipLaunchKernelGGL(v4 ? bn_apply_gelu_kernel<4> : bn_apply_gelu_kernel<1>, grid, dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, g.ppc, scale, shift);
+    else
+        hipLaunchKernelGGL(v4 ? bn_apply_kernel<4> : bn_apply_kernel<1>, grid, dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, g.ppc, scale, shift, mask, relu);
+}
+
+// The backward launchers take the kernels' own argument slots: POOL puts (winner bytes, full-resolution width) in (act, ldact) and has
+// VEC = 4 only; mask is the Dropout2d mask (ACT_RELU), the slope (ACT_LEAKY) or unused (ACT_GELU).
+template <bool POOL, int ACT>
+void launch_bn_bwd_reduce(const float* dy, int lddy, const float* x, int ldx, const float* act, int ldact, int n_img, int hw, int c,
+                          const float* mean, const float* invstd, typename MaskArg<ACT>::type mask, float* workspace, float* sums,
+                          const float* rscale, const float* rshift, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const Geom g = reduce_geom(n_img, hw, c);
+    const size_t lds = (size_t)g.rows * c * 2 * sizeof(float);
+    auto kernel = bn_bwd_reduce_partial<4, POOL, ACT>;
+    if constexpr (!POOL) if (g.vec == 1) kernel = bn_bwd_reduce_partial<1, false, ACT>;
+    hipLaunchKernelGGL(kernel, dim3(g.chunks, n_img), dim3(TPB), lds, st, dy, lddy, x, ldx, act, ldact, hw, c, mean, invstd, mask, g.ppc, workspace,
+                       rscale, rshift);
+    const int cw = final_cw(c, (long)g.chunks * n_img);
+    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, g.chunks * n_img, c, cw, sums);
+}
+
+template <bool POOL, int ACT>
+void launch_bn_bwd_apply(const float* dy, int lddy, const float* x, int ldx, const float* act, int ldact, float* dx, int lddx, long pixels, int hw,
+                         int c, const float* mean, const float* invstd, const float* scale, const float* sums,
+                         typename MaskArg<ACT>::type mask, long m_total, const float* rshift, void* stream) {
+    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
+    const int nimg = (int)(pixels / hw);
+    const Geom g = stream_geom(nimg, hw, c);
+    auto kernel = bn_bwd_apply_kernel<4, POOL, ACT>;
+    if constexpr (!POOL) if (g.vec == 1) kernel = bn_bwd_apply_kernel<1, false, ACT>;
+    hipLaunchKernelGGL(kernel, dim3(g.chunks, nimg), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, x, ldx, act, ldact, dx, lddx, hw, c, g.ppc, mean,
+                       invstd, scale, sums, mask, inv_m, rshift);
+}
+
 }  // namespace
 
 #define REQ_VEC(C) RUNET_REQUIRE((C) >= 1 && (C) <= 1024 && ((C) % 4 == 0 || (C) == 1), "channels must be 1 or a multiple of 4, at most 1024")
@@ -636,23 +688,16 @@ extern "C" int runet_chan_stats(const float* x, int ld, int n_img, int hw, int c
     RUNET_REQUIRE(n_img > 0 && hw > 0 && ld >= c, "bad shape");
     RUNET_REQUIRE(!want_minmax || (max_nc && min_nc && imax_nc && imin_nc), "min/max outputs missing");
     hipStream_t st = (hipStream_t)stream;
-    const int vec = (c % 4 == 0) ? 4 : 1;
-    const int cvec = c / vec, rows = TPB / cvec;
-    const int chunks = pick_chunks(n_img, hw, c, rows);
-    const int ppc = (hw + chunks - 1) / chunks;
-    const size_t lds = ((size_t)rows * c * (want_minmax ? 7 : 3) + (c * STATS_GROUPS <= TPB ? STATS_GROUPS * c * 7 : 0)) * sizeof(float);
+    const Geom g = reduce_geom(n_img, hw, c);
+    const size_t lds = stats_lds(g, c, want_minmax);
     RUNET_REQUIRE(lds <= 64 * 1024, "LDS budget");
-    dim3 grid(chunks, n_img);
-#define LAUNCH_STATS(V, MM) hipLaunchKernelGGL((chan_stats_partial<V, MM>), grid, dim3(TPB), lds, st, x, ld, hw, c, ppc, workspace)
-    if (vec == 4) { if (want_minmax) LAUNCH_STATS(4, true); else LAUNCH_STATS(4, false); }
-    else { if (want_minmax) LAUNCH_STATS(1, true); else LAUNCH_STATS(1, false); }
-#undef LAUNCH_STATS
-    const int ccw = chunks >= 16 ? (c >= 8 ? 8 : c) : (c >= 64 ? 64 : c);
+    launch_stats_partial(want_minmax, g, lds, x, ld, n_img, hw, c, workspace, st);
+    const int ccw = g.chunks >= 16 ? (c >= 8 ? 8 : c) : (c >= 64 ? 64 : c);
     dim3 cgrid(cdiv(c, ccw), n_img);
     if (want_minmax)
-        hipLaunchKernelGGL((chan_stats_combine<true>), cgrid, dim3(TPB), 0, st, workspace, c, chunks, ccw, mean_nc, m2_nc, max_nc, min_nc, imax_nc, imin_nc);
+        hipLaunchKernelGGL((chan_stats_combine<true>), cgrid, dim3(TPB), 0, st, workspace, c, g.chunks, ccw, mean_nc, m2_nc, max_nc, min_nc, imax_nc, imin_nc);
     else
-        hipLaunchKernelGGL((chan_stats_combine<false>), cgrid, dim3(TPB), 0, st, workspace, c, chunks, ccw, mean_nc, m2_nc, nullptr, nullptr, nullptr, nullptr);
+        hipLaunchKernelGGL((chan_stats_combine<false>), cgrid, dim3(TPB), 0, st, workspace, c, g.chunks, ccw, mean_nc, m2_nc, nullptr, nullptr, nullptr, nullptr);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -663,16 +708,11 @@ extern "C" int runet_bn_stats(const float* x, int ld, int n_img, int hw, int c, 
     REQ_VEC(c);
     RUNET_REQUIRE(n_img > 0 && hw > 0 && ld >= c && (long)n_img * hw > 1, "bad shape (training needs > 1 value per channel)");
     hipStream_t st = (hipStream_t)stream;
-    const int vec = (c % 4 == 0) ? 4 : 1;
-    const int cvec = c / vec, rows = TPB / cvec;
-    const int chunks = pick_chunks(n_img, hw, c, rows);
-    const int ppc = (hw + chunks - 1) / chunks;
-    const size_t lds = ((size_t)rows * c * 3 + (c * STATS_GROUPS <= TPB ? STATS_GROUPS * c * 7 : 0)) * sizeof(float);
+    const Geom g = reduce_geom(n_img, hw, c);
+    const size_t lds = stats_lds(g, c, false);
     RUNET_REQUIRE(lds <= 64 * 1024, "LDS budget");
-    dim3 grid(chunks, n_img);
-    if (vec == 4) hipLaunchKernelGGL((chan_stats_partial<4, false>), grid, dim3(TPB), lds, st, x, ld, hw, c, ppc, workspace);
-    else hipLaunchKernelGGL((chan_stats_partial<1, false>), grid, dim3(TPB), lds, st, x, ld, hw, c, ppc, workspace);
-    hipLaunchKernelGGL(chan_stats_finalize_kernel, dim3(c), dim3(TPB), 0, st, workspace, c, chunks * n_img, gamma, beta,
+    launch_stats_partial(false, g, lds, x, ld, n_img, hw, c, workspace, st);
+    hipLaunchKernelGGL(chan_stats_finalize_kernel, dim3(c), dim3(TPB), 0, st, workspace, c, g.chunks * n_img, gamma, beta,
                        run_mean, run_var, num_batches_tracked, momentum, eps, scale, shift, save_mean, save_invstd);
     RUNET_CHECK_LAUNCH();
 }
@@ -699,18 +739,17 @@ extern "C" int runet_bn_finalize(const float* mean_nc, const float* m2_nc, int n
     RUNET_CHECK_LAUNCH();
 }
 
+// ---- BatchNorm + activation: forward apply, backward reduce (sums of g and g * xhat -> sums[2c]) and backward apply.  One entry point
+// per (activation, pooled or not); each validates its own arguments and calls the launcher with its template arguments.
+// ReLU forms (the U-Net family): ReLU optional (relu), times a Dropout2d mask if given; the backward takes the ReLU decision from the saved
+// activation (act) or recomputes it from x with the forward's scale / shift (relu_scale / relu_shift), or has no ReLU (neither).
 extern "C" int runet_bn_apply(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale,
                               const float* shift, const float* mask_nc, int relu, void* stream) {
     RUNET_REQUIRE(x && y && scale && shift, "null pointer");
     REQ_VEC(c);
     RUNET_REQUIRE(pixels > 0 && hw > 0 && ldx >= c && ldy >= c, "bad shape");
-    hipStream_t st = (hipStream_t)stream;
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
-    int ppc;
-    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
-    if (vec == 4) hipLaunchKernelGGL((bn_apply_kernel<4>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift, mask_nc, relu);
-    else hipLaunchKernelGGL((bn_apply_kernel<1>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift, mask_nc, relu);
+    launch_bn_apply<ACT_RELU>(x, ldx, y, ldy, pixels, hw, c, scale, shift, stream, 0.f, mask_nc, relu);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -720,16 +759,7 @@ extern "C" int runet_bn_bwd_reduce(const float* dy, int lddy, const float* x, in
     RUNET_REQUIRE(dy && x && mean && invstd && workspace && sums, "null pointer");
     RUNET_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr) && !(act && relu_scale), "give either act or relu_scale + relu_shift");
     REQ_VEC(c);
-    hipStream_t st = (hipStream_t)stream;
-    const int vec = (c % 4 == 0) ? 4 : 1, cvec = c / vec, rows = TPB / cvec;
-    const int chunks = pick_chunks(n_img, hw, c, rows);
-    const int ppc = (hw + chunks - 1) / chunks;
-    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
-    dim3 grid(chunks, n_img);
-    if (vec == 4) hipLaunchKernelGGL((bn_bwd_reduce_partial<4>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, act, ldact, hw, c, mean, invstd, mask_nc, ppc, workspace, relu_scale, relu_shift);
-    else hipLaunchKernelGGL((bn_bwd_reduce_partial<1>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, act, ldact, hw, c, mean, invstd, mask_nc, ppc, workspace, relu_scale, relu_shift);
-    const int cw = final_cw(c, (long)chunks * n_img);
-    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    launch_bn_bwd_reduce<false, ACT_RELU>(dy, lddy, x, ldx, act, ldact, n_img, hw, c, mean, invstd, mask_nc, workspace, sums, relu_scale, relu_shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -739,14 +769,8 @@ extern "C" int runet_bn_bwd_apply(const float* dy, int lddy, const float* x, int
                                   void* stream) {
     RUNET_REQUIRE(dy && x && dx && mean && invstd && scale && sums && !(act && relu_shift), "null pointer / both act and relu_shift");
     REQ_VEC(c);
-    hipStream_t st = (hipStream_t)stream;
-    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
-    int ppc;
-    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
-    if (vec == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<4>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, act, ldact, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, mask_nc, inv_m, relu_shift);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<1>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, act, ldact, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, mask_nc, inv_m, relu_shift);
+    launch_bn_bwd_apply<false, ACT_RELU>(dy, lddy, x, ldx, act, ldact, dx, lddx, pixels, hw, c, mean, invstd, scale, sums, mask_nc, m_total, relu_shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -761,16 +785,15 @@ extern "C" int runet_chan_sum(const float* x, int ld, long pixels, int c, float*
     const long ppc = (pixels + chunks - 1) / chunks;
     chunks = (pixels + ppc - 1) / ppc;
     const size_t lds = (size_t)rows * c * sizeof(float);
-    if (vec == 4) hipLaunchKernelGGL((chan_sum_partial<4>), dim3((int)chunks), dim3(TPB), lds, st, x, ld, pixels, c, ppc, workspace);
-    else hipLaunchKernelGGL((chan_sum_partial<1>), dim3((int)chunks), dim3(TPB), lds, st, x, ld, pixels, c, ppc, workspace);
+    hipLaunchKernelGGL(vec == 4 ? chan_sum_partial<4> : chan_sum_partial<1>, dim3((int)chunks), dim3(TPB), lds, st, x, ld, pixels, c, ppc, workspace);
     const int cw = final_cw(c, chunks);
     hipLaunchKernelGGL(chan_sum_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, (int)chunks, c, cw, out, accumulate);
     RUNET_CHECK_LAUNCH();
 }
 
-// runet_bn_bwd_reduce / runet_bn_bwd_apply for a BatchNorm + ReLU whose output fed ONLY a 2x2 max-pool: the gradient arrives at pooled
-// resolution with the pool's winner bytes and is scattered in registers (POOL instances above); ReLU mask from x (relu_shift form).
-// Same chunking and summation order as the two-launch path, hence the same bits as runet_maxpool2_bwd(accumulate=0) + the plain calls.
+// ... whose output fed ONLY a 2x2 max-pool: the gradient arrives at pooled resolution with the pool's winner bytes and is scattered in
+// registers (POOL instances); ReLU mask from x (relu_shift form).  Same chunking and summation order as the two-launch path, hence the same
+// bits as runet_maxpool2_bwd(accumulate=0) + the plain calls.
 #define REQ_POOLED(h, w, c) RUNET_REQUIRE((h) > 0 && (w) > 0 && (h) % 2 == 0 && (w) % 2 == 0 && (c) % 4 == 0 && (c) >= 4 && (c) <= 1024, \
                                           "h, w must be even and c a multiple of 4 (at most 1024)")
 
@@ -780,15 +803,8 @@ extern "C" int runet_bn_bwd_reduce_pooled(const float* dpool, int ldp, const uns
     RUNET_REQUIRE(dpool && idx && x && mean && invstd && workspace && sums && relu_scale && relu_shift, "null pointer");
     REQ_POOLED(h, w, c);
     RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && ldp % 4 == 0 && ldx % 4 == 0, "bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    const int hw = h * w, rows = TPB / (c / 4);
-    const int chunks = pick_chunks(n_img, hw, c, rows);
-    const int ppc = (hw + chunks - 1) / chunks;
-    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
-    hipLaunchKernelGGL((bn_bwd_reduce_partial<4, true>), dim3(chunks, n_img), dim3(TPB), lds, st, dpool, ldp, x, ldx,
-                       reinterpret_cast<const float*>(idx), w, hw, c, mean, invstd, nullptr, ppc, workspace, relu_scale, relu_shift);
-    const int cw = final_cw(c, (long)chunks * n_img);
-    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    launch_bn_bwd_reduce<true, ACT_RELU>(dpool, ldp, x, ldx, reinterpret_cast<const float*>(idx), w, n_img, h * w, c, mean, invstd, nullptr, workspace,
+                                         sums, relu_scale, relu_shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -798,32 +814,21 @@ extern "C" int runet_bn_bwd_apply_pooled(const float* dpool, int ldp, const unsi
     RUNET_REQUIRE(dpool && idx && x && dx && mean && invstd && scale && sums && relu_shift, "null pointer");
     REQ_POOLED(h, w, c);
     RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && lddx >= c && ldp % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, "bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    const long pixels = (long)n_img * h * w;
-    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
-    const int hw = h * w;
-    int ppc;
-    const int chunks = stream_chunks(n_img, hw, c, TPB / (c / 4), ppc);
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true>), dim3(chunks, n_img), dim3(TPB), 0, st, dpool, ldp, x, ldx,
-                       reinterpret_cast<const float*>(idx), w, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, nullptr, inv_m, relu_shift);
+    launch_bn_bwd_apply<true, ACT_RELU>(dpool, ldp, x, ldx, reinterpret_cast<const float*>(idx), w, dx, lddx, (long)n_img * h * w, h * w, c, mean, invstd,
+                                        scale, sums, nullptr, m_total, relu_shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
-// ---- LeakyReLU(slope) forms of the BatchNorm kernels (YOLOSeg: every BatchNorm2d is followed by nn.LeakyReLU(0.1)).  The backward ones
-// recompute the factor from x with the forward's scale / shift (the relu_scale / relu_shift form of the ReLU entries).  Same launch
-// geometry and summation order as the ReLU entries; the ACT_LEAKY instances of the same kernels.
+// LeakyReLU(slope) forms (YOLOSeg: every BatchNorm2d is followed by nn.LeakyReLU(0.1)).  The backward ones recompute the factor from x with
+// the forward's scale / shift (the relu_scale / relu_shift form of the ReLU entries).  Same launch geometry and summation order as the ReLU
+// entries; the ACT_LEAKY instances of the same kernels.
 extern "C" int runet_bn_apply_leaky(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale, const float* shift,
                                     float slope, void* stream) {
     RUNET_REQUIRE(x && y && scale && shift, "null pointer");
     REQ_VEC(c);
     RUNET_REQUIRE(pixels > 0 && hw > 0 && ldx >= c && ldy >= c, "bad shape");
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    hipStream_t st = (hipStream_t)stream;
-    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
-    int ppc;
-    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
-    if (vec == 4) hipLaunchKernelGGL((bn_apply_leaky_kernel<4>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift, slope);
-    else hipLaunchKernelGGL((bn_apply_leaky_kernel<1>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift, slope);
+    launch_bn_apply<ACT_LEAKY>(x, ldx, y, ldy, pixels, hw, c, scale, shift, stream, slope);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -833,16 +838,7 @@ extern "C" int runet_bn_bwd_reduce_leaky(const float* dy, int lddy, const float*
     RUNET_REQUIRE(dy && x && mean && invstd && workspace && sums && scale && shift, "null pointer");
     REQ_VEC(c);
     RUNET_REQUIRE(n_img > 0 && hw > 0 && lddy >= c && ldx >= c, "bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    const int vec = (c % 4 == 0) ? 4 : 1, rows = TPB / (c / vec);
-    const int chunks = pick_chunks(n_img, hw, c, rows);
-    const int ppc = (hw + chunks - 1) / chunks;
-    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
-    dim3 grid(chunks, n_img);
-    if (vec == 4) hipLaunchKernelGGL((bn_bwd_reduce_partial<4, false, ACT_LEAKY>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, slope, ppc, workspace, scale, shift);
-    else hipLaunchKernelGGL((bn_bwd_reduce_partial<1, false, ACT_LEAKY>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, slope, ppc, workspace, scale, shift);
-    const int cw = final_cw(c, (long)chunks * n_img);
-    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    launch_bn_bwd_reduce<false, ACT_LEAKY>(dy, lddy, x, ldx, nullptr, 0, n_img, hw, c, mean, invstd, slope, workspace, sums, scale, shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -853,13 +849,7 @@ extern "C" int runet_bn_bwd_apply_leaky(const float* dy, int lddy, const float* 
     REQ_VEC(c);
     RUNET_REQUIRE(pixels > 0 && hw > 0 && lddy >= c && ldx >= c && lddx >= c, "bad shape");
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    hipStream_t st = (hipStream_t)stream;
-    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
-    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
-    int ppc;
-    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
-    if (vec == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<4, false, ACT_LEAKY>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, slope, inv_m, shift);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<1, false, ACT_LEAKY>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, slope, inv_m, shift);
+    launch_bn_bwd_apply<false, ACT_LEAKY>(dy, lddy, x, ldx, nullptr, 0, dx, lddx, pixels, hw, c, mean, invstd, scale, sums, slope, m_total, shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -870,15 +860,8 @@ extern "C" int runet_bn_bwd_reduce_pooled_leaky(const float* dpool, int ldp, con
     REQ_POOLED(h, w, c);
     RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && ldp % 4 == 0 && ldx % 4 == 0, "bad shape");
     RUNET_REQUIRE(((uintptr_t)dpool % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
-    hipStream_t st = (hipStream_t)stream;
-    const int hw = h * w, rows = TPB / (c / 4);
-    const int chunks = pick_chunks(n_img, hw, c, rows);
-    const int ppc = (hw + chunks - 1) / chunks;
-    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
-    hipLaunchKernelGGL((bn_bwd_reduce_partial<4, true, ACT_LEAKY>), dim3(chunks, n_img), dim3(TPB), lds, st, dpool, ldp, x, ldx,
-                       reinterpret_cast<const float*>(idx), w, hw, c, mean, invstd, slope, ppc, workspace, scale, shift);
-    const int cw = final_cw(c, (long)chunks * n_img);
-    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    launch_bn_bwd_reduce<true, ACT_LEAKY>(dpool, ldp, x, ldx, reinterpret_cast<const float*>(idx), w, n_img, h * w, c, mean, invstd, slope, workspace,
+                                          sums, scale, shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -889,32 +872,21 @@ extern "C" int runet_bn_bwd_apply_pooled_leaky(const float* dpool, int ldp, cons
     REQ_POOLED(h, w, c);
     RUNET_REQUIRE(n_img > 0 && ldp >= c && ldx >= c && lddx >= c && ldp % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, "bad shape");
     RUNET_REQUIRE(((uintptr_t)dpool % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dx % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
-    hipStream_t st = (hipStream_t)stream;
-    const long pixels = (long)n_img * h * w;
-    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
-    const int hw = h * w;
-    int ppc;
-    const int chunks = stream_chunks(n_img, hw, c, TPB / (c / 4), ppc);
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true, ACT_LEAKY>), dim3(chunks, n_img), dim3(TPB), 0, st, dpool, ldp, x, ldx,
-                       reinterpret_cast<const float*>(idx), w, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, slope, inv_m, shift);
+    launch_bn_bwd_apply<true, ACT_LEAKY>(dpool, ldp, x, ldx, reinterpret_cast<const float*>(idx), w, dx, lddx, (long)n_img * h * w, h * w, c, mean, invstd,
+                                         scale, sums, slope, m_total, shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
-// ---- GELU forms of the BatchNorm kernels (SegFormer-Lite's patch embeddings, Extended_Baseline_Comparison.py:677-688: Conv2d -> BatchNorm2d ->
-// nn.GELU()).  The ACT_GELU instances of the same kernels: same launch geometry and summation order as the LeakyReLU entries; the backward
-// recomputes z = x * scale + shift with the forward's scale / shift.
+// GELU forms (SegFormer-Lite's patch embeddings, Extended_Baseline_Comparison.py:677-688: Conv2d -> BatchNorm2d -> nn.GELU()).  The ACT_GELU
+// instances of the same kernels: same launch geometry and summation order as the LeakyReLU entries; the backward recomputes
+// z = x * scale + shift with the forward's scale / shift.
 extern "C" int runet_bn_apply_gelu(const float* x, int ldx, float* y, int ldy, long pixels, int hw, int c, const float* scale, const float* shift,
                                    void* stream) {
     RUNET_REQUIRE(x && y && scale && shift, "null pointer");
     REQ_VEC(c);
     RUNET_REQUIRE(pixels > 0 && hw > 0 && ldx >= c && ldy >= c, "bad shape");
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    hipStream_t st = (hipStream_t)stream;
-    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
-    int ppc;
-    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
-    if (vec == 4) hipLaunchKernelGGL((bn_apply_gelu_kernel<4>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift);
-    else hipLaunchKernelGGL((bn_apply_gelu_kernel<1>), dim3(chunks, nimg), dim3(TPB), 0, st, x, ldx, y, ldy, hw, c, ppc, scale, shift);
+    launch_bn_apply<ACT_GELU>(x, ldx, y, ldy, pixels, hw, c, scale, shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -923,16 +895,7 @@ extern "C" int runet_bn_bwd_reduce_gelu(const float* dy, int lddy, const float* 
     RUNET_REQUIRE(dy && x && mean && invstd && workspace && sums && scale && shift, "null pointer");
     REQ_VEC(c);
     RUNET_REQUIRE(n_img > 0 && hw > 0 && lddy >= c && ldx >= c, "bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    const int vec = (c % 4 == 0) ? 4 : 1, rows = TPB / (c / vec);
-    const int chunks = pick_chunks(n_img, hw, c, rows);
-    const int ppc = (hw + chunks - 1) / chunks;
-    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
-    dim3 grid(chunks, n_img);
-    if (vec == 4) hipLaunchKernelGGL((bn_bwd_reduce_partial<4, false, ACT_GELU>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, 0.f, ppc, workspace, scale, shift);
-    else hipLaunchKernelGGL((bn_bwd_reduce_partial<1, false, ACT_GELU>), grid, dim3(TPB), lds, st, dy, lddy, x, ldx, nullptr, 0, hw, c, mean, invstd, 0.f, ppc, workspace, scale, shift);
-    const int cw = final_cw(c, (long)chunks * n_img);
-    hipLaunchKernelGGL(bn_bwd_reduce_final, dim3(cdiv(c, cw)), dim3(TPB), 0, st, workspace, chunks * n_img, c, cw, sums);
+    launch_bn_bwd_reduce<false, ACT_GELU>(dy, lddy, x, ldx, nullptr, 0, n_img, hw, c, mean, invstd, 0.f, workspace, sums, scale, shift, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -943,12 +906,6 @@ extern "C" int runet_bn_bwd_apply_gelu(const float* dy, int lddy, const float* x
     REQ_VEC(c);
     RUNET_REQUIRE(pixels > 0 && hw > 0 && lddy >= c && ldx >= c && lddx >= c, "bad shape");
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    hipStream_t st = (hipStream_t)stream;
-    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
-    const int nimg = (int)(pixels / hw), vec = (c % 4 == 0) ? 4 : 1;
-    int ppc;
-    const int chunks = stream_chunks(nimg, hw, c, TPB / (c / vec), ppc);
-    if (vec == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<4, false, ACT_GELU>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, 0.f, inv_m, shift);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<1, false, ACT_GELU>), dim3(chunks, nimg), dim3(TPB), 0, st, dy, lddy, x, ldx, nullptr, 0, dx, lddx, hw, c, ppc, mean, invstd, scale, sums, 0.f, inv_m, shift);
+    launch_bn_bwd_apply<false, ACT_GELU>(dy, lddy, x, ldx, nullptr, 0, dx, lddx, pixels, hw, c, mean, invstd, scale, sums, 0.f, m_total, shift, stream);
     RUNET_CHECK_LAUNCH();
 }

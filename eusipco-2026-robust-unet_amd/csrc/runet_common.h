@@ -82,6 +82,21 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // 16-byte access to four consecutive floats (p 16-byte aligned)
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, const f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+// a thread's VEC (4 or 1) consecutive channels to / from registers: one 16-byte access, or one float
+template <int VEC>
+__device__ __forceinline__ void load_vec(const float* p, float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        const f32x4 t = ld4(p);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else v[0] = p[0];
+}
+template <int VEC>
+__device__ __forceinline__ void store_vec(float* p, const float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        const f32x4 t = {v[0], v[1], v[2], v[3]};
+        st4(p, t);
+    } else p[0] = v[0];
+}
 
 // ---- the two ordered passes of a two-stage reduction (no float atomics: these few lines fix the summation order, so the bits) ----
 // In-block row pass: sm holds [rows][width] floats, one row of sums per thread row of the block.  After the barrier thread u adds column u

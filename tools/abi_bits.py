@@ -1,5 +1,6 @@
 """Bit fingerprints of the entry points whose results rest on a fixed summation order: the two-stage reductions (chunk partials, then the
-ordered final pass sum_parts of csrc/runet_common.h) and the gather adjoints of the bilinear resizes.  Every case fills seeded inputs, calls
+ordered final pass sum_parts of csrc/runet_common.h), the gather adjoints of the bilinear resizes, and every entry point of csrc/norm_act.hip
+(BatchNorm statistics, apply and backward: Chan combines in chunk order, first-occurrence max / min, explicit FMAs).  Every case fills seeded inputs, calls
 the entry point once through the package's binding and prints one SHA-256 per output tensor.  Two builds of the library compute the same
 bits exactly when their printouts are equal line for line; RUNET_HIP_LIB selects the build (see _lib.py), one fresh process per build:
 
@@ -7,7 +8,8 @@ bits exactly when their printouts are equal line for line; RUNET_HIP_LIB selects
   python tools/abi_bits.py > b.txt && diff a.txt b.txt
 
 The shapes are the smallest at which an order can go wrong: fewer partial rows than the final pass has part-lanes (16 or 8), more than
-twice as many, a reduced width that is no multiple of the 16 / 32 outputs of a block; odd non-square and one-row maps for the resizes.
+twice as many, a reduced width that is no multiple of the 16 / 32 outputs of a block; odd non-square and one-row maps for the resizes;
+NA_SHAPES below for norm_act.hip.  New cases go at the end: the seeded generator is drawn from in case order.
 """
 import hashlib
 import importlib
@@ -144,6 +146,137 @@ def bilinear_nhwc_bwd(n, h, w, ho, wo, c):
     return [dx]
 
 
+# ---- csrc/norm_act.hip.  A shape is (n, h, w, c, ld): an NHWC view of c channels with pixel stride ld.
+NA_SHAPES = [
+    (2, 5, 7, 1, 1),            # scalar path, 16-thread grouped row combine, fewer pixels than thread rows
+    (2, 32, 32, 1, 1),          # scalar path, several chunks per image
+    (2, 6, 10, 12, 16),         # 3 channel groups: 85 thread rows plus one idle thread, strided view, even sides for the pooled forms
+    (3, 16, 16, 16, 16),        # the last width on the grouped combine (c * 16 == 256)
+    (3, 16, 16, 32, 40),        # the first width on the general combine, strided
+    (1, 4, 6, 1024, 1024),      # one thread row
+    (16, 64, 64, 4, 4),         # 256 partial rows: the final_cw switch from 32 to 4
+]
+NA_POOLED = [s for s in NA_SHAPES if s[1] % 2 == 0 and s[2] % 2 == 0 and s[3] % 4 == 0]
+
+
+def ties(*shape):
+    """quantised so that equal values occur and the first-occurrence rule decides the max / min indices"""
+    return (torch.round(2 * torch.randn(shape, generator=G)) / 2).to(DEV)
+
+
+def drop_mask(n, c):
+    return ((torch.rand((n, c), generator=G) > 0.5).float() * 2).to(DEV)
+
+
+def red_ws(n, h, w, c):
+    return ws(lib.runet_reduce_workspace_floats(n, h * w, c))
+
+
+def chan_stats(n, h, w, c, ld, minmax):
+    x, k = (ties if minmax else rnd)(n, h, w, ld), red_ws(n, h, w, c)
+    f = [out(n, c) for _ in range(4)]
+    i = [torch.zeros(n, c, dtype=torch.int32, device=DEV) for _ in range(2)]
+    mm = [p(t) if minmax else None for t in f[2:] + i]
+    check(lib.runet_chan_stats(p(x), ld, n, h * w, c, p(k), p(f[0]), p(f[1]), *mm, minmax, ops.stream()))
+    return f + i if minmax else f[:2]
+
+
+def bn_params(c):
+    """gamma, beta, running mean, running variance, num_batches_tracked | scale, shift, saved mean, saved invstd"""
+    return [rnd(c), rnd(c), rnd(c), pos(c), torch.zeros(1, dtype=torch.int64, device=DEV)], [out(c) for _ in range(4)]
+
+
+def bn_stats(n, h, w, c, ld):
+    x, k, (par, res) = rnd(n, h, w, ld), red_ws(n, h, w, c), bn_params(c)
+    check(lib.runet_bn_stats(p(x), ld, n, h * w, c, p(k), *map(p, par), 0.1, 1e-5, *map(p, res), ops.stream()))
+    return res + par[2:]
+
+
+def bn_stats_finalize(nparts, c):
+    part = torch.stack([torch.randint(1, 50, (nparts, c), generator=G).float(), torch.randn((nparts, c), generator=G),
+                        torch.rand((nparts, c), generator=G) * 40], dim=2).contiguous().to(DEV)
+    par, res = bn_params(c)
+    check(lib.runet_bn_stats_finalize(p(part), nparts, c, *map(p, par), 0.1, 1e-5, *map(p, res), ops.stream()))
+    return res + par[2:]
+
+
+def bn_finalize(n, c, hw, training):
+    mean_nc, m2_nc, (par, res) = rnd(n, c), pos(n, c), bn_params(c)
+    check(lib.runet_bn_finalize(p(mean_nc), p(m2_nc), n, c, hw, *map(p, par), 0.1, 1e-5, training, *map(p, res), ops.stream()))
+    return res + par[2:]
+
+
+def bn_apply(n, h, w, c, ld, act, relu=1, mask=False):
+    x, y, sc, sh = rnd(n, h, w, ld), out(n, h, w, ld), rnd(c), rnd(c)
+    head = (p(x), ld, p(y), ld, n * h * w, h * w, c, p(sc), p(sh))
+    if act == "relu":
+        m = drop_mask(n, c) if mask else None
+        check(lib.runet_bn_apply(*head, p(m) if mask else None, relu, ops.stream()))
+    elif act == "leaky":
+        check(lib.runet_bn_apply_leaky(*head, 0.1, ops.stream()))
+    else:
+        check(lib.runet_bn_apply_gelu(*head, ops.stream()))
+    return [y]
+
+
+def bn_bwd(n, h, w, c, ld, form, mask=False, m_total=0):
+    """the reduce entry, then the apply entry on the sums it left.  form: the ReLU entries with the saved activation ("act"), with the
+    decision recomputed from x ("shift") or without ReLU ("plain"); the "leaky" and "gelu" entries"""
+    dy, x, dx, sums, k = rnd(n, h, w, ld), rnd(n, h, w, ld), out(n, h, w, ld), out(2 * c), red_ws(n, h, w, c)
+    mean, invstd, sc, sh = rnd(c), pos(c), rnd(c), rnd(c)
+    hw, pixels, st = h * w, n * h * w, ops.stream()
+    if form in ("leaky", "gelu"):
+        tail = (0.1,) if form == "leaky" else ()
+        red, app = (lib.runet_bn_bwd_reduce_leaky, lib.runet_bn_bwd_apply_leaky) if form == "leaky" else (lib.runet_bn_bwd_reduce_gelu, lib.runet_bn_bwd_apply_gelu)
+        check(red(p(dy), ld, p(x), ld, n, hw, c, p(mean), p(invstd), p(k), p(sums), p(sc), p(sh), *tail, st))
+        check(app(p(dy), ld, p(x), ld, p(dx), ld, pixels, hw, c, p(mean), p(invstd), p(sc), p(sums), m_total, p(sh), *tail, st))
+        return [sums, dx]
+    act = torch.relu(rnd(n, h, w, ld)) if form == "act" else None
+    m = drop_mask(n, c) if mask else None
+    a = (p(act), ld) if form == "act" else (None, 0)
+    rs, rh = (p(sc), p(sh)) if form == "shift" else (None, None)
+    pm = p(m) if mask else None
+    check(lib.runet_bn_bwd_reduce(p(dy), ld, p(x), ld, *a, n, hw, c, p(mean), p(invstd), pm, p(k), p(sums), rs, rh, st))
+    check(lib.runet_bn_bwd_apply(p(dy), ld, p(x), ld, *a, p(dx), ld, pixels, hw, c, p(mean), p(invstd), p(sc), p(sums), pm, m_total, rh, st))
+    return [sums, dx]
+
+
+def bn_bwd_pooled(n, h, w, c, ld, leaky):
+    """gradient at pooled resolution + the 2x2 max-pool's winner bytes (seeded values in 0..3)"""
+    dpool, x, dx, sums, k = rnd(n, h // 2, w // 2, ld), rnd(n, h, w, ld), out(n, h, w, ld), out(2 * c), red_ws(n, h, w, c)
+    idx = torch.randint(0, 4, (n, h // 2, w // 2, c), generator=G, dtype=torch.uint8).to(DEV)
+    mean, invstd, sc, sh = rnd(c), pos(c), rnd(c), rnd(c)
+    red, app = (lib.runet_bn_bwd_reduce_pooled_leaky, lib.runet_bn_bwd_apply_pooled_leaky) if leaky else (lib.runet_bn_bwd_reduce_pooled, lib.runet_bn_bwd_apply_pooled)
+    tail = (0.1,) if leaky else ()
+    check(red(p(dpool), ld, p(idx), p(x), ld, n, h, w, c, p(mean), p(invstd), p(k), p(sums), p(sc), p(sh), *tail, ops.stream()))
+    check(app(p(dpool), ld, p(idx), p(x), ld, p(dx), ld, n, h, w, c, p(mean), p(invstd), p(sc), p(sums), 0, p(sh), *tail, ops.stream()))
+    return [sums, dx]
+
+
+def chan_sum(n, h, w, c, ld, accumulate):
+    x, res, k = rnd(n, h, w, ld), rnd(c), red_ws(n, h, w, c)
+    check(lib.runet_chan_sum(p(x), ld, n * h * w, c, p(k), p(res), accumulate, ops.stream()))
+    return [res]
+
+
+NORM_ACT_CASES = [
+    *[(chan_stats, (*s, mm)) for s in NA_SHAPES for mm in (0, 1)],
+    *[(bn_stats, s) for s in NA_SHAPES],
+    # partials per thread of the one-channel block: none for most | 2 | 4
+    (bn_stats_finalize, (5, 3)), (bn_stats_finalize, (300, 12)), (bn_stats_finalize, (1000, 1)),
+    # one block of 128 channels, partly filled | two blocks
+    *[(bn_finalize, (*s, tr)) for s in ((2, 12, 35), (16, 200, 4096)) for tr in (1, 0)],
+    *[(bn_apply, (*s, "relu", relu, mask)) for s in NA_SHAPES for relu in (0, 1) for mask in (False, True)],
+    *[(bn_bwd, (*s, form, mask)) for s in NA_SHAPES for form in ("act", "shift", "plain") for mask in (False, True)],
+    *[(bn_bwd, (*s, "shift", True, 3 * s[0] * s[1] * s[2])) for s in NA_SHAPES],
+    *[(bn_bwd_pooled, (*s, False)) for s in NA_POOLED],
+    *[(fn, (*s, *a)) for s in NA_SHAPES for fn, a in ((bn_apply, ("leaky",)), (bn_bwd, ("leaky",)))],
+    *[(bn_bwd_pooled, (*s, True)) for s in NA_POOLED],
+    *[(fn, (*s, *a)) for s in NA_SHAPES for fn, a in ((bn_apply, ("gelu",)), (bn_bwd, ("gelu",)))],
+    *[(chan_sum, (*s, acc)) for s in NA_SHAPES for acc in (0, 1)],
+]
+
+
 # (entry point, arguments).  Partial rows each reducing case yields, from its file's chunk rule, against the 16 (hrnet, multiscale,
 # water_index) or 8 (fastscnn, dwsep, dwconv) part-lanes of the final pass:
 CASES = [
@@ -165,6 +298,7 @@ CASES = [
     (pyramid_upsample_bwd, (2, 5, 7, 8)), (pyramid_upsample_bwd, (1, 1, 3, 4)), (pyramid_upsample_bwd, (2, 33, 65, 16)),
     (bilinear_bwd, (3, 5, 7, 11, 13)), (bilinear_bwd, (2, 1, 3, 2, 9)), (bilinear_bwd, (2, 9, 11, 5, 7)),
     (bilinear_nhwc_bwd, (2, 5, 7, 11, 13, 8)), (bilinear_nhwc_bwd, (1, 1, 3, 2, 9, 4)), (bilinear_nhwc_bwd, (2, 9, 11, 5, 7, 12)),
+    *NORM_ACT_CASES,
 ]
 
 
