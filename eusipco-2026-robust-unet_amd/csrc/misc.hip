@@ -372,16 +372,18 @@ extern "C" int runet_adam_multi_dev(const long long* table, int n_tensors, const
 
 // ---- loss scaling (fp16 operands): flag[0] = 1 if any element of buf is Inf / NaN (flag must be zeroed by the caller), flag[1] += flag[0]
 namespace {
+// Inf / NaN: all exponent bits set.  Every finite value is clean, +-FLT_MAX (3.4028235e38, above a literal 3.4e38f) included.
+__device__ __forceinline__ bool nonfinite_(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 __global__ __launch_bounds__(TPB) void nonfinite_kernel(const float* __restrict__ buf, long n, int* __restrict__ flag) {
     bool bad = false;
     const long nv = n / 4;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < nv; i += (long)gridDim.x * TPB) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(buf + i * 4);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) bad |= !(fabsf(v[e]) <= 3.4e38f);
+        for (int e = 0; e < 4; ++e) bad |= nonfinite_(v[e]);
     }
     if (blockIdx.x == 0)
-        for (long i = nv * 4 + threadIdx.x; i < n; i += TPB) bad |= !(fabsf(buf[i]) <= 3.4e38f);
+        for (long i = nv * 4 + threadIdx.x; i < n; i += TPB) bad |= nonfinite_(buf[i]);
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 __global__ void nonfinite_count_kernel(int* flag) { flag[1] += flag[0]; }

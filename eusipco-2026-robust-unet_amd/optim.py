@@ -7,6 +7,10 @@ It is a torch.optim.Optimizer (param_groups / zero_grad / state_dict / lr schedu
 ReduceLROnPlateau work unchanged).  Parameters may have any dense memory layout (model.py stores conv
 weights HWIO): the update is elementwise over the underlying storage, and the gradient must be laid
 out like its parameter (RobustUNet's backward produces exactly that).
+
+Step counts are per parameter, as in torch.optim.Adam: a parameter whose first gradient arrives late starts its own bias
+correction at 1.  The host-hyper form issues one launch per distinct step value in a group (one launch when they all agree); the
+device-hyper form (`capturable`) has ONE step counter per group and raises when the steps of a group's parameters differ.
 """
 from __future__ import annotations
 
@@ -55,6 +59,17 @@ class FusedAdam(torch.optim.Optimizer):
             if "step" in st:
                 st["step"] += 1
 
+    def load_state_dict(self, state_dict):
+        """The device-side step counter belongs to the state that is being replaced: set it to the loaded `step` (a kept counter would
+        go on from where THIS object had got to) and have the hyper-parameters sent again.  Both tensors keep their addresses."""
+        super().load_state_dict(state_dict)
+        for gi, group in enumerate(self.param_groups):
+            st = self._dev_state.get(gi)
+            if st is not None:
+                steps = [self.state[p]["step"] for p in group["params"] if "step" in self.state.get(p, ())]
+                st[1].fill_(int(steps[0]) if steps else 0)
+                st[2] = None
+
     def _table(self, gi, plist):
         key_ptrs = tuple(t.data_ptr() for p in plist for t in (p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]))
         cached = self._tables.get(gi)
@@ -74,6 +89,20 @@ class FusedAdam(torch.optim.Optimizer):
         self._tables[gi] = (key_ptrs, d_tab, d_chunks, len(chunks))
         return d_tab, d_chunks, len(chunks)
 
+    def _step_by_count(self, gi, group, plist):
+        """Host-hyper form, parameters of one group at different step counts: one launch per distinct count, each with its own bias
+        correction (torch.optim.Adam's per-parameter `step`)."""
+        b1, b2 = group["betas"]
+        by_step = {}
+        for p in plist:
+            by_step.setdefault(self.state[p]["step"], []).append(p)
+        for k, (step, sub) in enumerate(sorted(by_step.items())):
+            d_tab, d_chunks, n_chunks = self._table((gi, k), sub)
+            check(lib.runet_adam_multi(d_tab.data_ptr(), len(sub), d_chunks.data_ptr(), n_chunks, float(group["lr"]), float(b1), float(b2),
+                                       float(group["eps"]), float(group["weight_decay"]), int(step), float(self.grad_scale),
+                                       self.skip_flag.data_ptr() if self.skip_flag is not None else None,
+                                       ops.stream()))
+
     @torch.no_grad()
     def step(self, closure=None):
         ops.bump_weight_epoch()      # derived weights (Winograd-domain filters, packed bf16 copies) are stale after this step
@@ -85,6 +114,7 @@ class FusedAdam(torch.optim.Optimizer):
             plist = [p for p in group["params"] if p.grad is not None]
             if not plist:
                 continue
+            first, mixed = self.state[plist[0]], False
             for p in plist:
                 if not p.is_cuda:
                     raise RuntimeError("FusedAdam updates HIP-device parameters only")
@@ -96,7 +126,17 @@ class FusedAdam(torch.optim.Optimizer):
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
-            step = self.state[plist[0]]["step"]
+                mixed |= st["step"] != first["step"]
+            step = first["step"]
+            if mixed:
+                if self.capturable:
+                    for p in plist:       # nothing was launched: leave the counts as they were
+                        self.state[p]["step"] -= 1
+                    raise RuntimeError("FusedAdam(capturable): the parameters of a group have different step counts (a gradient that "
+                                       "arrived late, or a partly loaded state); the device-hyper form keeps one step counter per group. "
+                                       "Put such parameters into a group of their own or use the host-hyper form")
+                self._step_by_count(gi, group, plist)
+                continue
             d_tab, d_chunks, n_chunks = self._table(gi, plist)
             if self.capturable:
                 capturing = torch.cuda.is_current_stream_capturing()
