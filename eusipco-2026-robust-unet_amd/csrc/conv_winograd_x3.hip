@@ -105,10 +105,21 @@ __global__ __launch_bounds__(256, 2) void wino_conv_x3_kernel(WinoX3Args g) {
     const int rbase = ((2 * (lt >> 3)) * RW + 2 * (lt & 7)) * RPS + 2 * k2;
     const int vbase = (lt * 2 + ((k2 >> 2) ^ ((lt >> 3) & 1))) * 16 + (k2 & 3) * 4;      // bytes inside a position's [32 tiles][32 B] image
     auto put = [&](int xi, const float2 v) {
-        const bf16x2 h = {(__bf16)v.x, (__bf16)v.y};
-        const float rx = v.x - (float)h[0], ry = v.y - (float)h[1];
-        const bf16x2 m = {(__bf16)rx, (__bf16)ry};
-        const bf16x2 l = {(__bf16)(rx - (float)m[0]), (__bf16)(ry - (float)m[1])};
+        bool clamp = X3_MODE_WINO == X3_CLAMP;
+        if constexpr (X3_MODE_WINO == X3_WAVE) clamp = __builtin_amdgcn_ballot_w64(fmaxf(fabsf(v.x), fabsf(v.y)) >= H_OVERFLOWS) != 0;
+        bf16x2 h, m, l;
+        __bf16 hj, mj, lj;
+        if (clamp) {
+            split1(v.x, hj, mj, lj);
+            h[0] = hj; m[0] = mj; l[0] = lj;
+            split1(v.y, hj, mj, lj);
+            h[1] = hj; m[1] = mj; l[1] = lj;
+        } else {
+            split1_plain(v.x, hj, mj, lj);
+            h[0] = hj; m[0] = mj; l[0] = lj;
+            split1_plain(v.y, hj, mj, lj);
+            h[1] = hj; m[1] = mj; l[1] = lj;
+        }
         unsigned char* d = Vp + xi * (WT * 32) + vbase;
         *reinterpret_cast<bf16x2*>(d) = h;
         *reinterpret_cast<bf16x2*>(d + VPLANE) = m;

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void conv_nn_x3_kernel(X3ConvArgs g) {
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
             bf16x4 h, m, l;
-            split3(R.ra[v], h, m, l);
+            split3<X3_MODE_CONV>(R.ra[v], h, m, l);
             *reinterpret_cast<bf16x4*>(As + a_st[v]) = h;
             *reinterpret_cast<bf16x4*>(As + 4096 + a_st[v]) = m;
             *reinterpret_cast<bf16x4*>(As + 8192 + a_st[v]) = l;

@@ -2,7 +2,7 @@
 // (derive_multi.hip): every derived weight of the split-operand paths is a pure function of one fp32 weight tensor, thread = (octet of the
 // contraction side, column), 256 threads per block, no LDS.  `vb` is the block index WITHIN the tensor's own grid.
 #pragma once
-#include "runet_common.h"
+#include "x3_common.h"
 #include "../../include/runet_hip.h"
 
 namespace derive {
@@ -22,11 +22,9 @@ __device__ __forceinline__ void store_split(const float (&u)[8], __bf16* d, cons
     bf16x8 h, m, l;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float x = u[j];
-        const __bf16 hj = (__bf16)x;
-        const float r1 = x - (float)hj;
-        const __bf16 mj = (__bf16)r1;
-        h[j] = hj; m[j] = mj; l[j] = (__bf16)(r1 - (float)mj);
+        __bf16 hj, mj, lj;
+        x3::split1(u[j], hj, mj, lj);
+        h[j] = hj; m[j] = mj; l[j] = lj;
     }
     *reinterpret_cast<bf16x8*>(d) = h;
     *reinterpret_cast<bf16x8*>(d + plane) = m;

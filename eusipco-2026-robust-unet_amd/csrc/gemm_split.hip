@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_x3_kernel(X3Args g) {
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
             bf16x4 h, m, l;
-            split3(R.ra[v], h, m, l);
+            split3<X3_MODE_NN>(R.ra[v], h, m, l);
             *reinterpret_cast<bf16x4*>(As + a_st[v]) = h;
             *reinterpret_cast<bf16x4*>(As + 4096 + a_st[v]) = m;
             *reinterpret_cast<bf16x4*>(As + 8192 + a_st[v]) = l;
@@ -292,11 +292,11 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_x3_kernel(X3Args g) {
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
             bf16x4 h, m, l;
-            split3(R.ra[v], h, m, l);
+            split3<X3_MODE_TN>(R.ra[v], h, m, l);
             *reinterpret_cast<bf16x4*>(As + st_off[v]) = h;
             *reinterpret_cast<bf16x4*>(As + TN_PLANE + st_off[v]) = m;
             *reinterpret_cast<bf16x4*>(As + 2 * TN_PLANE + st_off[v]) = l;
-            split3(R.rb[v], h, m, l);
+            split3<X3_MODE_TN>(R.rb[v], h, m, l);
             *reinterpret_cast<bf16x4*>(Bs + st_off[v]) = h;
             *reinterpret_cast<bf16x4*>(Bs + TN_PLANE + st_off[v]) = m;
             *reinterpret_cast<bf16x4*>(Bs + 2 * TN_PLANE + st_off[v]) = l;
@@ -394,11 +394,9 @@ __global__ __launch_bounds__(256) void x3_pack_kernel(const float* __restrict__ 
     bf16x8 h, m, l;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float x = s[(long)j * n];
-        const __bf16 hj = (__bf16)x;
-        const float r1 = x - (float)hj;
-        const __bf16 mj = (__bf16)r1;
-        h[j] = hj; m[j] = mj; l[j] = (__bf16)(r1 - (float)mj);
+        __bf16 hj, mj, lj;
+        split1(s[(long)j * n], hj, mj, lj);
+        h[j] = hj; m[j] = mj; l[j] = lj;
     }
     __bf16* d = dst + (long)z * 3 * per * 8 + r * 8;
     *reinterpret_cast<bf16x8*>(d) = h;

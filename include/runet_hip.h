@@ -267,7 +267,8 @@ int runet_gemm_tn_batched(const float* a, int lda, long stride_a, const float* b
 const char* runet_gemm_batched_kernel_name(int batch, int rows, int k, int n);
 
 /* ---- the same GEMMs in fp32 on the BF16 matrix cores: exact three-way operand splitting, six bf16 MFMAs per fp32 product ("bf16x6") ----
- * The f32-input MFMA runs at 1/16 of the bf16 MFMA rate on gfx950.  x = h + m + l with three bf16 values holds exactly for every fp32 x;
+ * The f32-input MFMA runs at 1/16 of the bf16 MFMA rate on gfx950.  x = h + m + l with three bf16 values holds exactly for every finite fp32 x,
+ * FLT_MAX included (h from x clamped to +-bf16-max; Inf and NaN operands give non-finite results: DESIGN.md 3.0, C1 - C4);
  * six of the nine cross products are kept (the three dropped are <= 2^-23 of the product, the size of one fp32 rounding), all accumulate in
  * fp32: an fp32-accurate GEMM at 6/16 of the matrix time (csrc/gemm_split.hip; measured against float64 in tests/test_gpu_conv.py).
  * These serve the same role as runet_gemm_batched / runet_gemm_tn_batched (the position-GEMMs of nn.Conv2d 3x3, Main_Final.py:157,159).
