@@ -5,14 +5,16 @@
 //
 //   Y = A^T [ (G g G^T) .* (B^T d B) ] A      per 2x2 output tile, 4x4 input patch d, 3x3 filter g
 //
-// Same block (32 tiles = a 4 x 8 patch of 2x2 tiles, 64 output channels), same halo loader, same input transform in registers and same
-// LDS-exchange output transform as wino_conv_kernel<0, false>.  What changes:
+// Same block (32 tiles = a 4 x 8 patch of 2x2 tiles, 64 output channels), same halo loader and same input transform in registers as
+// wino_conv_kernel<0, false>.  What changes:
 //   * transform_store splits every transformed value on its way into LDS: V lives as three bf16 planes [plane][xi 16][tile 32][16 k]
 //     (32-byte rows with the two 16-byte k-octets swapped on tiles with bit 3 set - the conflict-free ds_read_b128 image of gemm_split.hip);
 //   * the filter comes PRE-SPLIT: runet_wino_weights_x3 writes U straight into Up[xi 16][plane 3][K/8][N][8] bf16, so a lane's B fragment
 //     (column n, eight consecutive k) is one 16-byte load from L2 per plane, ringed three steps ahead of its use as before;
-//   * wave w multiplies positions 4w .. 4w+3: per 16-channel chunk and position [32 tiles x 16 k] x [16 k x 64 n] = 2 x 6 MFMAs of 32 cycles
-//     (the f32 form: 16 MFMAs of 64 cycles).
+//   * wave w multiplies positions xi = 4 i + w, i = 0 .. 3 (column w of the 4 x 4 Winograd domain): per 16-channel chunk and position
+//     [32 tiles x 16 k] x [16 k x 64 n] = 2 x 6 MFMAs of 32 cycles (the f32 form: 16 MFMAs of 64 cycles);
+//   * the output transform's stage over i is therefore lane-local: a wave adds its four accumulators in registers and half as much data
+//     goes through the LDS exchange, with every lane storing (see the epilogue).
 #include "x3_common.h"
 #include "../../include/runet_hip.h"
 #include "derive_weights.h"
@@ -48,7 +50,7 @@ constexpr int RPS = 24;           // floats per halo pixel in LDS (16 channels +
 constexpr int VPLANE = 16 * WT * 32;      // bytes of one bf16 plane of V: 16 positions x 32 tiles x 16 k
 
 __global__ __launch_bounds__(256, 2) void wino_conv_x3_kernel(WinoX3Args g) {
-    __shared__ __attribute__((aligned(16))) unsigned char Vp[3 * VPLANE];   // 48 KB; reused as M[16][32][16] fp32 in the epilogue
+    __shared__ __attribute__((aligned(16))) unsigned char Vp[3 * VPLANE];   // 48 KB; reused as S[2][4][32][32] fp32 in the epilogue
     __shared__ __attribute__((aligned(16))) float R[RH * RW * RPS];         // 17 KB raw input halo of the current 16-channel chunk
     __shared__ float sred[4 * 4 * 8 * 2 * 3];                               // statistics: [pass][wave][channel pair][2][count, mean, M2]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -166,14 +168,14 @@ __global__ __launch_bounds__(256, 2) void wino_conv_x3_kernel(WinoX3Args g) {
     for (int b = 0; b < 2; ++b) uoff[b] = (n0 + b * 32 + li < g.N) ? lh * g.N + n0 + b * 32 + li : 0;
     bf16x8 ring[4][3];        // step t lives in slot t & 3, loaded three steps (18 MFMAs) ahead, across the chunk's barriers too
     auto load_step = [&](int t, int c0, bf16x8 (&slot)[3]) {
-        const int xi = wid * 4 + (t >> 1);
+        const int xi = (t >> 1) * 4 + wid;
 #pragma unroll
         for (int p = 0; p < 3; ++p) slot[p] = U16[(long)((xi * 3 + p) * K8 + (c0 >> 3)) * g.N + uoff[t & 1]];      // scalar base + lane offset
     };
     const int a_rd = (li * 2 + (lh ^ ((li >> 3) & 1))) * 16;
     auto read_a = [&](int xl, bf16x8 (&a)[3]) {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(Vp + p * VPLANE + (wid * 4 + xl) * (WT * 32) + a_rd);
+        for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(Vp + p * VPLANE + (xl * 4 + wid) * (WT * 32) + a_rd);
     };
 
     load_halo(0);
@@ -201,41 +203,45 @@ __global__ __launch_bounds__(256, 2) void wino_conv_x3_kernel(WinoX3Args g) {
         }
     }
 
-    // ---- epilogue: exchange the 16 positions through LDS (16 output channels per pass), A^T m A, store ----
-    float* M = reinterpret_cast<float*>(Vp);    // M[xi][t][16]
+    // ---- epilogue: Y = A^T M A with A^T = [1,1,1,0],[0,1,-1,-1].  The stage over i (xi = 4 i + j) is lane-local - the wave holds column j = wid
+    // for all four i - so only s[a'][j], 2 x 4 planes instead of the 16 of M, go through LDS, with every lane storing: two rounds of 32 channels
+    // (one column tile b each, two passes of 16 channels read it), S[a' 2][j 4][tile 32][32 channels] fp32 = 32 KB inside Vp.  A row's two
+    // 16-channel halves are swapped on tiles t with (t ^ t >> 1) & 1 set (tiles 1, 2 of every four): a 32-lane half stores 32 consecutive
+    // dwords; the four tiles it loads from (rows 128 B apart) lie in four different 16-dword groups of ds_read_b64's 64 banks, and the two tiles
+    // of 16 consecutive lanes in the two halves of the 32 banks the paired form ds_read2st64_b64 goes by ----
+    float* S = reinterpret_cast<float*>(Vp);
     const int et = tid >> 3;                    // tile of the two (tile, channel) items this thread finishes
     const int en = (tid & 7) * 2;               // channels en, en+1 of the pass
     const int e_ty = 4 * by + (et >> 3), e_tx = 8 * bx + (et & 7);
     const bool e_ok = e_ty < g.TY && e_tx < g.TX;
     const int e_h = 2 * e_ty, e_w = 2 * e_tx;
+    const int s_wr = (wid * WT + 4 * lh) * 32;
+    const int s_rd = et * 32 + ((((et ^ (et >> 1)) & 1) << 4) | en);
 #pragma unroll
     for (int pass = 0; pass < 4; ++pass) {
-        __syncthreads();
-        const int b = pass >> 1;                // which 32-wide N tile
-        if ((li >> 4) == (pass & 1)) {          // lanes whose column falls into this 16-channel pass
+        if ((pass & 1) == 0) {
+            const int b = pass >> 1;            // which 32-wide N tile
+            __syncthreads();                    // the last chunk's reads of V / the first round's reads of S are done
 #pragma unroll
-            for (int xl = 0; xl < 4; ++xl)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int t = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    M[((wid * 4 + xl) * WT + t) * 16 + (li & 15)] = acc[xl][b][r];
-                }
+            for (int r = 0; r < 16; ++r) {
+                const int t = (r & 3) + 8 * (r >> 2);                                  // + 4 lh: in s_wr
+                float* d = &S[s_wr + t * 32 + (li ^ (((r ^ (r >> 1)) & 1) << 4))];
+                d[0] = (acc[0][b][r] + acc[1][b][r]) + acc[2][b][r];                   // the parent's m[j] + m[4 + j] + m[8 + j], left to right
+                d[4 * WT * 32] = (acc[1][b][r] - acc[2][b][r]) - acc[3][b][r];         // m[4 + j] - m[8 + j] - m[12 + j]
+            }
+            __syncthreads();
         }
-        __syncthreads();
         float2 px[4];
         float npx = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) px[q] = make_float2(0.f, 0.f);
         if (e_ok) {
-            float2 m[16];
+            float2 s[2][4];                     // the stage over j is left
+            const float* sp = &S[s_rd ^ ((pass & 1) << 4)];
 #pragma unroll
-            for (int xi = 0; xi < 16; ++xi) m[xi] = *reinterpret_cast<const float2*>(&M[(xi * WT + et) * 16 + en]);
-            float2 s[2][4];                     // A^T m A : rows [1,1,1,0],[0,1,-1,-1]
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s[0][j] = make_float2(m[j].x + m[4 + j].x + m[8 + j].x, m[j].y + m[4 + j].y + m[8 + j].y);
-                s[1][j] = make_float2(m[4 + j].x - m[8 + j].x - m[12 + j].x, m[4 + j].y - m[8 + j].y - m[12 + j].y);
-            }
+                for (int j = 0; j < 4; ++j) s[i][j] = *reinterpret_cast<const float2*>(sp + (i * 4 + j) * (WT * 32));
             const int nch = n0 + pass * 16 + en;
             if (nch < g.N) {
                 float2 bv = make_float2(0.f, 0.f);

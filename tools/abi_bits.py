@@ -259,6 +259,28 @@ def chan_sum(n, h, w, c, ld, accumulate):
     return [res]
 
 
+def wino_conv_x3(n, h, w, k, nn, bias, accumulate, ldx, ldy, dgrad, stats):
+    """runet_wino_weights_x3, then runet_wino_conv_x3 or runet_wino_conv_x3_stats (csrc/conv_winograd_x3.hip): every bit of y rests on the
+    order of the six products per chunk and of the two output-transform stages, the partials on the order of the Chan combines"""
+    x, wt = rnd(n, h, w, ldx), rnd(3, 3, *((nn, k) if dgrad else (k, nn)))
+    b = rnd(nn) if bias else None
+    y = rnd(n, h, w, ldy) if accumulate else out(n, h, w, ldy)
+    up = torch.empty(lib.runet_wino_x3_pack_elems(k, nn), device=DEV, dtype=torch.bfloat16)
+    check(lib.runet_wino_weights_x3(p(wt), p(up), wt.shape[2], wt.shape[3], dgrad, ops.stream()))
+    head = (p(x), ldx, p(up), p(b) if bias else None, p(y), ldy, n, h, w, k, nn, accumulate)
+    if not stats:
+        check(lib.runet_wino_conv_x3(*head, ops.stream()))
+        return [y]
+    part = out(lib.runet_wino_conv_x3_stats_parts(n, h, w), nn, 3)
+    check(lib.runet_wino_conv_x3_stats(*head, p(part), ops.stream()))
+    return [y, part]
+
+
+# n, h, w, K, N, bias, accumulate, ldx, ldy, dgrad: one partial patch | one full patch at K = N = 64, with and without bias | a second output
+# chunk of 6 channels | 18 patches (remainder group of the block remap), three K chunks, accumulate into a strided slice | data-gradient weights
+WINO_X3_SHAPES = [(1, 6, 10, 16, 6, 1, 0, 16, 6, 0), (1, 8, 16, 64, 64, 1, 0, 64, 64, 0), (1, 8, 16, 64, 64, 0, 0, 64, 64, 0),
+                  (2, 12, 20, 32, 70, 1, 0, 32, 70, 0), (3, 16, 48, 48, 128, 1, 1, 64, 160, 0), (1, 8, 16, 64, 64, 0, 0, 64, 64, 1)]
+
 NORM_ACT_CASES = [
     *[(chan_stats, (*s, mm)) for s in NA_SHAPES for mm in (0, 1)],
     *[(bn_stats, s) for s in NA_SHAPES],
@@ -299,6 +321,7 @@ CASES = [
     (bilinear_bwd, (3, 5, 7, 11, 13)), (bilinear_bwd, (2, 1, 3, 2, 9)), (bilinear_bwd, (2, 9, 11, 5, 7)),
     (bilinear_nhwc_bwd, (2, 5, 7, 11, 13, 8)), (bilinear_nhwc_bwd, (1, 1, 3, 2, 9, 4)), (bilinear_nhwc_bwd, (2, 9, 11, 5, 7, 12)),
     *NORM_ACT_CASES,
+    *[(wino_conv_x3, (*s, st)) for s in WINO_X3_SHAPES for st in (0, 1)],
 ]
 
 
