@@ -10,6 +10,7 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   transformer baseline);  HRNetWater (the same script's multi-resolution baseline);  WaterNet / WaterIndexModule (its water-index U-Net baseline);
   MSWNet / MultiScaleBlock (its multi-scale baseline);  FastSCNN with DepthwiseSeparableConv, LearningToDownsample, PyramidPoolingFastSCNN,
   GlobalFeatureExtractor, FeatureFusionModule and Classifier (comne.py's depthwise-separable baseline);
+  ENet with InitialBlock and BottleneckBlock (comne.py's asymmetric / dilated bottleneck baseline);
   CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
@@ -40,6 +41,7 @@ _LAZY = {
     "HRNetWater": "hrnet", "WaterNet": "waternet", "WaterIndexModule": "waternet", "MSWNet": "mswnet", "MultiScaleBlock": "mswnet",
     "FastSCNN": "fastscnn", "DepthwiseSeparableConv": "fastscnn", "LearningToDownsample": "fastscnn", "PyramidPoolingFastSCNN": "fastscnn",
     "GlobalFeatureExtractor": "fastscnn", "FeatureFusionModule": "fastscnn", "Classifier": "fastscnn",
+    "ENet": "enet", "InitialBlock": "enet", "BottleneckBlock": "enet",
 }
 
 

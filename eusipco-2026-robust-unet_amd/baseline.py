@@ -76,7 +76,9 @@ class FusedNet(nn.Module):
         parameter decides (model._logical): the weight of a transposed convolution [kh, kw, cin, cout] -> [cin, cout, kh, kw], any other
         4-D gradient HWIO -> OIHW, the rest as it is.  Views; ops.deliver_grads copies."""
         if self._transposed is None:
-            self._transposed = frozenset(f"{k}.weight" for k, m in self.named_modules() if isinstance(m, (ConvTranspose2d, ConvTranspose2dK4)))
+            from .enet import ConvTranspose2dK3      # enet.py builds on this module
+            self._transposed = frozenset(f"{k}.weight" for k, m in self.named_modules()
+                                         if isinstance(m, (ConvTranspose2d, ConvTranspose2dK4, ConvTranspose2dK3)))
         return _logical(g, name in self._transposed)
 
 

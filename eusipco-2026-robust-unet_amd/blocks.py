@@ -1615,3 +1615,144 @@ def up_sigmoid_backward(dprob, prob, s):
     dz = torch.empty((n, ho // s, wo // s), device=prob.device, dtype=torch.float32)
     check(lib.runet_up_sigmoid_bwd(dprob.data_ptr(), prob.data_ptr(), dz.data_ptr(), n, ho // s, wo // s, s, ops.stream()))
     return dz
+
+
+# =============================================================================== ENet baseline (comne.py:482-608; csrc/enet.hip)
+# RUNET_NO_FUSED_ENET_INITIAL=1: the initial block from the shared kernels (runet_to_nhwc_pad, runet_conv2d_general with the weight zero-padded
+# to 16 columns, runet_maxpool2_fwd, runet_copy_nhwc, bn_coeff's own statistics pass, runet_conv_wgrad_general) - the A/B partner of
+# runet_enet_initial_*.  RUNET_NO_FUSED_ENET_TAIL=1: the bottleneck's tail from the shared kernels (runet_bn_apply, runet_add_inplace,
+# runet_relu_mask_nhwc and bn_backward per BatchNorm) - the A/B partner of runet_enet_tail_*.  Read at import.
+FUSED_ENET_INITIAL = os.environ.get("RUNET_NO_FUSED_ENET_INITIAL", "0") != "1"
+FUSED_ENET_TAIL = os.environ.get("RUNET_NO_FUSED_ENET_TAIL", "0") != "1"
+
+
+class BottleneckParams:
+    """Physical handles of one BottleneckBlock.  w1 / w3 / wd: HWIO 1x1 weights (wd, bnd: conv_down, None for a plain block); conv2:
+    [(HWIO weight, BNState, (pad_h, pad_w), (dil_h, dil_w))], one entry, or two for the asymmetric block; drop: the Dropout2d holder."""
+    __slots__ = ("w1", "bn1", "conv2", "w3", "bn3", "wd", "bnd", "drop", "cout")
+
+    def __init__(self, w1, bn1, conv2, w3, bn3, wd, bnd, drop, cout):
+        self.w1, self.bn1, self.conv2, self.w3, self.bn3, self.wd, self.bnd, self.drop, self.cout = w1, bn1, conv2, w3, bn3, wd, bnd, drop, cout
+
+
+def enet_initial_forward(x_nchw, w13, bn: BNState, training, sm: Small, save=True, fused=None):
+    """InitialBlock.forward (comne.py:492-497): relu(bn(cat([conv3x3 s2 p1 (x), maxpool2(x)]))).  w13: HWIO [3, 3, 3, 13].
+    Fused (runet_enet_initial_fwd): one pass over the NCHW image writes the 16-wide t and its BatchNorm partials.  Partner (shared kernels):
+    the convolution runs with the weight zero-padded to 16 output columns into the 16-wide buffer t, the pool's three channels are copied
+    over columns 13..15, bn_coeff takes its own statistics pass.  -> (a [n, H/2, W/2, 16], context)"""
+    n, _, H, W = x_nchw.shape
+    if FUSED_ENET_INITIAL if fused is None else fused:
+        t = ops.empty_nhwc(n, H // 2, W // 2, 16, x_nchw)
+        fs = {}
+        sp = ops._stats_buf(fs, lib.runet_enet_initial_parts(n, H, W), 16, x_nchw.device)
+        sn, sc, sh, sw = x_nchw.stride()
+        check(lib.runet_enet_initial_fwd(x_nchw.data_ptr(), sn, sc, sh, sw, w13.data_ptr(), t.data_ptr(), 16, sp, n, H, W, ops.stream()))
+        s, h, mean, invstd, _ = bn_coeff(t, bn, training, sm, fused=fs)
+        a = bn_apply(t, s, h, None, relu=True)
+        return a, (dict(x=x_nchw, t=t, s=s, h=h, mean=mean, invstd=invstd) if save else None)
+    xp = to_nhwc_pad(x_nchw, 4)
+    w16 = torch.zeros((3, 3, 3, 16), device=xp.device, dtype=torch.float32)
+    w16[..., :13].copy_(w13)
+    t = ops.empty_nhwc(n, H // 2, W // 2, 16, xp)
+    ops.conv_general_fwd(xp, w16, None, 2, 1, out=t)
+    pooled, _ = maxpool_forward(xp)
+    check(lib.runet_copy_nhwc(pooled.data_ptr(), ops.ld(pooled), t[..., 13:].data_ptr(), 16, n * (H // 2) * (W // 2), 3, ops.stream()))
+    s, h, mean, invstd, _ = bn_coeff(t, bn, training, sm)
+    a = bn_apply(t, s, h, None, relu=True)
+    return a, (dict(xp=xp, t=t, s=s, h=h, mean=mean, invstd=invstd) if save else None)
+
+
+def enet_initial_backward(cx, da, G, pre, training):
+    """da: gradient of the block's output (overwritten).  G[pre + "conv.weight"] (HWIO [3, 3, 3, 13]), G[pre + "bn.weight" / "bn.bias"]."""
+    sums = vec(32, da.device)
+    dt = bn_backward(da, cx["t"], cx["mean"], cx["invstd"], cx["s"], sums, relu_shift=cx["h"], out=da, training=training)
+    G[pre + "bn.weight"], G[pre + "bn.bias"] = sums[:16], sums[16:]
+    if "x" in cx:          # the fused forward kept the image itself
+        x = cx["x"]
+        n, _, H, W = x.shape
+        dw = torch.empty((3, 3, 3, 13), device=da.device, dtype=torch.float32)
+        sn, sc, sh, sw = x.stride()
+
+        def run():
+            ws = scratch(lib.runet_enet_initial_wgrad_workspace_floats(n, H, W), da.device)
+            check(lib.runet_enet_initial_wgrad(x.data_ptr(), sn, sc, sh, sw, dt.data_ptr(), ops.ld(dt), ws.data_ptr(), ws.numel(), dw.data_ptr(), n, H, W,
+                                               ops.stream()))
+            return dw
+        G[pre + "conv.weight"] = ops._on_side(run, (x, dt, dw)) if ops.side_stream() is not None else run()
+        return
+    dw16 = ops.conv_general_wgrad(cx["xp"], dt, 3, 3, 2, 1, cin_w=3)
+    G[pre + "conv.weight"] = dw16[..., :13].contiguous()
+
+
+def enet_tail_forward(t3, coef3, idn, coef_d=None, mask=None, fused=None):
+    """out = relu(mask * (t3 * scale3 + shift3) + id); id = idn (plain) or idn * scale_d + shift_d (coef_d given: the downsample block)."""
+    n, h, w, c = t3.shape
+    if tuple(idn.shape) != tuple(t3.shape):
+        raise ValueError(f"enet_tail_forward: identity {tuple(idn.shape)} against main branch {tuple(t3.shape)}")
+    s3, h3 = coef3
+    if FUSED_ENET_TAIL if fused is None else fused:
+        out = ops.empty_nhwc(n, h, w, c, t3)
+        sd, hd = coef_d if coef_d is not None else (None, None)
+        check(lib.runet_enet_tail_fwd(t3.data_ptr(), ops.ld(t3), idn.data_ptr(), ops.ld(idn), s3.data_ptr(), h3.data_ptr(),
+                                      sd.data_ptr() if sd is not None else None, hd.data_ptr() if hd is not None else None,
+                                      mask.data_ptr() if mask is not None else None, out.data_ptr(), ops.ld(out), n, h, w, c, ops.stream()))
+        return out
+    y = bn_apply(t3, s3, h3, mask, relu=False)
+    idb = bn_apply(idn, coef_d[0], coef_d[1]) if coef_d is not None else idn
+    check(lib.runet_add_inplace(y.data_ptr(), idb.data_ptr(), y.numel(), ops.stream()))
+    return bn_apply(y, _ones(c, y.device), zeros(c, y.device), None, relu=True, out=y)
+
+
+def enet_tail_backward(dout, out, t3, st3, idn=None, st_d=None, mask=None, training=True, fused=None):
+    """st3 / st_d = (mean, invstd, scale) of conv3's / conv_down's BatchNorm (st_d and idn: the downsample block).
+    -> (dt3, did, sums3 [2c], sums_d [2c] or None): did is dt_d, the gradient of conv_down's raw output, or for the plain block g = dout
+    where out > 0, the identity's gradient onto which the caller accumulates conv1's data gradient."""
+    n, h, w, c = t3.shape
+    dev = t3.device
+    m3, i3, s3 = st3
+    down = st_d is not None
+    if FUSED_ENET_TAIL if fused is None else fused:
+        sums = vec((4 if down else 2) * c, dev)
+        md, idv, sd = st_d if down else (None, None, None)
+        p = lambda t: t.data_ptr() if t is not None else None
+        ldi = ops.ld(idn) if idn is not None else 0
+        ws = scratch(lib.runet_enet_tail_bwd_workspace_floats(n, h, w, c, int(down)), dev)
+        check(lib.runet_enet_tail_bwd_reduce(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), t3.data_ptr(), ops.ld(t3), p(idn), ldi,
+                                             m3.data_ptr(), i3.data_ptr(), p(md), p(idv), p(mask), ws.data_ptr(), ws.numel(), sums.data_ptr(), n, h, w,
+                                             c, ops.stream()))
+        use = sums if training else zeros(4 * c, dev)
+        dt3, did = ops.empty_nhwc(n, h, w, c, t3), ops.empty_nhwc(n, h, w, c, t3)
+        check(lib.runet_enet_tail_bwd_apply(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), t3.data_ptr(), ops.ld(t3), p(idn), ldi,
+                                            m3.data_ptr(), i3.data_ptr(), s3.data_ptr(), p(md), p(idv), p(sd), p(mask), use.data_ptr(), 0,
+                                            dt3.data_ptr(), ops.ld(dt3), did.data_ptr(), ops.ld(did), n, h, w, c, ops.stream()))
+        return dt3, did, sums[:2 * c], (sums[2 * c:] if down else None)
+    g = ops.empty_nhwc(n, h, w, c, t3)
+    check(lib.runet_relu_mask_nhwc(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), g.data_ptr(), ops.ld(g), n * h * w, c, ops.stream()))
+    # runet_bn_bwd_reduce reads mask_nc only together with a ReLU decision (act or relu_shift): the Dropout2d factor is applied in front
+    gm = bn_apply(g, _ones(c, dev), zeros(c, dev), mask) if mask is not None else g
+    sums3 = vec(2 * c, dev)
+    dt3 = bn_backward(gm, t3, m3, i3, s3, sums3, training=training)
+    if not down:
+        return dt3, g, sums3, None
+    sums_d = vec(2 * c, dev)
+    md, idv, sd = st_d
+    return dt3, bn_backward(g, idn, md, idv, sd, sums_d, out=g, training=training), sums3, sums_d
+
+
+def enet_head_forward(x, w, b):
+    """decoder.6 + sigmoid: ConvTranspose2d(c, 1, 2, stride 2); w: the parameter's physical [2, 2, c, 1].  x [n, h, w, c] -> prob [n, 1, 2h, 2w]"""
+    n, h, wd, c = x.shape
+    prob = torch.empty((n, 1, 2 * h, 2 * wd), device=x.device, dtype=torch.float32)
+    check(lib.runet_enet_head_fwd(x.data_ptr(), ops.ld(x), w.data_ptr(), b.data_ptr(), prob.data_ptr(), n, h, wd, c, ops.stream()))
+    return prob
+
+
+def enet_head_backward(dprob, prob, x, w, sink, pre=""):
+    """-> dx; the sink receives pre + "weight" ([2, 2, c, 1]) and pre + "bias" out of one fixed-order buffer"""
+    n, h, wd, c = x.shape
+    dx = ops.empty_nhwc(n, h, wd, c, x)
+    dw_db = sink.buf(pre, [("weight", (2, 2, c, 1)), ("bias", (1,))])
+    ws = scratch(lib.runet_enet_head_bwd_workspace_floats(n, h, wd, c), x.device)
+    check(lib.runet_enet_head_bwd(dprob.data_ptr(), prob.data_ptr(), x.data_ptr(), ops.ld(x), w.data_ptr(), dx.data_ptr(), ops.ld(dx), ws.data_ptr(),
+                                  ws.numel(), dw_db.data_ptr(), n, h, wd, c, ops.stream()))
+    return dx

@@ -1374,6 +1374,141 @@ extern "C" int runet_conv_wgrad_general(const float* x, int ldx, const float* dy
     RUNET_CHECK_LAUNCH();
 }
 
+// Rectangular kernels with per-axis padding and dilation for the ENet baseline (comne.py:482-608: the asymmetric bottleneck's Conv2d (5, 1)
+// padding (2, 0) and (1, 5) padding (0, 2)).  runet_conv2d_general's contract and kernels with (pad_h, pad_w) and (dil_h, dil_w): the geometry
+// struct carries the two axes separately, so this is launcher work only.  Equal pads and dilations give runet_conv2d_general's launches and bits.
+extern "C" int runet_conv2d_rect(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int hin, int win,
+                                 int cin, int cin_w, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int dil_h, int dil_w, int mode,
+                                 int accumulate, void* stream) {
+    RUNET_REQUIRE(x && w && y, "null pointer");
+    RUNET_REQUIRE(cin > 0 && cin % 4 == 0 && cin_w > 0 && cin_w <= cin && cout > 0 && cout % 4 == 0, "channel counts must be multiples of 4");
+    RUNET_REQUIRE(kh >= 1 && kh <= 8 && kw >= 1 && kw <= 8 && stride >= 1 && stride <= 8 && pad_h >= 0 && pad_w >= 0 && dil_h >= 1 && dil_w >= 1,
+                  "unsupported geometry");
+    RUNET_REQUIRE(n_img > 0 && hin > 0 && win > 0, "empty shape");
+    RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
+    const int ho = (hin + 2 * pad_h - dil_h * (kh - 1) - 1) / stride + 1, wo = (win + 2 * pad_w - dil_w * (kw - 1) - 1) / stride + 1;
+    RUNET_REQUIRE(hin + 2 * pad_h - dil_h * (kh - 1) > 0 && win + 2 * pad_w - dil_w * (kw - 1) > 0 && ho > 0 && wo > 0, "empty output");
+    hipStream_t st = (hipStream_t)stream;
+    static const bool no_live_tap = getenv("RUNET_NO_LIVE_TAP_DGRAD") && atoi(getenv("RUNET_NO_LIVE_TAP_DGRAD")) != 0;
+    IGemmArgs a{};
+    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = accumulate; a.KH = kh; a.KW = kw;
+    a.a_div = 1; a.o_scale = 1;
+    if (mode == RUNET_CONV_FWD) {          // x [n,hin,win,cin] -> y [n,ho,wo,cout]
+        RUNET_REQUIRE(ldx >= cin && ldy >= cout, "bad pixel strides");
+        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin_w; a.Ncols = cout;
+        a.w_tap_stride = (long)cin_w * cout; a.w_sk = cout; a.w_sn = 1;
+        a.H = ho; a.W = wo; a.Hin = hin; a.Win = win; a.a_scale = stride; a.tdh = dil_h; a.tdw = dil_w; a.bh = -pad_h; a.bw = -pad_w;
+        a.Hout = ho; a.Wout = wo;
+        dispatch_igemm<false>(a, 1, st);
+    } else if (mode == RUNET_CONV_DGRAD && kh == stride && kw == stride && stride > 1 && pad_h == 0 && pad_w == 0 && dil_h == 1 && dil_w == 1 &&
+               hin == ho * stride && win == wo * stride && !no_live_tap) {
+        // kernel = stride, no padding: one live tap per dx pixel (runet_conv2d_general's form of it)
+        RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
+        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
+        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
+        a.H = ho; a.W = wo; a.Hin = ho; a.Win = wo; a.a_scale = 1; a.KH = 1; a.KW = 1;
+        a.Hout = hin; a.Wout = win; a.o_scale = stride; a.z_taps = stride;
+        dispatch_igemm<true>(a, stride * stride, st);
+    } else if (mode == RUNET_CONV_DGRAD) { // x := dy [n,ho,wo,cin(=conv Cout)] -> y := dx [n,hin,win,cout(=conv Cin)]; w [kh,kw,cout,cin]
+        RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
+        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
+        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
+        a.H = hin; a.W = win; a.Hin = ho; a.Win = wo; a.a_scale = 1; a.tdh = -dil_h; a.tdw = -dil_w; a.bh = pad_h; a.bw = pad_w; a.a_div = stride;
+        a.Hout = hin; a.Wout = win;
+        dispatch_igemm<true>(a, 1, st);
+    } else {
+        RUNET_REQUIRE(false, "mode must be RUNET_CONV_FWD or RUNET_CONV_DGRAD");
+    }
+    RUNET_CHECK_LAUNCH();
+}
+
+// ConvTranspose2d(k3, s2, p1, output_padding 1) forward by output parity class (ENet's decoder.0 / decoder.3): output pixel (2i + ph, 2j + pw)
+// takes the taps r = 1 (ph = 0: source row i) or r = 0, 2 (ph = 1: source rows i + 1, i), likewise for columns - 1, 2, 2 or 4 live taps instead
+// of the 9 (mostly dead) per output pixel that the data-gradient form of runet_conv2d_general runs: four GEMMs over the INPUT pixels whose rows
+// land on the class's output pixels (o_scale = 2).  wq [9][cin][cout]: the parameter's [3][3][cin][cout] slabs in class order,
+// (1,1) | (1,0) (1,2) | (0,1) (2,1) | (0,0) (0,2) (2,0) (2,2), so that tap t = rr * KW + ss of a class reads source (i + ph (1 - rr), j + pw (1 - ss)).
+extern "C" int runet_convt3_pack(const float* w, float* wq, int cin, int cout, void* stream) {
+    RUNET_REQUIRE(w && wq, "null pointer");
+    RUNET_REQUIRE(cin > 0 && cin % 4 == 0 && cout > 0 && cout % 4 == 0, "channel counts must be multiples of 4");
+    RUNET_REQUIRE(((uintptr_t)w % 16) == 0 && ((uintptr_t)wq % 16) == 0, "alignment");
+    RUNET_REQUIRE(w != wq, "wq must not be w (the slabs are permuted, not moved in place)");
+    static const int order[9] = {4, 3, 5, 1, 7, 0, 2, 6, 8};
+    const size_t slab = (size_t)cin * cout;
+    for (int t = 0; t < 9; ++t) {
+        if (hipMemcpyAsync(wq + t * slab, w + order[t] * slab, slab * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) break;
+    }
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_convt3_fwd(const float* x, int ldx, const float* wq, const float* bias, float* y, int ldy, int n_img, int h, int w_, int cin,
+                                int cout, void* stream) {
+    RUNET_REQUIRE(x && wq && y, "null pointer");
+    RUNET_REQUIRE(cin > 0 && cin % 4 == 0 && cout > 0 && cout % 4 == 0, "channel counts must be multiples of 4");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
+    RUNET_REQUIRE(ldx >= cin && ldy >= cout, "bad pixel strides");
+    RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wq % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
+    hipStream_t st = (hipStream_t)stream;
+    static const int first_tap[4] = {0, 1, 3, 5};
+    for (int cls = 0; cls < 4; ++cls) {
+        const int ph = cls >> 1, pw = cls & 1;
+        IGemmArgs a{};
+        a.x = x; a.ldx = ldx; a.w = wq + (long)first_tap[cls] * cin * cout; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.a_div = 1;
+        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
+        a.w_tap_stride = (long)cin * cout; a.w_sk = cout; a.w_sn = 1;
+        a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1;
+        a.KH = ph ? 2 : 1; a.KW = pw ? 2 : 1; a.tdh = ph ? -1 : 0; a.tdw = pw ? -1 : 0; a.bh = ph; a.bw = pw;
+        a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2; a.o_dh = ph; a.o_dw = pw;
+        dispatch_igemm<false>(a, 1, st);
+    }
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" long runet_conv_wgrad_rect_workspace_floats(int pixels, int cin_w, int cout, int kh, int kw) {
+    if (pixels <= 0 || cin_w <= 0 || cout <= 0 || kh < 1 || kh > 8 || kw < 1 || kw > 8) return -1;
+    bool big; int tiles, splits;
+    wgrad_plan(pixels, cin_w, cout, kh * kw, big, tiles, splits);
+    return splits > 1 ? (long)splits * kh * kw * cin_w * cout : 0;
+}
+
+extern "C" int runet_conv_wgrad_rect(const float* x, int ldx, const float* dy, int ldy, float* dw, float* workspace, long workspace_floats,
+                                     int n_img, int hin, int win, int cin, int cin_w, int cout, int kh, int kw, int stride, int pad_h, int pad_w,
+                                     int dil_h, int dil_w, void* stream) {
+    RUNET_REQUIRE(x && dy && dw, "null pointer");
+    RUNET_REQUIRE(cin > 0 && cin % 4 == 0 && cin_w > 0 && cin_w <= cin && cout > 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= cin &&
+                      ldy >= cout,
+                  "channel counts / strides must be multiples of 4");
+    RUNET_REQUIRE(kh >= 1 && kh <= 8 && kw >= 1 && kw <= 8 && stride >= 1 && stride <= 8 && pad_h >= 0 && pad_w >= 0 && dil_h >= 1 && dil_w >= 1,
+                  "unsupported geometry");
+    RUNET_REQUIRE(n_img > 0 && hin > 0 && win > 0, "empty shape");
+    RUNET_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)workspace % 16) == 0, "alignment");
+    const int ho = (hin + 2 * pad_h - dil_h * (kh - 1) - 1) / stride + 1, wo = (win + 2 * pad_w - dil_w * (kw - 1) - 1) / stride + 1;
+    RUNET_REQUIRE(hin + 2 * pad_h - dil_h * (kh - 1) > 0 && win + 2 * pad_w - dil_w * (kw - 1) > 0 && ho > 0 && wo > 0, "empty output");
+    hipStream_t st = (hipStream_t)stream;
+    WGradArgs a{};
+    a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy; a.Kci = cin; a.Kvalid = cin_w; a.Nco = cout; a.Nimg = n_img; a.KH = kh; a.KW = kw;
+    a.H = ho; a.W = wo; a.Hin = hin; a.Win = win; a.a_scale = stride; a.tdh = dil_h; a.tdw = dil_w; a.bh = -pad_h; a.bw = -pad_w;
+    a.Hout = ho; a.Wout = wo; a.o_scale = 1;
+    const long P = (long)n_img * ho * wo;
+    const int ntaps = kh * kw;
+    bool big; int tiles, splits;
+    wgrad_plan(P, cin_w, cout, ntaps, big, tiles, splits);
+    const long wsize = (long)ntaps * cin_w * cout;
+    if (splits > 1 && (workspace == nullptr || workspace_floats < splits * wsize)) {
+        splits = workspace ? (int)(workspace_floats / wsize) : 1;
+        if (splits < 1) splits = 1;
+    }
+    long pps = (P + splits - 1) / splits;
+    pps = (pps + 15) / 16 * 16;
+    splits = cdiv(P, pps);
+    a.pix_per_split = pps;
+    a.out = (splits > 1) ? workspace : dw;
+    dim3 grid(tiles, ntaps, splits);
+    if (big) hipLaunchKernelGGL((wgrad_kernel<128, 128, 64, 64>), grid, dim3(256), 2 * (16 * (128 + 4) * 2) * sizeof(float), st, a);
+    else hipLaunchKernelGGL((wgrad_kernel<64, 64, 32, 32>), grid, dim3(256), 2 * (16 * (64 + 4) * 2) * sizeof(float), st, a);
+    if (splits > 1) hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, splits);
+    RUNET_CHECK_LAUNCH();
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Batched plain GEMMs on the same kernels (the 36 position-GEMMs of the unfused Winograd F(4x4,3x3) path, conv_winograd4.hip).

@@ -1057,6 +1057,123 @@ def convt4_wgrad(x, dy, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------- rectangular kernels, k3-s2 transposed (ENet baseline)
+def _pair(v):
+    return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def conv_rect_out_hw(h, w, kh, kw, stride, pad, dil):
+    (ph, pw), (dh, dw) = _pair(pad), _pair(dil)
+    return (h + 2 * ph - dh * (kh - 1) - 1) // stride + 1, (w + 2 * pw - dw * (kw - 1) - 1) // stride + 1
+
+
+def conv_rect_fwd(x, w_hwio, bias, stride, pad, dil=1, out=None):
+    """Conv2d with a [kh, kw] kernel, padding (pad_h, pad_w) and dilation (dil_h, dil_w) (an int: both axes): runet_conv2d_rect."""
+    n, h, w, cin = x.shape
+    kh, kw, cin_w, cout = w_hwio.shape
+    (ph, pw), (dh, dw) = _pair(pad), _pair(dil)
+    ho, wo = conv_rect_out_hw(h, w, kh, kw, stride, pad, dil)
+    if out is None:
+        out = empty_nhwc(n, ho, wo, cout, x)
+    check(lib.runet_conv2d_rect(x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out),
+                                n, h, w, cin, cin_w, cout, kh, kw, stride, ph, pw, dh, dw, CONV_FWD, 0, stream()))
+    return out
+
+
+def conv_rect_dgrad(dy, w_hwio, hin, win, stride, pad, dil=1, out=None, accumulate=False):
+    n, ho, wo, cout = dy.shape
+    kh, kw, cin, _ = w_hwio.shape
+    (ph, pw), (dh, dw) = _pair(pad), _pair(dil)
+    if (ho, wo) != conv_rect_out_hw(hin, win, kh, kw, stride, pad, dil):
+        raise ValueError(f"dy is {ho} x {wo}, the convolution of a {hin} x {win} input gives {conv_rect_out_hw(hin, win, kh, kw, stride, pad, dil)}")
+    if out is None:
+        out = empty_nhwc(n, hin, win, cin, dy)
+    check(lib.runet_conv2d_rect(dy.data_ptr(), ld(dy), w_hwio.data_ptr(), None, out.data_ptr(), ld(out), n, hin, win, cout, cout, cin, kh, kw,
+                                stride, ph, pw, dh, dw, CONV_DGRAD, int(accumulate), stream()))
+    return out
+
+
+def _conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil, cin_w, out):
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    (ph, pw), (dh, dw) = _pair(pad), _pair(dil)
+    if tuple(dy.shape[1:3]) != conv_rect_out_hw(h, w, kh, kw, stride, pad, dil):
+        raise ValueError("dy does not have the convolution's output size")
+    ws = workspace(lib.runet_conv_wgrad_rect_workspace_floats(dy.shape[0] * dy.shape[1] * dy.shape[2], cin_w, cout, kh, kw), x.device)
+    check(lib.runet_conv_wgrad_rect(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin, cin_w, cout,
+                                    kh, kw, stride, ph, pw, dh, dw, stream()))
+    return out
+
+
+def conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil=1, cin_w=None, out=None, on_side=True):
+    """-> dw [kh, kw, cin_w, cout]; inside the backward pass on the weight-gradient stream, like conv_wgrad."""
+    cin_w = x.shape[3] if cin_w is None else cin_w
+    if out is None:
+        out = torch.empty((kh, kw, cin_w, dy.shape[3]), device=x.device, dtype=torch.float32)
+    if on_side and _side.get("active") is not None:
+        return _on_side(lambda: _conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil, cin_w, out), (x, dy, out))
+    return _conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil, cin_w, out)
+
+
+# RUNET_NO_CONVT3_CLASSES=1: the k3-s2 transposed forward as the data gradient of the stride-2 convolution (9 taps per output pixel, 1 / 2 / 4 live)
+# instead of runet_convt3_fwd's four parity-class GEMMs - its A/B partner.  Read at import.
+CONVT3_CLASSES = os.environ.get("RUNET_NO_CONVT3_CLASSES", "0") != "1"
+
+
+def convt3_class_weights(w_t3):
+    """[3, 3, cin, cout] -> [9, cin, cout] in runet_convt3_fwd's class order (cached per optimizer step)"""
+    _, _, cin, cout = w_t3.shape
+    wp, dev = w_t3.data_ptr(), w_t3.device
+
+    def make(out):
+        wq = out if out is not None else torch.empty((9, cin, cout), device=dev, dtype=torch.float32)
+        check(lib.runet_convt3_pack(wp, wq.data_ptr(), cin, cout, stream()))
+        return wq
+    return _cached(w_t3, "q3", make)
+
+
+def convt3_fwd(x, w_t3, bias=None, out=None, classes=None):
+    """ConvTranspose2d(k3, s2, p1, output_padding 1): x [n, h, w, cin] -> [n, 2h, 2w, cout].  w_t3: the parameter's physical [3, 3, cin, cout].
+    classes (default CONVT3_CLASSES): runet_convt3_fwd, one GEMM per output parity class over the input pixels.  Otherwise the data gradient
+    of Conv2d(cout -> cin, k3, s2, p1) from a 2h x 2w input with the same taps (no flip), whose HWIO weight is the per-tap transpose
+    [3, 3, cout, cin] (cached per optimizer step); the data-gradient mode adds `bias` in its epilogue like the forward."""
+    n, h, w, cin = x.shape
+    cout = w_t3.shape[3]
+    if out is None:
+        out = empty_nhwc(n, 2 * h, 2 * w, cout, x)
+    bp = bias.data_ptr() if bias is not None else None
+    if CONVT3_CLASSES if classes is None else classes:
+        check(lib.runet_convt3_fwd(x.data_ptr(), ld(x), convt3_class_weights(w_t3).data_ptr(), bp, out.data_ptr(), ld(out), n, h, w, cin, cout, stream()))
+        return out
+    wt = transposed_weights(w_t3)
+    check(lib.runet_conv2d_general(x.data_ptr(), ld(x), wt.data_ptr(), bp, out.data_ptr(), ld(out), n, 2 * h, 2 * w, cin, cin, cout, 3, 3, 2, 1, 1,
+                                   CONV_DGRAD, 0, stream()))
+    return out
+
+
+def convt3_dgrad(dy, w_t3, out=None):
+    """dy [n, 2h, 2w, cout] -> dx [n, h, w, cin]: the stride-2 convolution itself."""
+    return conv_general_fwd(dy, transposed_weights(w_t3), None, 2, 1, out=out)
+
+
+def _convt3_wgrad(x, dy, gt, out):
+    cin, cout = x.shape[3], dy.shape[3]
+    conv_general_wgrad(dy, x, 3, 3, 2, 1, out=gt)        # [3, 3, cout, cin]: the convolution's weight gradient, its input dy and output x
+    check(lib.runet_transpose_taps(gt.data_ptr(), out.data_ptr(), 9, cout, cin, stream()))
+    return out
+
+
+def convt3_wgrad(x, dy, out=None, on_side=True):
+    """-> dw in the parameter's physical layout [3, 3, cin, cout]"""
+    cin, cout = x.shape[3], dy.shape[3]
+    if out is None:
+        out = torch.empty((3, 3, cin, cout), device=x.device, dtype=torch.float32)
+    gt = torch.empty((3, 3, cout, cin), device=x.device, dtype=torch.float32)
+    if on_side and _side.get("active") is not None:
+        return _on_side(lambda: _convt3_wgrad(x, dy, gt, out), (x, dy, gt, out))
+    return _convt3_wgrad(x, dy, gt, out)
+
+
 # ------------------------------------------------------------------------------- Winograd F(4x4,3x3), unfused (deep layers)
 _ws4 = {}
 

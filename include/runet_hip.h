@@ -761,6 +761,72 @@ int runet_resize_nearest_u8(const unsigned char* src, int sh, int sw, unsigned c
 int runet_dilate_diff_u8(const unsigned char* mask, int h, int w, int k, unsigned char* coast, unsigned char* dilated, int* counts2,
                          void* stream);
 
+/* ---- ENet baseline (comne.py:482-608; csrc/enet.hip, the rectangular launchers in csrc/conv_igemm.hip).  Its 1x1 and 3x3 (dilation 1..16)
+ *      convolutions, BatchNorm + ReLU, the 2x2 max-pool and the k3-s2 transposed convolutions' gradients and A/B forward (the data gradient of a stride-2 convolution,
+ *      runet_conv2d_general) are shared; these are the pieces nothing else expresses.  NHWC fp32, pixel strides multiples of 4 floats that cover
+ *      the channels (sources and destinations may be channel slices of wider buffers, channels outside the slice stay untouched), tensors
+ *      16-byte aligned, c a multiple of 4, at most 1024.  No float atomics: every sum has a fixed order, block counts depend on the shape only,
+ *      two runs give identical bits.
+ * runet_conv2d_rect / runet_conv_wgrad_rect: runet_conv2d_general / runet_conv_wgrad_general (modes RUNET_CONV_FWD and RUNET_CONV_DGRAD, strides
+ *   1..8, kh, kw <= 8) with padding (pad_h, pad_w) and dilation (dil_h, dil_w) per axis: the asymmetric bottleneck's Conv2d (5, 1) padding
+ *   (2, 0) and (1, 5) padding (0, 2).  Equal pads and dilations give runet_conv2d_general's bits.  runet_conv_wgrad_rect_workspace_floats: the
+ *   split-K slabs for `pixels` output pixels (-1: bad shape).
+ * runet_convt3_fwd: ConvTranspose2d(k3, s2, p1, output_padding 1) forward (decoder.0 / decoder.3), x [n, h, w_, cin] -> y [n, 2h, 2w_, cout], by
+ *   output parity class: four GEMMs over the input pixels with 1 / 2 / 2 / 4 live taps (the data-gradient form of runet_conv2d_general runs
+ *   9 taps per output pixel).  wq [9][cin][cout]: the parameter's physical [3][3][cin][cout] slabs in class order, written by
+ *   runet_convt3_pack (device-to-device copies on `stream`).  bias [cout] may be NULL.
+ * Initial block (InitialBlock.forward): x is the NCHW image [n, 3, h, w_] read through its four strides (in floats, as runet_to_nhwc_pad), h and
+ *   w_ even; w [3][3][3][13], the HWIO memory of the [13, 3, 3, 3] parameter (13 output columns: no shared convolution entry takes it).
+ *   runet_enet_initial_fwd: t [n, h/2, w_/2, 16] = (Conv2d 3x3 stride 2 padding 1 (x), zero padding, taps in (r, s, channel) order | the 2x2
+ *     max of the three image channels, a subset of the same patch; a NaN wins), and part [runet_enet_initial_parts(n, h, w_)][16][3] =
+ *     (count, mean, M2) of t per block of 256 output pixels, the layout runet_bn_stats_finalize consumes (-1: bad shape).
+ *   runet_enet_initial_wgrad: dw [3][3][3][13] = sum over output pixels of patch (x) dt[..., 0:13], dt a 16-channel view; per-chunk partial slabs
+ *     in `workspace` (runet_enet_initial_wgrad_workspace_floats floats, -1: bad shape), added in chunk order.  The image takes no gradient.
+ * Bottleneck tail (BottleneckBlock.forward): t3 the raw output of conv3's convolution, idn the block's input (plain) or the raw output of
+ *   conv_down's convolution (downsample: scale_d / shift_d / mean_d / invstd_d given, NULL otherwise), mask_nc [n][c] the Dropout2d keep mask
+ *   already divided by 1 - p (NULL: none).
+ *   runet_enet_tail_fwd: out = relu(mask * (t3 * scale3 + shift3) + id), id = idn or idn * scale_d + shift_d.
+ *   runet_enet_tail_bwd_reduce: with g = dout where out > 0, sums [2c] = (sum g mask xhat3 | sum g mask), the local (dgamma | dbeta) of conv3's
+ *     BatchNorm; downsample: sums [4c], followed by (sum g xhat_d | sum g) of conv_down's.  workspace: runet_enet_tail_bwd_workspace_floats
+ *     floats (-1: bad shape).
+ *   runet_enet_tail_bwd_apply: dt3 = runet_bn_bwd_apply's formula on g mask (sums: those of the reduce, or zeros in eval mode where
+ *     dt3 = scale3 * g mask; m_total as there, 0: the local pixel count); did = the same for conv_down's BatchNorm on g (downsample) or g itself.
+ * Head (decoder.6 + sigmoid): ConvTranspose2d(c, 1, 2, stride 2), w [2][2][c] (the physical memory of the [c, 1, 2, 2] parameter), bias [1];
+ *   prob, dprob dense [n][2h][2w].
+ *   runet_enet_head_fwd: prob[n, 2i + a, 2j + b] = sigmoid(bias + sum_c x[n, i, j, c] * w[a][b][c]), channels in index order.
+ *   runet_enet_head_bwd: dz = dprob * prob * (1 - prob); dx[n, i, j, c] = sum_ab dz * w[a][b][c]; dw_db [4c + 1] = (dw [2][2][c] | db).
+ *     workspace: runet_enet_head_bwd_workspace_floats floats (-1: bad shape). */
+int runet_conv2d_rect(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int hin, int win, int cin,
+                      int cin_w, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int dil_h, int dil_w, int mode, int accumulate,
+                      void* stream);
+long runet_conv_wgrad_rect_workspace_floats(int pixels, int cin_w, int cout, int kh, int kw);
+int runet_conv_wgrad_rect(const float* x, int ldx, const float* dy, int ldy, float* dw, float* workspace, long workspace_floats, int n_img,
+                          int hin, int win, int cin, int cin_w, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int dil_h,
+                          int dil_w, void* stream);
+int runet_convt3_pack(const float* w, float* wq, int cin, int cout, void* stream);
+int runet_convt3_fwd(const float* x, int ldx, const float* wq, const float* bias, float* y, int ldy, int n_img, int h, int w_, int cin, int cout,
+                     void* stream);
+int runet_enet_initial_parts(int n_img, int h, int w_);
+int runet_enet_initial_fwd(const float* x, long sn, long sc, long sh, long sw, const float* w, float* t, int ldt, float* part, int n_img, int h,
+                           int w_, void* stream);
+long runet_enet_initial_wgrad_workspace_floats(int n_img, int h, int w_);
+int runet_enet_initial_wgrad(const float* x, long sn, long sc, long sh, long sw, const float* dt, int lddt, float* workspace,
+                             long workspace_floats, float* dw, int n_img, int h, int w_, void* stream);
+int runet_enet_tail_fwd(const float* t3, int ldt, const float* idn, int ldi, const float* scale3, const float* shift3, const float* scale_d,
+                        const float* shift_d, const float* mask_nc, float* out, int ldo, int n_img, int h, int w_, int c, void* stream);
+long runet_enet_tail_bwd_workspace_floats(int n_img, int h, int w_, int c, int downsample);
+int runet_enet_tail_bwd_reduce(const float* dout, int lddo, const float* out, int ldo, const float* t3, int ldt, const float* idn, int ldi,
+                               const float* mean3, const float* invstd3, const float* mean_d, const float* invstd_d, const float* mask_nc,
+                               float* workspace, long workspace_floats, float* sums, int n_img, int h, int w_, int c, void* stream);
+int runet_enet_tail_bwd_apply(const float* dout, int lddo, const float* out, int ldo, const float* t3, int ldt, const float* idn, int ldi,
+                              const float* mean3, const float* invstd3, const float* scale3, const float* mean_d, const float* invstd_d,
+                              const float* scale_d, const float* mask_nc, const float* sums, long m_total, float* dt3, int lddt, float* did,
+                              int lddi, int n_img, int h, int w_, int c, void* stream);
+int runet_enet_head_fwd(const float* x, int ldx, const float* w, const float* bias, float* prob, int n_img, int h, int w_, int c, void* stream);
+long runet_enet_head_bwd_workspace_floats(int n_img, int h, int w_, int c);
+int runet_enet_head_bwd(const float* dprob, const float* prob, const float* x, int ldx, const float* w, float* dx, int lddx, float* workspace,
+                        long workspace_floats, float* dw_db, int n_img, int h, int w_, int c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
