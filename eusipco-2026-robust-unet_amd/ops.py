@@ -485,6 +485,36 @@ def _conv_x3(mode, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate, stats=N
     return out
 
 
+# ---- the narrow 1x1 convolutions (both channel counts <= 128, below the split-operand kernels' contraction depth) on the streaming,
+# weight-resident kernel (csrc/conv1x1_stream.hip) instead of the tiled implicit GEMM: same fp32 MFMA chain per element, same bits.
+# RUNET_NO_CONV1X1_STREAM=1 restores the implicit-GEMM launches.  Read at call time.
+USE_CONV1X1_STREAM = os.environ.get("RUNET_NO_CONV1X1_STREAM", "0") != "1"
+
+
+def _conv1x1_stream_case(mode, x, cin, cin_w, cout, kh=1, kw=1, out=None):
+    """A plain 1x1 convolution (forward or data gradient; cin = channels read, cout = channels written) that the implicit GEMM would
+    serve and runet_conv1x1_stream supports.  Never a call that _conv_x3_case takes."""
+    return (USE_CONV1X1_STREAM and _PRECISION == "f32" and kh == 1 and kw == 1 and cin_w == cin
+            and bool(lib.runet_conv1x1_stream_supported(cin, cout, mode)) and not _conv_x3_case(x, cin, cin_w, cout)
+            and ld(x) % 4 == 0 and x.data_ptr() % 16 == 0 and (out is None or (ld(out) % 4 == 0 and out.data_ptr() % 16 == 0)))
+
+
+def _conv1x1_stream(mode, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate):
+    """w_hwio: the module's forward weight in both modes (the data gradient reads it transposed)."""
+    args = (x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out), n, h, w, cin, cout,
+            mode, int(accumulate), stream())
+    if _PROFILE is None:
+        check(lib.runet_conv1x1_stream(*args))
+        return out
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(lib.runet_conv1x1_stream(*args))
+    e1.record()
+    fl = 2.0 * n * h * w * cin * cout
+    _PROFILE.append((lib.runet_conv1x1_stream_kernel_name(cin, cout, int(accumulate)).decode(), fl, fl, e0, e1))
+    return out
+
+
 def conv_fwd(x, w_hwio, bias=None, out=None, dil=1, accumulate=False, keep_v=None, stats=None, pre=None):
     """stats: dict; when the kernel that serves this convolution can take the BatchNorm statistics of its output in its epilogue it fills
     stats["part"] / stats["nparts"] (blocks.bn_coeff(fused=stats) then skips its pass over the tensor), otherwise leaves it empty.
@@ -506,6 +536,8 @@ def conv_fwd(x, w_hwio, bias=None, out=None, dil=1, accumulate=False, keep_v=Non
         out = empty_nhwc(n, h, w, cout, x)
     if kh == 1 and _conv_x3_case(x, cin, cin_w, cout):
         return _conv_x3(CONV_FWD, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate, stats=stats)
+    if dil == 1 and _conv1x1_stream_case(CONV_FWD, x, cin, cin_w, cout, kh, kw, out):
+        return _conv1x1_stream(CONV_FWD, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate)
     _igemm(CONV_FWD, x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None,
            out.data_ptr(), ld(out), n, h, w, cin, cin_w, cout, kh, kw, dil, int(accumulate))
     return out
@@ -609,6 +641,8 @@ def conv_dgrad(dy, w_hwio, out=None, dil=1, accumulate=False, keep_z=None, bn=No
         out = empty_nhwc(n, h, w, cin, dy)
     if kh == 1 and _conv_x3_case(dy, cout, cout, cin):
         return _conv_x3(CONV_DGRAD, dy, w_hwio, None, out, n, h, w, cout, cin, accumulate)
+    if dil == 1 and _conv1x1_stream_case(CONV_DGRAD, dy, cout, cout, cin, kh, kw, out):
+        return _conv1x1_stream(CONV_DGRAD, dy, w_hwio, None, out, n, h, w, cout, cin, accumulate)
     if USE_TRANSPOSED_DGRAD:
         _igemm(CONV_DGRAD_T, dy.data_ptr(), ld(dy), transposed_weights(w_hwio).data_ptr(), None, out.data_ptr(), ld(out), n, h, w,
                cout, cout, cin, kh, kw, dil, int(accumulate))
@@ -752,6 +786,20 @@ def _on_side(fn, tensors):
     return r
 
 
+# The weight gradient of the same narrow 1x1 layers on the streaming kernel (runet_conv1x1_wgrad_stream) instead of wgrad_tile_kernel; same
+# stream, same workspace pool.  Off by default: alone it does not move the step (it runs on the side stream), and it pairs the pixels
+# differently, so the gradients differ from the tile kernel's in their last bits.  RUNET_CONV1X1_WGRAD_STREAM=1 turns it
+# on, RUNET_NO_CONV1X1_WGRAD_STREAM=1 keeps it off whatever else is set.  Read at call time.
+USE_CONV1X1_WGRAD_STREAM = (os.environ.get("RUNET_CONV1X1_WGRAD_STREAM", "0") == "1"
+                            and os.environ.get("RUNET_NO_CONV1X1_WGRAD_STREAM", "0") != "1")
+
+
+def _conv1x1_wgrad_stream_case(x, dy, cin, cin_w, cout, kh=1, kw=1, out=None):
+    return (USE_CONV1X1_WGRAD_STREAM and _PRECISION == "f32" and kh == 1 and kw == 1 and cin_w == cin
+            and bool(lib.runet_conv1x1_wgrad_stream_supported(cin, cout)) and ld(x) % 4 == 0 and x.data_ptr() % 16 == 0
+            and ld(dy) % 4 == 0 and dy.data_ptr() % 16 == 0 and (out is None or (out.is_contiguous() and out.data_ptr() % 16 == 0)))
+
+
 def conv_wgrad(x, dy, kh, kw, cin_w=None, dil=1, out=None, v=None, on_side=True, z=None):
     if on_side and _side.get("active") is not None:
         if out is None:
@@ -784,6 +832,11 @@ def _conv_wgrad(x, dy, kh, kw, cin_w=None, dil=1, out=None, v=None, z=None):
         nws = lib.runet_wino_wgrad_workspace_floats(n, h, w, cin, cout)
         ws = workspace(nws, x.device)
         check(lib.runet_wino_wgrad(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin, cout, stream()))
+    elif dil == 1 and _conv1x1_wgrad_stream_case(x, dy, cin, cin_w, cout, kh, kw, out):
+        name = "conv1x1_wgrad_stream_kernel(+sum)"
+        ws = workspace(lib.runet_conv1x1_wgrad_stream_workspace_floats(n, h, w, cin, cout), x.device)
+        check(lib.runet_conv1x1_wgrad_stream(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin, cout,
+                                             stream()))
     else:
         name = "wgrad_tile_kernel/wgrad_kernel(+reduce)"
         nws = lib.runet_conv_wgrad_workspace_floats(n, h, w, cin_w, cout, kh, kw)

@@ -301,6 +301,29 @@ int runet_conv_x3(const float* x, int ldx, const void* wpacked, const float* bia
                   int mode, int accumulate, void* stream);
 const char* runet_conv_x3_kernel_name(int n_img, int h, int w, int cout, int mode);
 
+/* ---- the narrow nn.Conv2d(k=1) layers (Main_Final.py:126,131,172), forward and data gradient, as a streaming kernel with the weight
+ * resident in LDS (csrc/conv1x1_stream.hip): persistent blocks, one weight load per block, no block barrier in the pixel loop, the next
+ * tile's loads in flight across the current tile's MFMAs.  Modes RUNET_CONV_FWD (w [cin][cout]) and RUNET_CONV_DGRAD (w = the module's
+ * forward weight [cout][cin], read transposed) with runet_conv_igemm's argument meaning; cin % 16 == 0, cout % 4 == 0, both <= 128,
+ * ldx / ldy % 4 == 0, pointers 16-byte aligned.  y has the bits runet_conv_igemm gives (same fp32 MFMA chain per element, acc + bias + old).
+ * runet_conv1x1_stream_blocks: the number of persistent blocks of a launch (from the CU count; RUNET_CONV1X1_STREAM_BLOCKS, read at
+ * call time, forces it: measurement knob).  runet_conv1x1_stream_kernel_name: the instantiation's name as rocprofv3 prints it. */
+int runet_conv1x1_stream_supported(int cin, int cout, int mode);
+int runet_conv1x1_stream_blocks(int n_img, int h, int w, int cin, int cout);
+int runet_conv1x1_stream(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int h, int w_, int cin,
+                         int cout, int mode, int accumulate, void* stream);
+const char* runet_conv1x1_stream_kernel_name(int cin, int cout, int accumulate);
+/* weight gradient of the same layers (Main_Final.py:581 loss.backward()): dw[cin][cout] = sum over pixels of x (x) dy, the pixel as the MFMA
+ * contraction, every wave streaming a contiguous pixel range with the whole result in registers; one slab per block in `workspace`
+ * (>= runet_conv1x1_wgrad_stream_workspace_floats floats), summed in a fixed order.  cin, cout in {32, 64, 128}, not both 128.  The slab
+ * count depends on the pixel count alone (runet_conv1x1_wgrad_stream_slabs: ceil(pixels / 256), at most 256), so the result is bitwise
+ * reproducible from run to run and on every device. */
+int runet_conv1x1_wgrad_stream_supported(int cin, int cout);
+int runet_conv1x1_wgrad_stream_slabs(int n_img, int h, int w);
+long runet_conv1x1_wgrad_stream_workspace_floats(int n_img, int h, int w, int cin, int cout);
+int runet_conv1x1_wgrad_stream(const float* x, int ldx, const float* dy, int ldy, float* dw, float* workspace, long workspace_floats,
+                               int n_img, int h, int w_, int cin, int cout, void* stream);
+
 /* ---- every derived weight of a step in one launch (csrc/derive_multi.hip).  The split-operand kernels read their weights as bf16 planes made
  * by runet_wino4_weights_x3 / runet_wino_weights_x3 / runet_conv_x3_pack once per optimizer step (the reference has no such step: its weights
  * are read as they are, Main_Final.py:123-134, 261-270); these three calls batch them: fill a host table with runet_derive_desc (same arguments as

@@ -105,6 +105,16 @@ def main():
         by = 4.0 * (ipix * cin + opix * cout * (2 if acc else 1)) + 6.0 * taps * cin * cout
         return f"{MODES.get(mode, mode):>14s} {n}x{h}x{w} {cin:4d}->{cout:4d} x3 ld{a[1]}/{a[5]}{' +=' if acc else ''}", fl, by
 
+    def d_conv1x1_stream(a):    # x ldx w bias y ldy n h w cin cout mode acc stream
+        n, h, w, cin, cout, mode, acc = a[6:13]
+        fl = 2.0 * n * h * w * cin * cout
+        by = 4.0 * (n * h * w * (cin + cout * (2 if acc else 1)) + cin * cout)
+        return f"{MODES.get(mode, mode):>14s} {n}x{h}x{w} {cin:4d}->{cout:4d} stream ld{a[1]}/{a[5]}{' +=' if acc else ''}", fl, by
+
+    def d_conv1x1_wgrad_stream(a):    # x ldx dy ldy dw ws wsf n h w cin cout stream
+        n, h, w, cin, cout = a[7:12]
+        return f"{'wgrad':>14s} {n}x{h}x{w} {cin:4d}->{cout:4d} k1 d1 stream", 2.0 * n * h * w * cin * cout, 4.0 * (n * h * w * (cin + cout) + cin * cout)
+
     def d_gemm_x3_tn(a):  # a lda sa b ldb sb c batch rows k n rps stream
         batch, rows, k, n = a[7:11]
         return f"{'gemm TN x3':>14s} {batch}x[{rows}x{k}]^T[{rows}x{n}]", 4.0 * 2.0 * batch * rows * k * n, 4.0 * batch * rows * (k + n)
@@ -114,6 +124,9 @@ def main():
         return f"{'gemm NN x3':>14s} {batch}x[{rows}x{k}][{k}x{n}]", 4.0 * 2.0 * batch * rows * k * n, 4.0 * batch * (rows * (k + n)) + 6.0 * batch * k * n
 
     wrap("runet_conv_x3", d_conv_x3)
+    if hasattr(lib, "runet_conv1x1_stream"):      # absent from an older build selected for an A/B
+        wrap("runet_conv1x1_stream", d_conv1x1_stream)
+        wrap("runet_conv1x1_wgrad_stream", d_conv1x1_wgrad_stream)
     wrap("runet_wino4_conv_x3", d_wino4)
     wrap("runet_gemm_x3_tn_batched", d_gemm_x3_tn)
     wrap("runet_gemm_x3_batched", d_gemm_x3_nn)
