@@ -11,6 +11,7 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   MSWNet / MultiScaleBlock (its multi-scale baseline);  FastSCNN with DepthwiseSeparableConv, LearningToDownsample, PyramidPoolingFastSCNN,
   GlobalFeatureExtractor, FeatureFusionModule and Classifier (comne.py's depthwise-separable baseline);
   ENet with InitialBlock and BottleneckBlock (comne.py's asymmetric / dilated bottleneck baseline);
+  PSPNet with PyramidPooling (comne.py's pyramid-pooling baseline);
   CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
@@ -42,6 +43,7 @@ _LAZY = {
     "FastSCNN": "fastscnn", "DepthwiseSeparableConv": "fastscnn", "LearningToDownsample": "fastscnn", "PyramidPoolingFastSCNN": "fastscnn",
     "GlobalFeatureExtractor": "fastscnn", "FeatureFusionModule": "fastscnn", "Classifier": "fastscnn",
     "ENet": "enet", "InitialBlock": "enet", "BottleneckBlock": "enet",
+    "PSPNet": "pspnet", "PyramidPooling": "pspnet",
 }
 
 

@@ -1511,14 +1511,23 @@ def _pyr_view(buf, j, n):
 def ppm_forward(cat, p: PPMParams, training, sm: Small, save=True):
     """PyramidPoolingFastSCNN (comne.py:343-371).  cat [n, h, w, 2c]: channels [0, c) hold the module's input (written there by its producer),
     channels [c, 2c) receive the four resized branches - the reference's torch.cat without a copy.  -> context or None"""
-    n, h, w, c2 = cat.shape
-    c = c2 // 2
+    c = cat.shape[3] // 2
+    cx = ppm_cells_forward(cat[..., :c], p, training, sm)
+    n, h, w, _ = cx["shape"]
+    up = cat[..., c:]
+    check(lib.runet_pyramid_upsample_fwd(cx["acts"].data_ptr(), c // 4, up.data_ptr(), ops.ld(up), n, h, w, c // 4, ops.stream()))
+    return cx if save else None
+
+
+def ppm_cells_forward(x, p: PPMParams, training, sm: Small):
+    """ppm_forward up to the activated branch cells, without the resize: x [n, h, w, c] (may be a channel slice).
+    -> context with acts [50 n, c // 4], branch-major (_pyr_view)"""
+    n, h, w, c = x.shape
     cq = c // 4
-    x = cat[..., :c]
     st = ops.stream()
-    pooled = torch.empty((PYR_ROWS * n, c), device=cat.device, dtype=torch.float32)
+    pooled = torch.empty((PYR_ROWS * n, c), device=x.device, dtype=torch.float32)
     check(lib.runet_pyramid_pool_fwd(x.data_ptr(), ops.ld(x), pooled.data_ptr(), c, n, h, w, c, st))
-    acts = torch.empty((PYR_ROWS * n, cq), device=cat.device, dtype=torch.float32)
+    acts = torch.empty((PYR_ROWS * n, cq), device=x.device, dtype=torch.float32)
     br = []
     for j in range(4):
         pj = _pyr_view(pooled, j, n)
@@ -1527,9 +1536,7 @@ def ppm_forward(cat, p: PPMParams, training, sm: Small, save=True):
         s, hh, mean, invstd, _ = bn_coeff(t, p.bns[j], training, sm, fused=fs)
         bn_apply(t, s, hh, None, relu=True, out=_pyr_view(acts, j, n))
         br.append(dict(x=pj, w=p.ws[j], t=t, s=s, h=hh, mean=mean, invstd=invstd))
-    up = cat[..., c:]
-    check(lib.runet_pyramid_upsample_fwd(acts.data_ptr(), cq, up.data_ptr(), ops.ld(up), n, h, w, cq, st))
-    return dict(br=br, acts=acts, shape=(n, h, w, c)) if save else None
+    return dict(br=br, acts=acts, shape=(n, h, w, c))
 
 
 def ppm_backward(cx, dcat, G, pre, training):
@@ -1537,11 +1544,19 @@ def ppm_backward(cx, dcat, G, pre, training):
     {pre}convs.{j}.2.weight / .bias (the BatchNorms).  -> the gradient of the module's input [n, h, w, c]"""
     n, h, w, c = cx["shape"]
     cq = c // 4
-    dev = dcat.device
-    st = ops.stream()
     dup = dcat[..., c:]
-    dacts = torch.empty((PYR_ROWS * n, cq), device=dev, dtype=torch.float32)
-    check(lib.runet_pyramid_upsample_bwd(dup.data_ptr(), ops.ld(dup), dacts.data_ptr(), cq, n, h, w, cq, st))
+    dacts = torch.empty((PYR_ROWS * n, cq), device=dcat.device, dtype=torch.float32)
+    check(lib.runet_pyramid_upsample_bwd(dup.data_ptr(), ops.ld(dup), dacts.data_ptr(), cq, n, h, w, cq, ops.stream()))
+    return ppm_cells_backward(cx, dacts, dcat[..., :c], G, pre, training)
+
+
+def ppm_cells_backward(cx, dacts, direct, G, pre, training):
+    """ppm_backward behind the resize's adjoint: dacts [50 n, c // 4] the gradient of the activated branch cells, direct [n, h, w, c] (may be
+    a channel slice) the gradient that reaches the module's input beside the pyramid.  -> the gradient of the module's input"""
+    n, h, w, c = cx["shape"]
+    cq = c // 4
+    dev = dacts.device
+    st = ops.stream()
     dpooled = torch.empty((PYR_ROWS * n, c), device=dev, dtype=torch.float32)
     for j, b in enumerate(cx["br"]):
         sums = vec(2 * cq, dev)
@@ -1550,8 +1565,7 @@ def ppm_backward(cx, dcat, G, pre, training):
         G[f"{pre}convs.{j}.1.weight"] = ops.conv_wgrad(b["x"], dt, 1, 1)
         G[f"{pre}convs.{j}.1.bias"] = chan_sum(dt, vec(cq, dev))
         ops.conv_dgrad(dt, b["w"], out=_pyr_view(dpooled, j, n))
-    direct = dcat[..., :c]
-    dx = ops.empty_nhwc(n, h, w, c, dcat)
+    dx = ops.empty_nhwc(n, h, w, c, direct)
     check(lib.runet_pyramid_pool_bwd(dpooled.data_ptr(), c, direct.data_ptr(), ops.ld(direct), dx.data_ptr(), ops.ld(dx), n, h, w, c, st))
     return dx
 
@@ -1756,3 +1770,128 @@ def enet_head_backward(dprob, prob, x, w, sink, pre=""):
     check(lib.runet_enet_head_bwd(dprob.data_ptr(), prob.data_ptr(), x.data_ptr(), ops.ld(x), w.data_ptr(), dx.data_ptr(), ops.ld(dx), ws.data_ptr(),
                                   ws.numel(), dw_db.data_ptr(), n, h, wd, c, ops.stream()))
     return dx
+
+
+# =============================================================================== PSPNet baseline (comne.py:214-299; csrc/pspnet.hip)
+# final_conv.0 convolves cat[x, up(P_1), up(P_2), up(P_3), up(P_6)].  Tap planes: the pyramid half of that convolution on the 50 cells per
+# image (Z_j = P_j . Wtap_j through the shared 1x1 convolution, runet_psp_taps_fwd adds the shifted, resized planes onto the 3x3 convolution
+# of x alone); no concat buffer, no upsampled channels, half the matrix work of the layer in all three passes.  Head: BatchNorm, ReLU,
+# Dropout2d and the 1x1 convolution in one pass (runet_psp_head_*).  Both are OPT-IN (RUNET_FUSED_PSP_TAPS=1, RUNET_FUSED_PSP_HEAD=1): in
+# the 16 x 256^2 step neither gain - the tap planes over the reference's order on the shared kernels (the concat buffer,
+# runet_pyramid_upsample_*, one 3x3 convolution 2c -> cout), the head over runet_bn_apply + runet_outc_* - was larger than the
+# round-to-round spread.  RUNET_NO_FUSED_PSP_TAPS=1 / RUNET_NO_FUSED_PSP_HEAD=1 force the default.  Read at import.
+FUSED_PSP_TAPS = os.environ.get("RUNET_FUSED_PSP_TAPS", "0") == "1" and os.environ.get("RUNET_NO_FUSED_PSP_TAPS", "0") != "1"
+FUSED_PSP_HEAD = os.environ.get("RUNET_FUSED_PSP_HEAD", "0") == "1" and os.environ.get("RUNET_NO_FUSED_PSP_HEAD", "0") != "1"
+PSP_HEAD_SCALE = 16
+
+
+def psp_split_weights(w_hwio, cache):
+    """final_conv.0's weight [3, 3, 2c, cout] (the parameter's physical view) -> (wx [3, 3, c, cout]: the rows that meet x; wp [1, 1, c, 9 cout]:
+    the rows that meet the pyramid, input channel outermost, so branch j's Wtap_j [c // 4, 9 cout] is the contiguous block wp[:, :, j c/4 : (j + 1) c/4]).
+    Copies kept in `cache` (the model's dict) and rewritten in place, on the current stream, when the parameter has changed (its version
+    counter or ops.WEIGHT_EPOCH): call it before ops.prefetch_derived(), whose refills of the derived forms of wx / wp then follow the copy
+    in stream order.  The copies go through torch, so their own version counters move and ops._cached sees them as new."""
+    base = w_hwio._base if w_hwio._base is not None else w_hwio
+    kh, kw, c2, cout = w_hwio.shape
+    c = c2 // 2
+    tag = (base._version, ops.WEIGHT_EPOCH, w_hwio.data_ptr(), tuple(w_hwio.shape))
+    if cache.get("tag") != tag:
+        if "wx" not in cache or cache["wx"].device != w_hwio.device or tuple(cache["wx"].shape) != (kh, kw, c, cout):
+            cache["wx"] = torch.empty((kh, kw, c, cout), device=w_hwio.device, dtype=torch.float32)
+            cache["wp"] = torch.empty((1, 1, c, kh * kw * cout), device=w_hwio.device, dtype=torch.float32)
+        with torch.no_grad():
+            cache["wx"].copy_(w_hwio[:, :, :c, :])
+            cache["wp"].view(c, kh, kw, cout).copy_(w_hwio[:, :, c:, :].permute(2, 0, 1, 3))
+        cache["tag"] = tag
+    return cache["wx"], cache["wp"]
+
+
+def psp_join_wgrad(dwx, dwp):
+    """the two halves' weight gradients -> one [3, 3, 2c, cout] tensor in the parameter's physical layout.  Inside the backward pass the
+    halves are written on the weight-gradient stream, so the two copies go there too (torch-level switch: they are torch copies)."""
+    kh, kw, c, cout = dwx.shape
+    g = torch.empty((kh, kw, 2 * c, cout), device=dwx.device, dtype=torch.float32)
+
+    def run():
+        g[:, :, :c, :].copy_(dwx)
+        g[:, :, c:, :].copy_(dwp.view(c, kh, kw, cout).permute(1, 2, 0, 3))
+        return g
+    if ops.side_stream() is None:
+        return run()
+    prev = ops._side.get("torch_switch")
+    ops._side["torch_switch"] = True
+    try:
+        return ops._on_side(run, (dwx, dwp, g))
+    finally:
+        ops._side["torch_switch"] = prev
+
+
+def psp_taps_forward(t, acts, wp):
+    """t [n, h, w, cout] (may be a channel slice) += the pyramid half of the 3x3 convolution: acts [50 n, cq] the activated branch cells
+    (ppm_cells_forward), wp [1, 1, 4 cq, 9 cout] (psp_split_weights).  -> t"""
+    n, h, w, cout = t.shape
+    cq = acts.shape[1]
+    z = torch.empty((PYR_ROWS * n, 9 * cout), device=t.device, dtype=torch.float32)
+    for j in range(4):
+        ops.conv_fwd(_pyr_view(acts, j, n), wp[:, :, j * cq:(j + 1) * cq, :], None, out=_pyr_view(z, j, n))
+    check(lib.runet_psp_taps_fwd(z.data_ptr(), 9 * cout, t.data_ptr(), ops.ld(t), n, h, w, cout, ops.stream()))
+    return t
+
+
+def psp_taps_backward(dt, acts, wp):
+    """dt [n, h, w, cout]: the gradient of the 3x3 convolution's output.  -> (dacts [50 n, cq], dwp shaped like wp)"""
+    n, h, w, cout = dt.shape
+    cq = acts.shape[1]
+    dev = dt.device
+    dz = torch.empty((PYR_ROWS * n, 9 * cout), device=dev, dtype=torch.float32)
+    ws = scratch(lib.runet_psp_taps_bwd_workspace_floats(n, h, w, cout), dev)
+    check(lib.runet_psp_taps_bwd(dt.data_ptr(), ops.ld(dt), dz.data_ptr(), 9 * cout, ws.data_ptr(), ws.numel(), n, h, w, cout, ops.stream()))
+    dacts = torch.empty((PYR_ROWS * n, cq), device=dev, dtype=torch.float32)
+    dwp = torch.empty_like(wp)
+    for j in range(4):
+        ops.conv_wgrad(_pyr_view(acts, j, n), _pyr_view(dz, j, n), 1, 1, out=dwp[:, :, j * cq:(j + 1) * cq, :])
+    # dP = dZ . Wtap^T is 100 K outputs behind a 9 cout deep contraction: a few tiles of the shared data gradient, each walking all of it
+    # (572 us for the four branches at the 16 x 256^2 workload); runet_psp_taps_dp splits the contraction by tap
+    ws = scratch(lib.runet_psp_taps_dp_workspace_floats(n, cq), dev)
+    check(lib.runet_psp_taps_dp(dz.data_ptr(), 9 * cout, wp.data_ptr(), 9 * cout, ws.data_ptr(), ws.numel(), dacts.data_ptr(), cq, n, cq, cout,
+                                ops.stream()))
+    return dacts, dwp
+
+
+def psp_head_forward(t, scale, shift, mask, w, b, fused=None):
+    """sigmoid(upsample16(conv1x1(dropout(relu(t * scale + shift))))) -> (prob [n, 1, 16 h, 16 w], saved).  t [n, h, w, c]: final_conv.0's raw
+    output, mask [n, c] or None, w: the 1x1 convolution's physical [1, 1, c, 1], b [1].  Fused: saved = None (the backward needs t and prob);
+    partner: saved = the activation [n, h, w, c]."""
+    n, h, wd, c = t.shape
+    if FUSED_PSP_HEAD if fused is None else fused:
+        z = torch.empty((n, h, wd), device=t.device, dtype=torch.float32)
+        check(lib.runet_psp_head_fwd(t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                     w.data_ptr(), b.data_ptr(), z.data_ptr(), n, h, wd, c, ops.stream()))
+        return up_sigmoid_forward(z, PSP_HEAD_SCALE), None
+    a = bn_apply(t, scale, shift, mask, relu=True)
+    _, logit = outc_forward(a, w, b, want_logit=True)
+    return up_sigmoid_forward(logit.view(n, h, wd), PSP_HEAD_SCALE), a
+
+
+def psp_head_backward(dprob, prob, t, scale, shift, mask, w, mean, invstd, saved=None, training=True):
+    """-> (dt [n, h, w, c], out [3c + 1] = (dgamma | dbeta | dw | db)); saved: what psp_head_forward returned (None = the fused path)"""
+    n, h, wd, c = t.shape
+    dev = t.device
+    st = ops.stream()
+    out = torch.empty(3 * c + 1, device=dev, dtype=torch.float32)
+    dz = up_sigmoid_backward(dprob, prob, PSP_HEAD_SCALE)
+    mp = mask.data_ptr() if mask is not None else None
+    if saved is None:
+        ws = scratch(lib.runet_psp_head_bwd_workspace_floats(n, h, wd, c), dev)
+        check(lib.runet_psp_head_bwd_reduce(dz.data_ptr(), t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), mp, w.data_ptr(), mean.data_ptr(),
+                                            invstd.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), n, h, wd, c, st))
+        use = out if training else zeros(2 * c, dev)
+        dt = ops.empty_nhwc(n, h, wd, c, t)
+        check(lib.runet_psp_head_bwd_apply(dz.data_ptr(), t.data_ptr(), ops.ld(t), mp, w.data_ptr(), dt.data_ptr(), ops.ld(dt), n, h, wd, c, mean.data_ptr(),
+                                           invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), use.data_ptr(), 0, st))
+        return dt, out
+    da = ops.empty_nhwc(n, h, wd, c, t)
+    check(lib.runet_outc_bwd(dz.data_ptr(), None, saved.data_ptr(), ops.ld(saved), w.data_ptr(), da.data_ptr(), ops.ld(da), _ws(n, h * wd, c, dev).data_ptr(),
+                             out[2 * c:].data_ptr(), n * h * wd, c, st))
+    dt = bn_backward(da, t, mean, invstd, scale, out[:2 * c], mask=mask, relu_shift=shift, out=da, training=training)
+    return dt, out

@@ -850,6 +850,48 @@ long runet_enet_head_bwd_workspace_floats(int n_img, int h, int w_, int c);
 int runet_enet_head_bwd(const float* dprob, const float* prob, const float* x, int ldx, const float* w, float* dx, int lddx, float* workspace,
                         long workspace_floats, float* dw_db, int n_img, int h, int w_, int c, void* stream);
 
+/* ---- PSPNet baseline (comne.py:214-299; csrc/pspnet.hip).  Its stride-2 convolutions (runet_conv2d_general), the pyramid's pooling, 1x1
+ *      convolutions and BatchNorms (runet_pyramid_pool_*, Fast-SCNN's entries at c = 512), the 3x3 convolution, the one-channel resize +
+ *      sigmoid (runet_up_sigmoid_*) and the unfused A/B partners (runet_pyramid_upsample_*, runet_bn_apply, runet_outc_*) are shared.  fp32,
+ *      NHWC, pixel strides multiples of 4 floats that cover the channels, tensors 16-byte aligned.  No float atomics: every sum has a fixed
+ *      order, results are bitwise reproducible.  Source-index rule: runet_pyramid_upsample_fwd's (ATen align_corners=False, scale = b / size).
+ * Tap planes: the pyramid half of final_conv.0 (:240 torch.cat + :279 Conv2d(1024, 512, 3, padding=1)) computed on the 50 cells per image.
+ *   z [50 n][9 cout] (row stride ldz >= 9 cout) holds, branch-major like runet_pyramid_pool_fwd's rows, Z_j[n][cy][cx][r][s][0:cout] =
+ *   P_j[n][cy][cx][:] . W[r][s][512 + 128 j : 512 + 128 (j + 1)][:]: a cell's activations times the nine taps' weight rows of its branch.
+ *   runet_psp_taps_fwd: t [n, h, w_, 0:cout] (ldt; may be a channel slice, the neighbouring channels are not touched) += sum_j sum_(r, s)
+ *     bilinear_(h, w_)(Z_j[..][r][s][:]) at (y + r - 1, x + s - 1), zero where that lies outside the map (the concat's zero padding).  Rows
+ *     first (into LDS), then columns.
+ *   runet_psp_taps_bwd: dz [50 n][9 cout] (lddz) = the adjoint in gather form of dt [n, h, w_, 0:cout] (lddt): columns first (into the
+ *     workspace, >= runet_psp_taps_bwd_workspace_floats = n h 36 cout floats; -1: bad shape), then rows; one owner per element.
+ *   runet_psp_taps_dp: da [50 n][cq] (lda) = the cells' gradient dP_j = dZ_j . Wtap_j^T of all four branches, dz as runet_psp_taps_bwd wrote it,
+ *     wp [4 cq][9 cout] (row stride ldw) the pyramid rows of the weight with the input channel outermost (row j cq + k = branch j, channel k).
+ *     The 9 cout deep contraction is split by tap (partials in the workspace, >= runet_psp_taps_dp_workspace_floats = 9 * 50 n cq floats;
+ *     -1: bad shape) and summed in tap order; cq a multiple of 4 up to 256.
+ * Head: final_conv.1-4 (:280-283 BatchNorm2d, ReLU, Dropout2d, Conv2d(c, 1, 1)) on the 3x3 convolution's raw output t [n, h, w_, c] (ldt);
+ *   mask_nc [n][c] = the Dropout2d keep-mask / (1 - p), NULL in eval mode; c a multiple of 4 up to 1024.
+ *   runet_psp_head_fwd: z [n, h, w_] = b[0] + sum_c w[c] * mask_nc[n][c] * relu(t * scale[c] + shift[c]); the activated tensor is not written.
+ *   runet_psp_head_bwd_reduce: one pass over t and dz [n, h, w_] -> out [3c + 1] = (dgamma [c] | dbeta [c] | dw [c] | db): the BatchNorm sums
+ *     (sum g * xhat | sum g) of g = dz * w[c] * mask_nc[n][c] * (t * scale + shift > 0), dw[c] = sum dz * mask_nc * relu(t * scale + shift),
+ *     db = sum dz.  workspace >= runet_psp_head_bwd_workspace_floats floats (-1: bad shape).
+ *   runet_psp_head_bwd_apply: dt [n, h, w_, c] (lddt) by runet_bn_bwd_apply's formula with g recomputed; sums = out[0 : 2c] of the reduce (or
+ *     zeros in eval mode, where dt = g * scale), m_total as there (0: the local pixel count). */
+int runet_psp_taps_fwd(const float* z, int ldz, float* t, int ldt, int n_img, int h, int w_, int cout, void* stream);
+long runet_psp_taps_bwd_workspace_floats(int n_img, int h, int w_, int cout);
+int runet_psp_taps_bwd(const float* dt, int lddt, float* dz, int lddz, float* workspace, long workspace_floats, int n_img, int h, int w_, int cout,
+                       void* stream);
+long runet_psp_taps_dp_workspace_floats(int n_img, int cq);
+int runet_psp_taps_dp(const float* dz, int lddz, const float* wp, int ldw, float* workspace, long workspace_floats, float* da, int lda, int n_img,
+                      int cq, int cout, void* stream);
+int runet_psp_head_fwd(const float* t, int ldt, const float* scale, const float* shift, const float* mask_nc, const float* w, const float* b, float* z,
+                       int n_img, int h, int w_, int c, void* stream);
+long runet_psp_head_bwd_workspace_floats(int n_img, int h, int w_, int c);
+int runet_psp_head_bwd_reduce(const float* dz, const float* t, int ldt, const float* scale, const float* shift, const float* mask_nc, const float* w,
+                              const float* mean, const float* invstd, float* workspace, long workspace_floats, float* out, int n_img, int h, int w_,
+                              int c, void* stream);
+int runet_psp_head_bwd_apply(const float* dz, const float* t, int ldt, const float* mask_nc, const float* w, float* dt, int lddt, int n_img, int h,
+                             int w_, int c, const float* mean, const float* invstd, const float* scale, const float* shift, const float* sums,
+                             long m_total, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
