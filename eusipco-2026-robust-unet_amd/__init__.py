@@ -13,6 +13,8 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   ENet with InitialBlock and BottleneckBlock (comne.py's asymmetric / dilated bottleneck baseline);
   PSPNet with PyramidPooling (comne.py's pyramid-pooling baseline);
   CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling)
+  enhance_scene, convert_scene, band_percentiles, select_bands, percentile_ranks (scene.py: the multi-band raster -> uint8 RGB step of
+  tif_to_image.py / predict_coastline.py on the device: exact 2-98 % percentiles and the float64 stretch)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
 Sub-modules are imported lazily so that host-only pieces (data, portable_rng) stay usable
@@ -44,6 +46,7 @@ _LAZY = {
     "GlobalFeatureExtractor": "fastscnn", "FeatureFusionModule": "fastscnn", "Classifier": "fastscnn",
     "ENet": "enet", "InitialBlock": "enet", "BottleneckBlock": "enet",
     "PSPNet": "pspnet", "PyramidPooling": "pspnet",
+    "enhance_scene": "scene", "convert_scene": "scene", "band_percentiles": "scene", "select_bands": "scene", "percentile_ranks": "scene",
 }
 
 

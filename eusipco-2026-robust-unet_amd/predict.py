@@ -14,7 +14,14 @@ Between the upload of the uint8 image and the single download of (water mask, co
 every output pixel is taken from exactly one tile's core (tile_plan), so there is no blending and the result is bit-deterministic.
 
 OpenCV is not a dependency.  Steps 3-5 restate OpenCV's rules (index rule, ellipse spans, Suzuki-Abe border following); vertex-for-vertex
-equality of the contours with cv2 is not claimed.  GDAL band handling, the matplotlib report, the GUI and the CLI are out of scope.
+equality of the contours with cv2 is not claimed.  The matplotlib report, the GUI and the CLI are out of scope.
+
+Multi-band rasters (load_tif_image, :425-581) come in through scene.py: `extract_coastline_from_image` and `predict_scene` take the raw
+bands - a [B, H, W] array or device tensor with B <= 6, a .npy path, or anything through `bands=` (a .tif path there is read with GDAL where
+it is installed; as `image` a .tif path stays what it was, an RGB file for PIL) - and run the reference's band selection, 2-98 % stretch
+and darkening on the device (runet_band_percentiles, runet_band_stretch_u8).  On the tiled path the enhanced scene never leaves the device:
+one upload (the raw bands), one download (the results).  On the resized path it is downloaded once, because the reference resizes the
+ENHANCED image with PIL's bilinear filter (:467, :387) and that order is kept.  GDAL itself is not a dependency.
 """
 from __future__ import annotations
 
@@ -27,7 +34,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import data, ops
+from . import data, ops, scene as _scene
 from ._lib import check, lib
 
 MAX_DILATION = 31
@@ -276,6 +283,23 @@ def _load_rgb(image):
     return Image.fromarray(np.ascontiguousarray(a)), None
 
 
+def _as_bands(image, bands):
+    """The rule that tells a band raster from an RGB image.  -> the raster input, or None for an image.  A raster is: whatever comes through
+    `bands=`; a .npy path; a numpy array or tensor with ndim == 3 and shape[0] <= 6 that is not a uint8 [H, W, 3] image (a uint8 array whose
+    last axis is 3 stays an image, as before: pass such a raster through `bands=`).  Every other path, .tif included, is an image file for
+    PIL, as before: a multi-band .tif goes through `bands=` (and needs GDAL)."""
+    if bands is not None:
+        if image is not None:
+            raise ValueError("pass either an image or bands=, not both")
+        return bands
+    if isinstance(image, (str, os.PathLike)):
+        return image if os.path.splitext(os.fspath(image))[1].lower() == ".npy" else None
+    if isinstance(image, (np.ndarray, torch.Tensor)) and image.ndim == 3 and image.shape[0] <= _scene.MAX_BANDS:
+        is_u8 = image.dtype == (torch.uint8 if isinstance(image, torch.Tensor) else np.uint8)
+        return None if is_u8 and image.shape[2] == 3 else image
+    return None
+
+
 def save_extraction_result(result, output_dir):
     """predict_coastline.py:620-652 without the matplotlib report: <base>_water_mask.png, <base>_coastline_mask.png (* 255) and
     <base>_coastlines.json with the reference's keys."""
@@ -288,6 +312,11 @@ def save_extraction_result(result, output_dir):
            "extraction_time": result["extraction_time"]}
     with open(os.path.join(output_dir, f"{base}_coastlines.json"), "w", encoding="utf-8") as fh:
         json.dump(doc, fh, indent=2, ensure_ascii=False)
+
+
+def _raise_nonfinite(count):
+    if count:
+        raise ValueError(f"the selected bands hold {count} non-finite values: mask them (nodata) before the stretch")
 
 
 class CoastlineExtractor:
@@ -337,9 +366,24 @@ class CoastlineExtractor:
             argmax_stitch(self._z4(scene_to_tiles(scene, o, tile)), o, halo, mask, self.model.n_classes)
         return mask
 
-    def predict_scene(self, image, tile=512, halo=64, batch=8, as_tensor=False):
+    def predict_scene(self, image=None, tile=512, halo=64, batch=8, as_tensor=False, bands=None, mode="water"):
         """Water mask at the scene's own resolution, no resize: tiles of side `tile` whose cores (tile - 2 * halo) partition the scene, `batch`
-        tiles per network call.  Each pixel comes from exactly one core.  Beyond the scene the tiles read 0.0 (normalised units)."""
+        tiles per network call.  Each pixel comes from exactly one core.  Beyond the scene the tiles read 0.0 (normalised units).
+        A band raster (_as_bands) is enhanced on the device first (scene.py, `mode`) and goes straight into the tiles."""
+        raster = _as_bands(image, bands)
+        if raster is not None:
+            r = _scene.load_raster(raster, self.device)
+            scene, nonfinite = _scene._enhance(r, mode)
+            if as_tensor:
+                return self._predict_tiled(scene, tile, halo, batch)
+            # water mask | non-finite count: one download
+            seg = (r.h * r.w + 15) // 16 * 16
+            buf = torch.empty(seg + 16, device=self.device, dtype=torch.uint8)
+            self._predict_tiled(scene, tile, halo, batch, out=buf[:r.h * r.w].view(r.h, r.w))
+            buf[seg:seg + 4].view(torch.int32).copy_(nonfinite)
+            host = buf.cpu().numpy()
+            _raise_nonfinite(int(host[seg:seg + 4].view(np.int32)[0]))
+            return host[:r.h * r.w].reshape(r.h, r.w).copy()
         pil, _ = _load_rgb(image)
         scene = _dev_u8(np.array(pil, dtype=np.uint8), self.device)
         mask = self._predict_tiled(scene, tile, halo, batch)
@@ -353,21 +397,42 @@ class CoastlineExtractor:
         coast = coast.cpu().numpy()
         return coastlines_from_mask(coast), coast
 
-    def extract_coastline_from_image(self, image, output_dir=None, dilation_size=5, tiled=False, tile=512, halo=64, batch=8):
+    def extract_coastline_from_image(self, image=None, output_dir=None, dilation_size=5, tiled=False, tile=512, halo=64, batch=8, bands=None,
+                                     mode="water"):
+        """predict_coastline.py:366-423.  `image`: a path, a PIL image or a uint8 [H, W, 3] array as before, or a band raster (_as_bands),
+        which is enhanced on the device (scene.py, `mode`): tiled, the enhanced scene feeds the tiles directly; resized, it is downloaded
+        once for the PIL bilinear resize, the reference's order."""
         ellipse_spans(dilation_size)
-        pil, path = _load_rgb(image)
-        w, h = pil.size
+        raster = _as_bands(image, bands)
+        scene = nonfinite = None
+        if raster is not None:
+            r = _scene.load_raster(raster, self.device)
+            path = r.meta.get("path")
+            if tiled:
+                scene, nonfinite = _scene._enhance(r, mode)
+                pil, (w, h) = None, (r.w, r.h)
+            else:
+                pil = Image.fromarray(_scene.enhance_scene(r, mode))
+                w, h = pil.size
+        else:
+            pil, path = _load_rgb(image)
+            w, h = pil.size
         # one device buffer for everything that goes back: water mask | coastline mask | the two counts -> one download
         seg = (h * w + 15) // 16 * 16
         buf = torch.empty(2 * seg + 16, device=self.device, dtype=torch.uint8)
         water, coast = buf[:h * w].view(h, w), buf[seg:seg + h * w].view(h, w)
         counts = buf[2 * seg:2 * seg + 8].view(torch.int32)
-        if tiled:
+        if scene is not None:
+            self._predict_tiled(scene, tile, halo, batch, out=water)
+            buf[2 * seg + 8:2 * seg + 12].view(torch.int32).copy_(nonfinite)
+        elif tiled:
             self._predict_tiled(_dev_u8(np.array(pil, dtype=np.uint8), self.device), tile, halo, batch, out=water)
         else:
             self._predict_resized(pil, out=water)
         dilate_diff(water, dilation_size, coast=coast, counts=counts)
         host = buf.cpu().numpy()
+        if scene is not None:
+            _raise_nonfinite(int(host[2 * seg + 8:2 * seg + 12].view(np.int32)[0]))
         water_np = host[:h * w].reshape(h, w).copy()
         coast_np = host[seg:seg + h * w].reshape(h, w).copy()
         n_water, n_coast = (int(v) for v in host[2 * seg:2 * seg + 8].view(np.int32))

@@ -892,6 +892,44 @@ int runet_psp_head_bwd_apply(const float* dz, const float* t, int ldt, const flo
                              int w_, int c, const float* mean, const float* invstd, const float* scale, const float* shift, const float* sums,
                              long m_total, void* stream);
 
+/* ---- scene ingestion: the multi-band raster in front of the predictor (tif_to_image.py:42-171, train_water_segmentation.py:103-174,
+ *      predict_coastline.py:425-581; csrc/scene_bands.hip).  bands is a planar device raster [n_bands][h][w] as GDAL's ReadAsArray stack gives
+ *      it, dtype one of RUNET_BAND_*, read through band_stride / row_stride / elem_stride IN ELEMENTS (a row or column window of a larger raster
+ *      needs no copy; strides must be positive and cover the extent), aligned to its element size, h * w < 2^31.  sel0..2 name the planes.
+ * runet_band_percentiles: np.percentile(band, [q_lo, q_hi]) (method "linear") of the first n_sel (1..3) selected planes -> pct, device float64
+ *   [n_sel][2].  The HOST computes numpy's ranks and weights, vi = (n - 1) * (q / 100), k = floor(vi), g = vi - k, and passes k_lo, g_lo, k_hi,
+ *   g_hi; the device finds the exact order statistics of ranks k and min(k + 1, n - 1) (radix select on an order-preserving key, integer
+ *   atomics only: bits do not depend on arrival order) and interpolates by numpy's _lerp in float64 without contraction: a + (b - a) * g,
+ *   replaced by b - (b - a) * (1 - g) where g >= 0.5.  b - a is taken as numpy takes it, in the band's own dtype (int16 wraps, float32
+ *   rounds); wide_diff != 0 takes it in float64 instead, which is np.percentile of band.astype(float64) (normalize_image_for_display).
+ *   -0.0 and +0.0 are one value (+0.0).  float32: nonfinite (device int32 [1], cleared by the call, 0 for the other dtypes) counts the NaNs
+ *   and infinities of the selected planes; the percentiles of such a plane are unspecified.  workspace: device memory of at least
+ *   runet_band_percentiles_workspace(n_sel) BYTES (host only, -1: bad n_sel), 8-byte aligned, cleared by the call.  No host synchronisation.
+ * runet_band_stretch_u8: out, interleaved uint8 [h][w][3] with out_row_stride bytes per row (any address phase), from the three selected
+ *   planes and pct [3][2]; per pixel, in float64, true division, no contraction:
+ *     s = min(max((double(v) - p_lo) / (p_hi - p_lo) * 255, 0), 255)
+ *   mode 0 "water" (enhance_image_for_water, enhance_image(enhance_water=True)): channel 0 only, s < 100 -> s * 0.7;  mode 1 "rgb"
+ *   (enhance_image(enhance_water=False)): nothing more;  mode 2 "display" (normalize_image_for_display): a channel whose p_hi - p_lo > 0 does
+ *   not hold takes s = min(max(double(v), 0), 255).  The cast follows the reference's detour through the input dtype: integer inputs truncate
+ *   s toward zero, float32 input rounds s to float32 first and truncates that.  A constant band in modes 0 / 1 divides by zero, which the
+ *   reference leaves to an undefined float -> integer cast; here a NaN quotient (0 / 0, or a NaN input) writes 0, +inf writes 255 and -inf 0.
+ * Both validate on the host and return non-zero before any device work.
+ * runet_band_percentiles_timed: MEASUREMENT ONLY (tools/bench_scene.py) - the same call with a device event around every selection pass (one
+ *   counting launch + one scan launch); it synchronises the host and writes the passes' milliseconds to the HOST array pass_ms [4]. */
+#define RUNET_BAND_U8 0
+#define RUNET_BAND_U16 1
+#define RUNET_BAND_I16 2
+#define RUNET_BAND_F32 3
+long runet_band_percentiles_workspace(int n_sel);
+int runet_band_percentiles(const void* bands, int dtype, int n_bands, int h, int w, long band_stride, long row_stride, long elem_stride, int sel0,
+                           int sel1, int sel2, int n_sel, long k_lo, double g_lo, long k_hi, double g_hi, int wide_diff, double* pct,
+                           int* nonfinite, void* workspace, long workspace_bytes, void* stream);
+int runet_band_percentiles_timed(const void* bands, int dtype, int n_bands, int h, int w, long band_stride, long row_stride, long elem_stride,
+                                 int sel0, int sel1, int sel2, int n_sel, long k_lo, double g_lo, long k_hi, double g_hi, int wide_diff,
+                                 double* pct, int* nonfinite, void* workspace, long workspace_bytes, void* stream, float* pass_ms);
+int runet_band_stretch_u8(const void* bands, int dtype, int n_bands, int h, int w, long band_stride, long row_stride, long elem_stride, int sel0,
+                          int sel1, int sel2, const double* pct, int mode, unsigned char* out, long out_row_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
