@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
                 float a, b;
                 bn_bwd_coef(psc[q], pre.mean[c + q], pre.invstd[c + q], pre.sums[c + q], pre.sums[C + c + q], pre.inv_m, a, b);
                 pca[q] = a; pcb[q] = b;
+                if (pfa[q] == 0.f) psh[q] = -INFINITY;      // a dropped plane: g = +0, as bn_bwd_apply_kernel takes it (same bits)
             }
         }
     }

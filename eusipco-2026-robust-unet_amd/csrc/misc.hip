@@ -257,6 +257,8 @@ __global__ __launch_bounds__(TPB) void seg_counts_kernel(const float* __restrict
 extern "C" int runet_maxpool2_fwd(const float* x, int ldx, float* y, int ldy, unsigned char* idx, int n_img, int h, int w, int c, void* stream) {
     RUNET_REQUIRE(x && y && idx, "null pointer");
     RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && ldx >= c && ldy >= c && ldx % 4 == 0 && ldy % 4 == 0, "bad shape");
+    RUNET_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
     hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, idx, n_img, h / 2, w / 2, c);
     RUNET_CHECK_LAUNCH();
@@ -266,6 +268,8 @@ extern "C" int runet_maxpool2_bwd(const float* dy, int lddy, const unsigned char
                                   int accumulate, void* stream) {
     RUNET_REQUIRE(dy && dx && idx, "null pointer");
     RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && c > 0, "h, w must be even and c a multiple of 4");
+    RUNET_REQUIRE(n_img > 0 && h > 0 && w > 0 && lddy >= c && lddx >= c && lddy % 4 == 0 && lddx % 4 == 0, "bad shape");
+    RUNET_REQUIRE(((uintptr_t)dy % 16) == 0 && ((uintptr_t)dx % 16) == 0 && ((uintptr_t)idx % 4) == 0, "alignment");
     const long total = (long)n_img * (h / 2) * (w / 2) * (c / 4);
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total, 4096)), dim3(TPB), 0, (hipStream_t)stream, dy, lddy, idx, dx, lddx, n_img, h / 2, w / 2, c, accumulate);
     RUNET_CHECK_LAUNCH();

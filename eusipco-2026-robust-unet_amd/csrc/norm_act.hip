@@ -407,6 +407,10 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_partial(const float* __rest
         if constexpr (ACT != ACT_RELU) mk[q] = 1.f;
         else mk[q] = (ok && mask) ? mask[(long)n * C + c] : 1.f;
         fs[q] = (ok && recompute) ? rscale[c] : 0.f; fh[q] = (ok && recompute) ? rshift[c] : 0.f;
+        // A dropped plane (mask 0) saved act = 0, so the act form takes g = +0 there; recomputed, z > 0 would give dy * 0 = +-0.  A shift of
+        // -inf makes the recomputed decision false as well, so both forms give the same bits (the sign of a zero reaches dx where the channel
+        // is dropped in every image: its sums, hence ca and cb, are zero).  Costs nothing per element.
+        if constexpr (ACT == ACT_RELU) if (mk[q] == 0.f) fh[q] = -INFINITY;
     }
     if (row < rows) {
         const long ib = (long)n * HW;
@@ -500,6 +504,7 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(const float* __restri
         if constexpr (ACT != ACT_RELU) mk[q] = 1.f;
         else mk[q] = mask ? mask[(long)n * C + c] : 1.f;
         fh[q] = recompute ? rshift[c] : 0.f;
+        if constexpr (ACT == ACT_RELU) if (mk[q] == 0.f) fh[q] = -INFINITY;      // a dropped plane: g = +0 as in the act form (see the reduce)
     }
     const long ib = (long)n * HW;
     for (int p = p0 + row; p < p1; p += rows) {
@@ -759,6 +764,7 @@ extern "C" int runet_bn_bwd_reduce(const float* dy, int lddy, const float* x, in
     RUNET_REQUIRE(dy && x && mean && invstd && workspace && sums, "null pointer");
     RUNET_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr) && !(act && relu_scale), "give either act or relu_scale + relu_shift");
     REQ_VEC(c);
+    RUNET_REQUIRE(n_img > 0 && hw > 0 && lddy >= c && ldx >= c && (!act || ldact >= c), "bad shape");
     launch_bn_bwd_reduce<false, ACT_RELU>(dy, lddy, x, ldx, act, ldact, n_img, hw, c, mean, invstd, mask_nc, workspace, sums, relu_scale, relu_shift, stream);
     RUNET_CHECK_LAUNCH();
 }
@@ -769,6 +775,7 @@ extern "C" int runet_bn_bwd_apply(const float* dy, int lddy, const float* x, int
                                   void* stream) {
     RUNET_REQUIRE(dy && x && dx && mean && invstd && scale && sums && !(act && relu_shift), "null pointer / both act and relu_shift");
     REQ_VEC(c);
+    RUNET_REQUIRE(pixels > 0 && hw > 0 && lddy >= c && ldx >= c && lddx >= c && (!act || ldact >= c), "bad shape");
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
     launch_bn_bwd_apply<false, ACT_RELU>(dy, lddy, x, ldx, act, ldact, dx, lddx, pixels, hw, c, mean, invstd, scale, sums, mask_nc, m_total, relu_shift, stream);
     RUNET_CHECK_LAUNCH();

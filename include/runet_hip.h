@@ -130,7 +130,7 @@ int runet_bn_apply(const float* x, int ldx, float* y, int ldy, long pixels, int 
                    const float* mask_nc, int relu, void* stream);
 
 /* g = dy, or dy*mask_nc[n,c]*(act > 0) when act != NULL (act = saved output of relu/dropout), or - relu_scale/relu_shift given, act NULL -
- * dy*mask_nc[n,c]*(x*relu_scale[c] + relu_shift[c] > 0): the forward's affine recomputed from x, one tensor less to read.
+ * dy*mask_nc[n,c]*(x*relu_scale[c] + relu_shift[c] > 0): the forward's affine recomputed from x, one tensor less to read.  Both forms give the same bits: where mask_nc[n,c] is 0, g is +0 in either.
  * sums[0:c] = sum g*xhat (= dgamma), sums[c:2c] = sum g (= dbeta): the order of (weight, bias). */
 int runet_bn_bwd_reduce(const float* dy, int lddy, const float* x, int ldx, const float* act, int ldact, int n_img, int hw, int c,
                         const float* mean, const float* invstd, const float* mask_nc, float* workspace, float* sums, const float* relu_scale,
