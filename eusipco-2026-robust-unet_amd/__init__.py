@@ -12,7 +12,8 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   GlobalFeatureExtractor, FeatureFusionModule and Classifier (comne.py's depthwise-separable baseline);
   ENet with InitialBlock and BottleneckBlock (comne.py's asymmetric / dilated bottleneck baseline);
   PSPNet with PyramidPooling (comne.py's pyramid-pooling baseline);
-  CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling)
+  CoastlineExtractor (predict_coastline.py's predictor: device post-processing, native-resolution tiling) and
+  trace_external_contours_device (its cv2.findContours step as parallel border following on the device)
   enhance_scene, convert_scene, band_percentiles, select_bands, percentile_ranks (scene.py: the multi-band raster -> uint8 RGB step of
   tif_to_image.py / predict_coastline.py on the device: exact 2-98 % percentiles and the float64 stretch)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
@@ -47,6 +48,7 @@ _LAZY = {
     "ENet": "enet", "InitialBlock": "enet", "BottleneckBlock": "enet",
     "PSPNet": "pspnet", "PyramidPooling": "pspnet",
     "enhance_scene": "scene", "convert_scene": "scene", "band_percentiles": "scene", "select_bands": "scene", "percentile_ranks": "scene",
+    "trace_external_contours_device": "predict",
 }
 
 

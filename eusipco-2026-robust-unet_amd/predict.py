@@ -5,11 +5,12 @@ Reference pipeline, one image at a time (line numbers of predict_coastline.py):
   2. :390-392        UNet(3, 2).eval(), argmax(logits, dim=1)                                 unet_forward(nhwc=True), runet_argmax_stitch
   3. :395-396        cv2.resize(pred, (W, H), INTER_NEAREST)                                  runet_resize_nearest_u8
   4. :595-602        MORPH_ELLIPSE k x k, cv2.dilate, dilated - mask                          runet_dilate_diff_u8 (+ the two pixel counts)
-  5. :605-616        cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), > 10 points,       host: trace_external_contours, approx_poly_dp
-                     approxPolyDP(0.002 * arcLength)
+  5. :605-616        cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), > 10 points,       runet_contours_count / runet_contours_trace (device
+                     approxPolyDP(0.002 * arcLength)                                          masks; host: trace_external_contours), host approx_poly_dp
   6. :404-413, :620-652  result dict, two PNG masks (* 255), <base>_coastlines.json           save_extraction_result
 
-Between the upload of the uint8 image and the single download of (water mask, coastline mask, counts) nothing returns to the host.
+Between the upload of the uint8 image and the single download of (water mask, coastline mask, counts, packed contours) nothing returns to
+the host but the two size words the contour tracing needs to allocate (its state count, then its contour and vertex counts).
 `predict_scene` is the addition for scenes larger than one network input: the scene is cut into overlapping tiles at its own resolution and
 every output pixel is taken from exactly one tile's core (tile_plan), so there is no blending and the result is bit-deterministic.
 
@@ -38,6 +39,9 @@ from . import data, ops, scene as _scene
 from ._lib import check, lib
 
 MAX_DILATION = 31
+# RUNET_NO_DEVICE_CONTOURS=1: masks that live on the device are downloaded and traced by the host loop (trace_external_contours) as before.
+# Consulted at every call; the results are identical either way.
+DEVICE_CONTOURS = os.environ.get("RUNET_NO_DEVICE_CONTOURS", "0") != "1"
 
 
 # ------------------------------------------------------------------------------------------------ host-side plans
@@ -208,6 +212,53 @@ def trace_external_contours(mask):
     return contours
 
 
+# ------------------------------------------------------------------------------------------------ contours (device)
+def _trace_packed(mask, min_points=0):
+    """mask: device uint8 [h, w] -> device int32 tensor {n, total, offsets [n + 1], points [total][2]} (csrc/contours.hip), or None for a
+    mask without a set pixel.  Two small downloads: the state count, then (n, total) to cut the packed result to its length."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.ndim != 2 or not mask.is_cuda:
+        raise ValueError("expected a 2-D uint8 device tensor")
+    if min_points < 0:
+        raise ValueError("min_points must not be negative")
+    mask = mask.contiguous()
+    h, w = mask.shape
+    if h == 0 or w == 0:
+        return None
+    nbytes = lib.runet_contours_workspace_bytes(h, w)
+    if nbytes < 0:
+        raise ValueError(f"a {h} x {w} mask is too large for the device tracer (h * w must stay below 2^31)")
+    ws = torch.empty(nbytes, device=mask.device, dtype=torch.uint8)
+    count = torch.empty(1, device=mask.device, dtype=torch.int64)
+    check(lib.runet_contours_count(mask.data_ptr(), h, w, ws.data_ptr(), nbytes, count.data_ptr(), ops.stream()))
+    n_states = int(count.cpu()[0])                                                     # download 1
+    if n_states == 0:
+        return None
+    sbytes = lib.runet_contours_state_workspace_bytes(n_states)
+    if sbytes < 0:
+        raise ValueError(f"{n_states} border states do not fit int32")
+    sws = torch.empty(sbytes, device=mask.device, dtype=torch.uint8)
+    check(lib.runet_contours_trace(h, w, ws.data_ptr(), nbytes, n_states, int(min_points), sws.data_ptr(), sbytes, ops.stream()))
+    n, total = (int(v) for v in sws[:8].view(torch.int32).cpu())                       # download 2
+    return sws[:4 * (3 + n + 2 * total)].view(torch.int32)
+
+
+def _unpack_contours(packed):
+    """host int32 {n, total, offsets [n + 1], points [total][2]} -> list of int32 [k, 2] arrays"""
+    packed = np.asarray(packed, dtype=np.int32)
+    n, total = int(packed[0]), int(packed[1])
+    off = packed[2:3 + n]
+    pts = packed[3 + n:3 + n + 2 * total].reshape(total, 2)
+    return [pts[off[i]:off[i + 1]].copy() for i in range(n)]
+
+
+def trace_external_contours_device(mask, min_points=0):
+    """trace_external_contours(mask.cpu().numpy()) computed on the device (runet_contours_count / runet_contours_trace), the same arrays in the
+    same order; min_points > 0 also drops the contours with <= min_points vertices there (the reference's filter is 10).  The mask stays on
+    the device: three downloads, two size words and the packed vertices."""
+    packed = _trace_packed(mask, min_points)
+    return [] if packed is None else _unpack_contours(packed.cpu().numpy())            # download 3
+
+
 def arc_length(points, closed=True):
     p = np.asarray(points, dtype=np.float64).reshape(-1, 2)
     if len(p) < 2:
@@ -261,13 +312,19 @@ def approx_poly_dp(points, eps, closed=True):
     return np.asarray(points, dtype=np.int32).reshape(-1, 2)[idx]
 
 
+def _simplify(contours, min_points, eps_factor):
+    return [approx_poly_dp(c, eps_factor * arc_length(c, True), True).tolist() for c in contours if len(c) > min_points]
+
+
 def coastlines_from_mask(coastline_mask, min_points=10, eps_factor=0.002):
-    """predict_coastline.py:605-616 -> list of [[x, y], ...]"""
-    out = []
-    for c in trace_external_contours(coastline_mask):
-        if len(c) > min_points:
-            out.append(approx_poly_dp(c, eps_factor * arc_length(c, True), True).tolist())
-    return out
+    """predict_coastline.py:605-616 -> list of [[x, y], ...].  A device tensor is traced and length-filtered on the device and its packed
+    vertices downloaded once (DEVICE_CONTOURS off: the mask is downloaded and traced on the host); arc length and Douglas-Peucker stay on
+    the host in float64 either way, so the lists are the same."""
+    if isinstance(coastline_mask, torch.Tensor):
+        if coastline_mask.is_cuda and DEVICE_CONTOURS:
+            return _simplify(trace_external_contours_device(coastline_mask, min_points), min_points, eps_factor)
+        coastline_mask = coastline_mask.cpu().numpy()
+    return _simplify(trace_external_contours(coastline_mask), min_points, eps_factor)
 
 
 # ------------------------------------------------------------------------------------------------ the extractor
@@ -394,8 +451,15 @@ class CoastlineExtractor:
         """-> (coastlines, coastline_mask) as predict_coastline.py:583-618; water_mask: numpy array or device tensor, uint8."""
         mask = _dev_u8(water_mask, self.device)
         coast, _, _ = dilate_diff(mask, dilation_kernel_size)
-        coast = coast.cpu().numpy()
-        return coastlines_from_mask(coast), coast
+        if not (coast.is_cuda and DEVICE_CONTOURS):
+            coast = coast.cpu().numpy()
+            return coastlines_from_mask(coast), coast
+        # trace before the download; packed contours | coastline mask -> one download
+        packed = _trace_packed(coast, 10)
+        head = 0 if packed is None else 4 * packed.numel()
+        host = (coast.view(-1) if packed is None else torch.cat([packed.view(torch.uint8), coast.view(-1)])).cpu().numpy()
+        contours = [] if packed is None else _unpack_contours(host[:head].view(np.int32))
+        return _simplify(contours, 10, 0.002), host[head:].reshape(coast.shape).copy()
 
     def extract_coastline_from_image(self, image=None, output_dir=None, dilation_size=5, tiled=False, tile=512, halo=64, batch=8, bands=None,
                                      mode="water"):
@@ -430,13 +494,21 @@ class CoastlineExtractor:
         else:
             self._predict_resized(pil, out=water)
         dilate_diff(water, dilation_size, coast=coast, counts=counts)
+        on_device = coast.is_cuda and DEVICE_CONTOURS
+        packed = _trace_packed(coast, 10) if on_device else None
+        if packed is not None:                           # the packed contours ride along in the one download
+            buf = torch.cat([buf, packed.view(torch.uint8)])
         host = buf.cpu().numpy()
         if scene is not None:
             _raise_nonfinite(int(host[2 * seg + 8:2 * seg + 12].view(np.int32)[0]))
         water_np = host[:h * w].reshape(h, w).copy()
         coast_np = host[seg:seg + h * w].reshape(h, w).copy()
         n_water, n_coast = (int(v) for v in host[2 * seg:2 * seg + 8].view(np.int32))
-        coastlines = coastlines_from_mask(coast_np)
+        if on_device:
+            contours = [] if packed is None else _unpack_contours(host[2 * seg + 16:].view(np.int32))
+            coastlines = _simplify(contours, 10, 0.002)
+        else:
+            coastlines = coastlines_from_mask(coast_np)
         result = {"image_path": path if path is not None else "image", "image_size": (w, h), "water_mask": water_np,
                   "coastline_mask": coast_np, "coastlines": coastlines, "coastline_count": len(coastlines), "dilation_size": int(dilation_size),
                   "extraction_time": str(datetime.now()), "water_pixels": n_water, "coastline_pixels": n_coast}

@@ -784,6 +784,40 @@ int runet_resize_nearest_u8(const unsigned char* src, int sh, int sw, unsigned c
 int runet_dilate_diff_u8(const unsigned char* mask, int h, int w, int k, unsigned char* coast, unsigned char* dilated, int* counts2,
                          void* stream);
 
+/* ---- prediction: the contours of the coastline mask (predict_coastline.py:605-608: cv2.findContours(coastline_mask, RETR_EXTERNAL,
+ *      CHAIN_APPROX_SIMPLE) and the `len(contour) > 10` filter) on the device, as parallel border following (csrc/contours.hip).  It replaces
+ *      the host loop predict.trace_external_contours and returns its arrays: the outer border of every top-level component, in raster order of
+ *      their start pixels, from the same first vertex, in the same order, collinear runs reduced the same way.  mask: dense uint8 [h][w], any
+ *      non-zero byte is set, any address alignment, h * w < 2^31; it is only read and never goes to the host.
+ * Formulation.  Directions d = 0..7 are E, NE, N, NW, W, SW, S, SE (y grows downwards).  Foreground is 8-connected, background 4-connected,
+ *   outside the image is background.  A STATE (p, d) is a set pixel p whose neighbour in direction d is set ("at p, having come from there");
+ *   its SUCCESSOR scans e = d + 1, d + 2, ... (mod 8) to the first set neighbour q of p and is (q, (e + 4) % 8); p is LEFT in direction e.  On
+ *   the valid states this map is a bijection, so the states fall into disjoint cycles, one per border (outer or hole).  States exist only on
+ *   pixels with a clear 4-neighbour (every border pixel is one; a spare state whose successor leaves them is its own successor), an isolated
+ *   pixel carries one state that is its own successor.  START: (p0, d1) opens a contour iff p0's west neighbour is clear and 4-connected to
+ *   the outside of the zero-padded image (the component is top-level), d1 is the first set neighbour of p0 clockwise from west (W, NW, N, NE,
+ *   E, SE, S, SW) and p0 is the smallest pixel index of its cycle.  VERTEX: the pixel of state (p, d) is kept iff e != (d + 4) % 8, i.e. it is
+ *   left in another direction than the previous pixel was; an isolated pixel is a one-vertex contour.  min_points > 0 drops every contour with
+ *   <= min_points kept vertices, order preserved (the reference's filter is min_points = 10).
+ * Two calls, caller-owned memory, all validation on the host before any device work:
+ *   runet_contours_count: flags the border pixels, counts and numbers their states (prefix sum) and labels the background (union-find with
+ *     minimum-index roots, integer atomicMin only) into `workspace` (>= runet_contours_workspace_bytes(h, w) bytes, 16-byte aligned; -1: bad
+ *     shape); *n_states (device int64 [1], 8-byte aligned) receives the state count.  n_states = 0: no contour, nothing more to call.
+ *   runet_contours_trace: with that count read back by the caller and `workspace` unchanged: successors, cycle minima and ranks by pointer
+ *     jumping (a fixed ceil(log2(n_states)) rounds each, double-buffered), start marks, vertex flags, prefix sums, the filter, the packed
+ *     result.  state_workspace: >= runet_contours_state_workspace_bytes(n_states) bytes (-1: n_states < 1 or >= 2^31), 16-byte aligned.  The
+ *     packed result stands at its start: int32 {n, total, offsets [n + 1], points [total][2] = (x, y)}; contour i is points[offsets[i] :
+ *     offsets[i + 1]]; n <= n_states, total <= n_states.
+ * Every device loop is bounded by the data size (fixed jumping rounds, union-find walks over strictly decreasing indices).  No float atomics;
+ * nothing depends on arrival order: two runs give the same bytes.  No host synchronisation except the caller's own reads: n_states between
+ * the two calls, then {n, total}, then the packed result - three device-to-host transfers per mask.
+ * runet_contours_workspace_bytes / runet_contours_state_workspace_bytes: HOST ONLY. */
+long runet_contours_workspace_bytes(int h, int w);
+long runet_contours_state_workspace_bytes(long n_states);
+int runet_contours_count(const unsigned char* mask, int h, int w, void* workspace, long workspace_bytes, long* n_states, void* stream);
+int runet_contours_trace(int h, int w, void* workspace, long workspace_bytes, long n_states, int min_points, void* state_workspace,
+                         long state_workspace_bytes, void* stream);
+
 /* ---- ENet baseline (comne.py:482-608; csrc/enet.hip, the rectangular launchers in csrc/conv_igemm.hip).  Its 1x1 and 3x3 (dilation 1..16)
  *      convolutions, BatchNorm + ReLU, the 2x2 max-pool and the k3-s2 transposed convolutions' gradients and A/B forward (the data gradient of a stride-2 convolution,
  *      runet_conv2d_general) are shared; these are the pieces nothing else expresses.  NHWC fp32, pixel strides multiples of 4 floats that cover

@@ -6,10 +6,14 @@
   * each of the four new kernels at 512^2 and 4096^2 against the same step composed from stock torch device ops on the same data, the two
     alternated in windows of back-to-back calls timed with device events (>= 1 s per variant after a warm-up), with the bytes each kernel
     must move (from the shapes) over its time;
-  * the post-processing share of one 512^2 prediction.
+  * the post-processing share of one 512^2 prediction;
+  * contour tracing (csrc/contours.hip) against the host tracer on the same coastline band, on this box, in interleaved rounds: the band
+    of the 512^2 scene above, and the bands of a seeded smooth random field at 2048^2 and 10980^2; device time by device events and by the
+    wall clock including its three downloads, the workspace bytes at each size.  Where the host tracer would exceed --host-budget seconds
+    it is timed on the top-left 2048^2 crop instead, and the report says so.
 
 Not a bench line of the contract (bench.py measures the Robust U-Net training metric); the figures are kept in profiles/predict_postprocess.txt.
-  python tools/bench_predict.py [--what all|path|kernels] [--window 0.5] [--out FILE]
+  python tools/bench_predict.py [--what all|path|kernels|contours] [--window 0.5] [--host-budget 20] [--out FILE]
 """
 import argparse
 import importlib
@@ -193,9 +197,76 @@ def path_rows(window_s):
     return out
 
 
+def field_water(size, seed, cell=48):
+    """a seeded smooth random field (bicubic interpolation of a coarse normal grid, one cell = `cell` pixels) thresholded at 0: winding
+    shores at every size, built on the device"""
+    g = torch.Generator().manual_seed(seed)
+    coarse = torch.randn((1, 1, size // cell + 3, size // cell + 3), generator=g).to(DEV)
+    return (F.interpolate(coarse, size=(size, size), mode="bicubic", align_corners=True)[0, 0] > 0).to(torch.uint8)
+
+
+def contour_rows(sizes, host_budget):
+    lib = importlib.import_module("eusipco-2026-robust-unet_amd._lib").lib
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    rows = []
+    host_px_per_s = None
+    for size in sizes:
+        water = torch.from_numpy(scene_u8(512, 512, 1)[1]).to(DEV) if size == 512 else field_water(size, size)
+        band = P.dilate_diff(water, 5)[0]
+        del water
+        h, w = band.shape
+        n_set = int(band.sum(dtype=torch.int64))
+        # the host side of the comparison: the whole band, or a crop when the whole band would not fit the budget
+        crop = size
+        if host_px_per_s is not None and n_set / host_px_per_s > host_budget:
+            crop = 2048
+        band_np = band[:crop, :crop].cpu().numpy()
+        rounds = 5 if size <= 512 else 3
+        t_dev, t_wall, t_host = [], [], []
+        got = P.trace_external_contours_device(band)     # warm-up: code objects, allocator
+        for _ in range(rounds):                          # interleaved: device, host, device, host, ...
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ev[0].record()
+            got = P.trace_external_contours_device(band)
+            ev[1].record()
+            ev[1].synchronize()
+            t_wall.append(time.perf_counter() - t0)
+            t_dev.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+            t0 = time.perf_counter()
+            want = P.trace_external_contours(band_np)
+            t_host.append(time.perf_counter() - t0)
+        check = got if crop == size else P.trace_external_contours_device(band[:crop, :crop].contiguous())
+        assert len(check) == len(want) and all(np.array_equal(a, b) for a, b in zip(check, want)), "device and host contours differ"
+        host_px_per_s = int(np.count_nonzero(band_np)) / float(np.median(t_host))
+        # workspace bytes: the pixel stage from the shape, the state stage from the state count
+        ws_bytes = lib.runet_contours_workspace_bytes(h, w)
+        ws = torch.empty(ws_bytes, device=DEV, dtype=torch.uint8)
+        cnt = torch.empty(1, device=DEV, dtype=torch.int64)
+        assert lib.runet_contours_count(band.data_ptr(), h, w, ws.data_ptr(), ws_bytes, cnt.data_ptr(), None) == 0
+        torch.cuda.synchronize()
+        n_states = int(cnt.cpu()[0])
+        sws_bytes = lib.runet_contours_state_workspace_bytes(n_states)
+        del ws
+        row = {"size": size, "set_pixels": n_set, "states": n_states, "contours": len(got), "vertices": int(sum(len(c) for c in got)),
+               "device_ms_events": round(float(np.median(t_dev)) * 1e3, 3), "device_ms_wall_with_downloads": round(float(np.median(t_wall)) * 1e3, 3),
+               "host_ms": round(float(np.median(t_host)) * 1e3, 1), "host_on": f"{crop}^2" + ("" if crop == size else " crop"),
+               "host_set_pixels": int(np.count_nonzero(band_np)), "rounds": rounds, "workspace_bytes": ws_bytes,
+               "state_workspace_bytes": sws_bytes, "device_ms_all": [round(t * 1e3, 3) for t in t_wall],
+               "host_ms_all": [round(t * 1e3, 1) for t in t_host]}
+        rows.append(row)
+        say(f"  {size:5d}^2 band: {n_set} set pixels, {n_states} states, {row['contours']} contours, {row['vertices']} vertices | device "
+            f"{row['device_ms_events']:.3f} ms (events) {row['device_ms_wall_with_downloads']:.3f} ms (wall, 3 downloads) | host tracer on "
+            f"{row['host_on']} ({row['host_set_pixels']} set pixels) {row['host_ms']:.1f} ms | medians of {rounds} interleaved rounds | "
+            f"workspace {ws_bytes / 2**20:.1f} MiB + states {sws_bytes / 2**20:.1f} MiB")
+        del band
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", default="all", choices=("all", "path", "kernels"))
+    ap.add_argument("--what", default="all", choices=("all", "path", "kernels", "contours"))
+    ap.add_argument("--host-budget", type=float, default=20.0, help="seconds one host tracing run may take before it moves to a 2048^2 crop")
     ap.add_argument("--window", type=float, default=0.5, help="seconds per timed window (two windows per variant)")
     ap.add_argument("--out", help="also write the text report here")
     a = ap.parse_args()
@@ -209,6 +280,9 @@ def main():
     if a.what in ("all", "path"):
         say("prediction (fp32, seeded untrained UNet(3, 2)):")
         res["path"] = path_rows(a.window)
+    if a.what in ("all", "contours"):
+        say("contour tracing (csrc/contours.hip against predict.trace_external_contours on the same band, results checked equal):")
+        res["contours"] = contour_rows((512, 2048, 10980), a.host_budget)
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(LINES) + "\n")
