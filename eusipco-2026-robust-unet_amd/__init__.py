@@ -16,6 +16,9 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   trace_external_contours_device (its cv2.findContours step as parallel border following on the device)
   enhance_scene, convert_scene, band_percentiles, select_bands, percentile_ranks (scene.py: the multi-band raster -> uint8 RGB step of
   tif_to_image.py / predict_coastline.py on the device: exact 2-98 % percentiles and the float64 stretch)
+  DeviceCoastalDataset, DeviceLoader, Augment, prepare_device_dataset, resize_pil_device, resample_tables, nearest_table, rotation_words
+  (device_data.py: the dataset built once and kept on the device as bytes, PIL-exact resampling there, batches assembled on the device with
+  the augmentation of train_water_segmentation.py:313-321)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
 Sub-modules are imported lazily so that host-only pieces (data, portable_rng) stay usable
@@ -49,6 +52,8 @@ _LAZY = {
     "PSPNet": "pspnet", "PyramidPooling": "pspnet",
     "enhance_scene": "scene", "convert_scene": "scene", "band_percentiles": "scene", "select_bands": "scene", "percentile_ranks": "scene",
     "trace_external_contours_device": "predict",
+    "DeviceCoastalDataset": "device_data", "DeviceLoader": "device_data", "Augment": "device_data", "prepare_device_dataset": "device_data",
+    "resize_pil_device": "device_data", "resample_tables": "device_data", "nearest_table": "device_data", "rotation_words": "device_data",
 }
 
 

@@ -964,6 +964,45 @@ int runet_band_percentiles_timed(const void* bands, int dtype, int n_bands, int 
 int runet_band_stretch_u8(const void* bands, int dtype, int n_bands, int h, int w, long band_stride, long row_stride, long elem_stride, int sel0,
                           int sel1, int sel2, const double* pct, int mode, unsigned char* out, long out_row_stride, void* stream);
 
+/* ---- device-resident dataset (csrc/input_pipeline.hip, device_data.py).  The reference's dataset decodes, rasterises and LANCZOS-resizes
+ *      every sample on every epoch (Main_Final.py:40-54), and its training script augments on the host with torchvision
+ *      (train_water_segmentation.py:313-321: RandomHorizontalFlip, RandomRotation(10), ColorJitter(0.1, 0.1, 0.1), the / 255 conversion to float, Normalize).  Here
+ *      a sample is built once into a uint8 cache on the device and every batch is assembled there.  All of it is exact against PIL, byte for
+ *      byte; every table comes from the host (device_data.resample_tables / nearest_table / rotation_words, PIL's rules in double precision),
+ *      the kernels apply them and clamp what they read from a table to the source.  All validation happens on the host before any device
+ *      work and reports through runet_last_error.
+ * runet_resample8_rows / runet_resample8_cols: the horizontal and the vertical pass of Image.resize on dense HWC uint8, c = 1 or 3, source and
+ *   destination at any byte address.  bounds int32 [out][2] = (first source index, tap count), coeffs int32 [out][ksize] = 22-bit fixed-point
+ *   weights (1 <= ksize <= 255), both 4-byte aligned.  Per output byte: clamp((2^21 + sum_t coeffs[o][t] * src[first + t]) >> 22, 0, 255),
+ *   int32 accumulator, arithmetic shift.  The filter (LANCZOS, BILINEAR) is in the tables alone.  rows: [h][w_in][c] -> [h][w_out][c];
+ *   cols: [h_in][w][c] -> [h_out][w][c], h_out <= 65535.  An image stays below 2^31 bytes.
+ * runet_gather2d_u8: dst[y][x] = src[ytab[y]][xtab[x]] on one dense uint8 plane (Image.resize(NEAREST) of the mask); dst 4-byte aligned.
+ * runet_batch_gray_sums: sums[i] (device int64 [b], 8-byte aligned, cleared by the call) = the integer sum of L = (19595 R + 38470 G + 7471 B
+ *   + 32768) >> 16 over sample i as it stands in front of its contrast step: gathered through flip and rotation, the jitter steps that come
+ *   before contrast in its order applied.  Integer adds only (64-bit atomics): two runs give the same bytes.
+ * runet_batch_assemble: images uint8 [m][s][s][3] and masks uint8 [m][s][s] (the cache, 4-byte aligned), index int32 [b] (any order,
+ *   repeats allowed; an index outside 0..m-1 is clamped), 1 <= s <= 4096, 1 <= b <= 65535 -> out_images float32 [b][3][s][s], out_masks float32
+ *   [b][1][s][s] (16-byte aligned).  Without geom / factors / sums (all three NULL): out = ((byte / 255) - mean[c]) / std[c] in correctly
+ *   rounded float32 operations, mask = (float)byte.  With them (all three given), per output pixel (x, y) of sample i:
+ *     geom int32 [b][8] = {flip, a0, a1, a2, a3, a4, a5, order}: source ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16) of the flipped
+ *       image (Image.rotate's 16.16 affine_fixed after transpose(FLIP_LEFT_RIGHT)); outside the image: 0.
+ *     order = step0 | step1 << 2 | step2 << 4 with 0 brightness, 1 contrast, 2 saturation; factors float32 [b][3] in that numbering.  Each
+ *       step is Image.blend(degenerate d, image a, f): t = float32(d) + float32(f * float32(a - d)), no fused multiply-add; trunc(t) for
+ *       0 <= f <= 1, else clamped to 0..255 first; the byte goes on to the next step.  d = 0 (brightness), the pixel's L (saturation),
+ *       int(sums[i] / s^2 + 0.5) in double (contrast: ImageStat's mean of the whole current image, zero-filled corners included).
+ *     mask_mode 1 ("follow"): the mask takes the same gather, fill 0;  0 ("fixed"): the mask is left alone, as the reference does. */
+int runet_resample8_rows(const unsigned char* src, int h, int w_in, int c, const int* bounds, const int* coeffs, int ksize, unsigned char* dst,
+                         int w_out, void* stream);
+int runet_resample8_cols(const unsigned char* src, int h_in, int w, int c, const int* bounds, const int* coeffs, int ksize, unsigned char* dst,
+                         int h_out, void* stream);
+int runet_gather2d_u8(const unsigned char* src, int sh, int sw, const int* ytab, const int* xtab, unsigned char* dst, int dh, int dw,
+                      void* stream);
+int runet_batch_gray_sums(const unsigned char* images, int m, int s, const int* index, int b, const int* geom, const float* factors, long* sums,
+                          void* stream);
+int runet_batch_assemble(const unsigned char* images, const unsigned char* masks, int m, int s, const int* index, int b, float mean0,
+                         float mean1, float mean2, float std0, float std1, float std2, const int* geom, const float* factors, const long* sums,
+                         int mask_mode, float* out_images, float* out_masks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
