@@ -2,9 +2,12 @@
 //
 // Replaces the ATen/oneDNN kernels behind every nn.Conv2d / nn.ConvTranspose2d of the reference's
 // RobustUNet (/root/reference/Main_Final.py:157,159,172,126,131,205-208,261-270) for forward, data
-// gradient and weight gradient.  One kernel template serves 1x1 / 3x3 (dilation 1,2,4) convolutions
-// and the k2-s2 transposed convolution; the geometry struct says how a GEMM row (a pixel of the
-// iteration space) maps to source and destination pixels.
+// gradient and weight gradient, and of the baseline models (strided, dilated, rectangular and large
+// kernels, k3 / k4 transposed convolutions, batched GEMMs).  One kernel template serves them all; the
+// geometry struct says how a GEMM row (a pixel of the iteration space) maps to source and destination
+// pixels.  File layout: the kernels; then the host side - builders that fill the geometry structs, the
+// route (tile variant, weight layout, loader) computed from a filled struct, the split-K launcher - and
+// last the extern "C" entry points: their own argument checks, then builder -> route -> launch.
 //
 // Data layout in HBM: activations NHWC fp32 (pixel stride `ld` floats, so a tensor may be a channel
 // slice of a wider concat buffer); weights "HWIO": w[tap][cin][cout], cout contiguous.
@@ -20,7 +23,6 @@
 //   GEMM M = cin, N = cout, K = pixels (step 16 pixels); split over pixel ranges (grid.z) into
 //   partial slabs that a second kernel sums in a fixed order (bitwise reproducible, no atomics).
 #include "runet_common.h"
-#include <stdlib.h>
 #include "../../include/runet_hip.h"
 
 namespace {
@@ -701,7 +703,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_tile_kernel(WGradTileArgs g) {
 
 struct TilePlan { int tm, tn, ci_chunks, co_chunks, total_tiles, tiles_h, tiles_w, splits, tps; };
 
-static TilePlan wgrad_tile_plan(int n_img, int h, int w_, int cin_w, int cout, int ks) {
+// z_taps: taps that ride on grid.z (4 for the k2-s2 transposed convolution, whose splits shrink by as much), else 1
+static TilePlan wgrad_tile_plan(int n_img, int h, int w_, int cin_w, int cout, int ks, int z_taps = 1) {
     TilePlan p{};
     if (ks == 3) { p.tm = 1; p.tn = 1; }
     else { p.tm = cin_w > 64 ? 2 : 1; p.tn = cout > 64 ? 2 : 1; }
@@ -715,6 +718,7 @@ static TilePlan wgrad_tile_plan(int n_img, int h, int w_, int cin_w, int cout, i
     if (splits < 1) splits = 1;
     p.tps = cdiv(p.total_tiles, splits);
     p.splits = cdiv(p.total_tiles, p.tps);
+    if (z_taps > 1) { p.splits = cdiv(p.splits, z_taps); p.tps = cdiv(p.total_tiles, p.splits); p.splits = cdiv(p.total_tiles, p.tps); }
     return p;
 }
 
@@ -807,74 +811,6 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
     }
 }
 
-template <int BM, int BN, int WM, int WN, bool KC>
-void launch_igemm(const IGemmArgs& a, int gz, hipStream_t st) {
-    const long P = (long)a.Nimg * a.H * a.W;
-    dim3 grid(cdiv(P, BM), cdiv(a.Ncols, BN), gz);
-    const size_t lds = 2 * (BM * 20 + 16 * (BN + 4)) * sizeof(float);
-    static const bool no_simple = getenv("RUNET_IGEMM_GENERAL") && atoi(getenv("RUNET_IGEMM_GENERAL")) != 0;      // measurement knob
-    // every tap of every row inside the source image, no coordinate division: the plain 1x1 convolution (also the four 1x1 GEMMs of the
-    // k2-s2 transposed forward, z_taps > 0) and the k2-s2 transposed convolution's data gradient (source pixel (2h + r, 2w + s))
-    const bool plain1 = a.KH == 1 && a.KW == 1 && a.a_scale == 1 && a.Hin == a.H && a.Win == a.W;
-    const bool up2 = a.KH == 2 && a.KW == 2 && a.z_taps == 0 && a.a_scale == 2 && a.tdh == 1 && a.tdw == 1 && a.Hin == 2 * a.H && a.Win == 2 * a.W;
-    const bool simple = !no_simple && (plain1 || up2) && a.a_div <= 1 && !a.zmode4 && a.bh == 0 && a.bw == 0 && a.K % 16 == 0 && a.Kx >= a.K &&
-                        a.Kvalid >= a.K && a.Ncols >= 4 && P > 0;
-    if (simple) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, KC, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, KC, false>), grid, dim3(256), lds, st, a);
-}
-
-enum IGemmVariant { V_128x32 = 0, V_256x64 = 1, V_128x64 = 2, V_128x128 = 3, V_64x64 = 4 };
-
-int g_forced_variant = -1;      // tools/igemm_variants.py: time every tile variant on one shape (runet_igemm_force_variant)
-
-// k1: channels read by a plain 1x1 convolution (0 for every other geometry); kc: k-contiguous weights (the data gradients);
-// up2: the k2-s2 transposed convolution's data gradient
-IGemmVariant pick_variant(long P, int ncols, int k1, bool kc, bool up2 = false) {
-    if (g_forced_variant >= 0) return (IGemmVariant)g_forced_variant;
-    if (ncols <= 32) return V_128x32;
-    // 1x1 convolutions are short (K / 16 steps per tile) and near the HBM / MFMA balance point: many small tiles hide the prologue and
-    // the `+=` epilogue behind other tiles better than few large ones.  Measured on the 32 1x1 launches of the 16 x 256^2 step
-    // (tools/igemm_variants.py, profiles/round2_igemm_variants.txt): 64x64 wins for every data gradient and for every forward with
-    // K <= 128 (10-30 %); from K = 256 on the forward prefers the large tiles below (weights re-read per tile start to count).
-    static const bool old_rules = getenv("RUNET_IGEMM_OLD_TILES") && atoi(getenv("RUNET_IGEMM_OLD_TILES")) != 0;      // A/B knob
-    if (!old_rules && k1 > 0 && (kc || k1 <= 128)) return V_64x64;
-    if (!old_rules && up2 && kc && ncols <= 256) return V_64x64;      // same table: 199 -> 175 us (128 -> 256 @ 64^2), 198 -> 184 us (64 -> 128 @ 128^2)
-    if (ncols <= 64) return (P >= 256L * 512) ? V_256x64 : V_128x64;
-    const long blocks128 = (long)cdiv(P, 128) * cdiv(ncols, 128);
-    if (blocks128 >= 512 || (ncols % 128 == 0 && blocks128 >= 256)) return V_128x128;
-    if ((long)cdiv(P, 128) * cdiv(ncols, 64) < 256) return V_64x64;      // few pixels (deep levels): smaller tiles keep every CU busy
-    return V_128x64;
-}
-
-template <bool KC>
-void dispatch_igemm(const IGemmArgs& a, int gz, hipStream_t st) {
-    const bool plain1 = a.KH == 1 && a.KW == 1 && a.a_scale == 1 && a.Hin == a.H && a.Win == a.W && a.z_taps == 0;
-    const bool up2 = a.KH == 2 && a.KW == 2 && a.z_taps == 0 && a.a_scale == 2;
-    switch (pick_variant((long)a.Nimg * a.H * a.W, a.Ncols, plain1 ? a.K : 0, KC, up2)) {
-    case V_128x32: launch_igemm<128, 32, 32, 32, KC>(a, gz, st); break;
-    case V_256x64: launch_igemm<256, 64, 64, 64, KC>(a, gz, st); break;
-    case V_128x64: launch_igemm<128, 64, 64, 32, KC>(a, gz, st); break;
-    case V_128x128: launch_igemm<128, 128, 64, 64, KC>(a, gz, st); break;
-    case V_64x64: launch_igemm<64, 64, 32, 32, KC>(a, gz, st); break;
-    }
-}
-
-// the k4 transposed forward with the statistics epilogue: the tile variant dispatch_igemm<false> would pick (same grid, same y)
-template <int BM, int BN, int WM, int WN>
-void launch_igemm_stats(const IGemmArgs& a, int gz, float* stats, hipStream_t st) {
-    const long P = (long)a.Nimg * a.H * a.W;
-    dim3 grid(cdiv(P, BM), cdiv(a.Ncols, BN), gz);
-    const size_t lds = 2 * (BM * 20 + 16 * (BN + 4)) * sizeof(float);
-    static_assert((BM / WM) * BN * 3 <= 2 * (BM * 20 + 16 * (BN + 4)), "statistics exchange fits the stages");
-    hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, false, false, float*>), grid, dim3(256), lds, st, a, stats);
-}
-
-IGemmVariant convt4_fwd_variant(long P, int cout) { return pick_variant(P, cout, 0, false, false); }
-int variant_bm(IGemmVariant v) { return v == V_256x64 ? 256 : v == V_64x64 ? 64 : 128; }
-
-}  // namespace
-
-namespace {
 // wt[tap][co][ci] = w[tap][ci][co]: 32x32 tiles through LDS, both sides coalesced
 __global__ __launch_bounds__(256) void transpose_taps_kernel(const float* __restrict__ w, float* __restrict__ wt, int cin, int cout) {
     __shared__ float tile[32][33];
@@ -886,6 +822,284 @@ __global__ __launch_bounds__(256) void transpose_taps_kernel(const float* __rest
     for (int r = ty; r < 32; r += 8)
         if (co0 + r < cout && ci0 + tx < cin) wt[base + (long)(co0 + r) * cin + ci0 + tx] = tile[tx][r];
 }
+
+// The template kernels this file instantiates: all of them and no others, in the order the device object has always carried them (the order
+// of first use in the launchers as they once were).  Naming them here, ahead of every launcher, keeps the device code byte for byte the same
+// however the host code below is arranged, so a host-side change can be checked by comparing the .text sections of two builds.
+#define K(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+#define IGEMM_LOADERS(...) K(igemm_kernel<__VA_ARGS__, true>), K(igemm_kernel<__VA_ARGS__, false>)
+#define IGEMM_STATS(...) K(igemm_kernel<__VA_ARGS__, false, false, float*>)
+const void* const INSTANTIATIONS[] = {
+    IGEMM_LOADERS(256, 64, 64, 64, false),
+    IGEMM_LOADERS(128, 32, 32, 32, true), IGEMM_LOADERS(256, 64, 64, 64, true), IGEMM_LOADERS(128, 64, 64, 32, true),
+    IGEMM_LOADERS(128, 128, 64, 64, true), IGEMM_LOADERS(64, 64, 32, 32, true),
+    K(wgrad_tile_kernel<3, 1, 1>), K(wgrad_tile_kernel<1, 2, 2>), K(wgrad_tile_kernel<1, 2, 1>), K(wgrad_tile_kernel<1, 1, 2>), K(wgrad_tile_kernel<1, 1, 1>),
+    K(wgrad_kernel<128, 128, 64, 64>), K(wgrad_kernel<64, 64, 32, 32>),
+    IGEMM_STATS(128, 32, 32, 32), IGEMM_STATS(256, 64, 64, 64), IGEMM_STATS(128, 64, 64, 32), IGEMM_STATS(128, 128, 64, 64), IGEMM_STATS(64, 64, 32, 32),
+    IGEMM_LOADERS(128, 64, 64, 32, false), IGEMM_LOADERS(128, 128, 64, 64, false), IGEMM_LOADERS(64, 64, 32, 32, false), IGEMM_LOADERS(128, 32, 32, 32, false)};
+#undef IGEMM_STATS
+#undef IGEMM_LOADERS
+#undef K
+
+// =========================================================================================================================== host side
+// Each geometry, each routing condition and the split-K tail are written once:
+//   operands + weight layout + geometry -> IGemmArgs -> igemm_route -> launch_route      (forward, data gradient, GEMM)
+//   operands + geometry -> WGradArgs -> launch_wgrad_splitk                              (per-tap weight gradient)
+
+// ------------------------------------------------------------------------------------------ IGemmArgs builders
+// The operands: `cin` channels are read from x (K pads them to whole k-steps), rows >= cin_w of the weight are zero, `cout` columns are written.
+static IGemmArgs igemm_operands(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int cin, int cin_w, int cout,
+                                int accumulate) {
+    IGemmArgs a{};
+    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = accumulate; a.a_div = 1;
+    a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin_w; a.Ncols = cout;
+    return a;
+}
+// The two weight layouts: [tap][k][n], n contiguous (forward weights "HWIO", and the data gradients' pre-transposed ones), and
+// [tap][n][k], k contiguous (a data gradient reading the forward weight in place).  igemm_route tells them apart by w_sn.
+static void weights_n_contig(IGemmArgs& a) { a.w_tap_stride = (long)a.Kvalid * a.Ncols; a.w_sk = a.Ncols; a.w_sn = 1; }
+static void weights_k_contig(IGemmArgs& a) { a.w_tap_stride = (long)a.Ncols * a.Kx; a.w_sk = 1; a.w_sn = a.Kx; }
+
+// One convolution's spatial parameters, shared by the forward, data-gradient and weight-gradient geometries: input (hin, win), output (ho, wo)
+struct Conv2dGeom { int hin, win, ho, wo, kh, kw, stride, pad_h, pad_w, dil_h, dil_w; };
+// 'same' padding, stride 1 (runet_conv_igemm, runet_conv_wgrad)
+static Conv2dGeom same_conv(int h, int w_, int kh, int kw, int dil) { return {h, w_, h, w_, kh, kw, 1, dil * (kh / 2), dil * (kw / 2), dil, dil}; }
+
+// The geometry builders return grid.z.
+// strided / dilated / per-axis padded forward: rows = output pixels, tap (r, s) reads input (h stride - pad_h + r dil_h, ...)
+static int geom_conv_fwd(IGemmArgs& a, const Conv2dGeom& c) {
+    a.H = c.ho; a.W = c.wo; a.Hin = c.hin; a.Win = c.win; a.a_scale = c.stride; a.KH = c.kh; a.KW = c.kw;
+    a.tdh = c.dil_h; a.tdw = c.dil_w; a.bh = -c.pad_h; a.bw = -c.pad_w; a.Hout = c.ho; a.Wout = c.wo; a.o_scale = 1;
+    return 1;
+}
+// its data gradient: rows = input pixels, tap (r, s) reads dy at (h + pad_h - r dil_h) / stride where that divides (a_div)
+static int geom_conv_dgrad(IGemmArgs& a, const Conv2dGeom& c) {
+    a.H = c.hin; a.W = c.win; a.Hin = c.ho; a.Win = c.wo; a.a_scale = 1; a.KH = c.kh; a.KW = c.kw;
+    a.tdh = -c.dil_h; a.tdw = -c.dil_w; a.bh = c.pad_h; a.bw = c.pad_w; a.a_div = c.stride; a.Hout = c.hin; a.Wout = c.win; a.o_scale = 1;
+    return 1;
+}
+// s x s 1x1 GEMMs over the (h, w) low-resolution pixels; blockIdx.z = tap (r, c) picks the weight slab and the destination pixel
+// (h s + r, w s + c).  s = 2: the k2-s2 transposed forward.  Any s with k-contiguous weights: the data gradient of a kernel = stride, unpadded
+// convolution (SegFormer-Lite's key / value reductions), where each dx pixel has exactly one live tap - the a_div form above would run all s^2
+// taps through the matrix loop for every pixel, s^2 - 1 of them dead.
+static int geom_z_taps(IGemmArgs& a, int h, int w_, int s) {
+    a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = 1; a.KW = 1; a.Hout = h * s; a.Wout = w_ * s; a.o_scale = s; a.z_taps = s;
+    return s * s;
+}
+// data gradient of a stride-2 transposed convolution with a k x k kernel and padding `pad`: dx (h, w) reads dy (2h - pad + r, 2w - pad + s).
+// k = 2, pad = 0 is "up2" (every tap inside the source); k = 4, pad = 1 is the k4-s2-p1 one.
+static int geom_convt_s2_dgrad(IGemmArgs& a, int h, int w_, int k, int pad) {
+    a.H = h; a.W = w_; a.Hin = 2 * h; a.Win = 2 * w_; a.a_scale = 2; a.KH = k; a.KW = k; a.tdh = 1; a.tdw = 1; a.bh = -pad; a.bw = -pad;
+    a.Hout = h; a.Wout = w_; a.o_scale = 1;
+    return 1;
+}
+// ConvTranspose2d(k4, s2, p1) forward: blockIdx.z = output parity class, 2x2 live taps each (zmode4)
+static int geom_convt4_fwd(IGemmArgs& a, int h, int w_) {
+    a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = 2; a.KW = 2; a.zmode4 = 1; a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2;
+    return 4;
+}
+// ConvTranspose2d(k3, s2, p1, output_padding 1) forward, parity class (ph, pw): 1, 2 or 4 live taps, tap (rr, ss) reads source (i + ph (1 - rr), j + pw (1 - ss))
+static int geom_convt3_class(IGemmArgs& a, int h, int w_, int ph, int pw) {
+    a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1;
+    a.KH = ph ? 2 : 1; a.KW = pw ? 2 : 1; a.tdh = ph ? -1 : 0; a.tdw = pw ? -1 : 0; a.bh = ph; a.bw = pw;
+    a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2; a.o_dh = ph; a.o_dw = pw;
+    return 1;
+}
+// plain batched GEMM: one image row of `rows` pixels, one tap; blockIdx.z = the GEMM of the batch
+static int geom_gemm_batch(IGemmArgs& a, int rows, int batch, long stride_a, long stride_b, long stride_c) {
+    a.H = 1; a.W = rows; a.Hin = 1; a.Win = rows; a.a_scale = 1; a.KH = 1; a.KW = 1; a.Hout = 1; a.Wout = rows; a.o_scale = 1;
+    a.w_tap_stride = 0; a.zbatch = 1; a.zs_x = stride_a; a.zs_w = stride_b; a.zs_y = stride_c;
+    return batch;
+}
+
+// kernel = stride, no padding, no dilation, input a whole number of kernels: the data gradient takes geom_z_taps.
+// RUNET_NO_LIVE_TAP_DGRAD=1 (measurement knob, tools/segformer_step.py --kernels): through the general a_div form instead.
+static bool live_tap_dgrad(const Conv2dGeom& c) {
+    static const bool off = env_flag("RUNET_NO_LIVE_TAP_DGRAD");
+    return c.kh == c.stride && c.kw == c.stride && c.stride > 1 && c.pad_h == 0 && c.pad_w == 0 && c.dil_h == 1 && c.dil_w == 1 &&
+           c.hin == c.ho * c.stride && c.win == c.wo * c.stride && !off;
+}
+// runet_conv2d_general / runet_conv2d_rect after validation: weights and geometry of a forward or a data gradient
+static int conv2d_args(IGemmArgs& a, const Conv2dGeom& c, int mode) {
+    if (mode == RUNET_CONV_FWD) { weights_n_contig(a); return geom_conv_fwd(a, c); }
+    weights_k_contig(a);
+    return live_tap_dgrad(c) ? geom_z_taps(a, c.ho, c.wo, c.stride) : geom_conv_dgrad(a, c);
+}
+// runet_conv_igemm's six modes: FWD / DGRAD(_T) are the stride-1 'same' case of the general forward and data gradient; the _T modes read
+// per-tap transposed weights, so they take the n-contiguous layout.  Returns 0 for an unknown mode.
+static int conv_igemm_args(IGemmArgs& a, int h, int w_, int kh, int kw, int dil, int mode) {
+    switch (mode) {
+    case RUNET_CONV_FWD: weights_n_contig(a); return geom_conv_fwd(a, same_conv(h, w_, kh, kw, dil));
+    case RUNET_CONV_DGRAD: weights_k_contig(a); return geom_conv_dgrad(a, same_conv(h, w_, kh, kw, dil));
+    case RUNET_CONV_DGRAD_T: weights_n_contig(a); return geom_conv_dgrad(a, same_conv(h, w_, kh, kw, dil));
+    case RUNET_CONVT_FWD: weights_n_contig(a); return geom_z_taps(a, h, w_, 2);
+    case RUNET_CONVT_DGRAD: weights_k_contig(a); return geom_convt_s2_dgrad(a, h, w_, 2, 0);
+    case RUNET_CONVT_DGRAD_T: weights_n_contig(a); return geom_convt_s2_dgrad(a, h, w_, 2, 0);
+    default: return 0;
+    }
+}
+static int convt4_args(IGemmArgs& a, int h, int w_, int mode) {
+    if (mode == RUNET_CONVT_FWD) { weights_n_contig(a); return geom_convt4_fwd(a, h, w_); }
+    weights_k_contig(a);
+    return geom_convt_s2_dgrad(a, h, w_, 4, 1);
+}
+
+// ------------------------------------------------------------------------------------------ the route: tile variant, weight layout, loader
+enum IGemmVariant { V_128x32 = 0, V_256x64 = 1, V_128x64 = 2, V_128x128 = 3, V_64x64 = 4 };
+template <int BM_, int BN_, int WM_, int WN_> struct Tile { static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_; };
+// the one place that maps a variant to its template arguments: f(Tile<BM, BN, WM, WN>{})
+template <typename F>
+static void with_tile(IGemmVariant v, F&& f) {
+    switch (v) {
+    case V_128x32: f(Tile<128, 32, 32, 32>{}); break;
+    case V_256x64: f(Tile<256, 64, 64, 64>{}); break;
+    case V_128x64: f(Tile<128, 64, 64, 32>{}); break;
+    case V_128x128: f(Tile<128, 128, 64, 64>{}); break;
+    case V_64x64: f(Tile<64, 64, 32, 32>{}); break;
+    }
+}
+static int variant_bm(IGemmVariant v) { return v == V_256x64 ? 256 : v == V_64x64 ? 64 : 128; }
+// [k-contiguous weights][SIMPLE loader][tile variant]: the names rocprofv3 prints for the plain (no statistics) instantiations
+static const char* const IGEMM_NAMES[2][2][5] = {
+    {{"igemm_kernel<128, 32, 32, 32, false, false>", "igemm_kernel<256, 64, 64, 64, false, false>", "igemm_kernel<128, 64, 64, 32, false, false>",
+      "igemm_kernel<128, 128, 64, 64, false, false>", "igemm_kernel<64, 64, 32, 32, false, false>"},
+     {"igemm_kernel<128, 32, 32, 32, false, true>", "igemm_kernel<256, 64, 64, 64, false, true>", "igemm_kernel<128, 64, 64, 32, false, true>",
+      "igemm_kernel<128, 128, 64, 64, false, true>", "igemm_kernel<64, 64, 32, 32, false, true>"}},
+    {{"igemm_kernel<128, 32, 32, 32, true, false>", "igemm_kernel<256, 64, 64, 64, true, false>", "igemm_kernel<128, 64, 64, 32, true, false>",
+      "igemm_kernel<128, 128, 64, 64, true, false>", "igemm_kernel<64, 64, 32, 32, true, false>"},
+     {"igemm_kernel<128, 32, 32, 32, true, true>", "igemm_kernel<256, 64, 64, 64, true, true>", "igemm_kernel<128, 64, 64, 32, true, true>",
+      "igemm_kernel<128, 128, 64, 64, true, true>", "igemm_kernel<64, 64, 32, 32, true, true>"}}};
+
+int g_forced_variant = -1;      // tools/igemm_variants.py: time every tile variant on one shape (runet_igemm_force_variant)
+
+// k1: channels read by a plain 1x1 convolution (0 for every other geometry); kc: k-contiguous weights (the data gradients);
+// up2: the k2-s2 transposed convolution's data gradient
+static IGemmVariant pick_variant(long P, int ncols, int k1, bool kc, bool up2) {
+    if (g_forced_variant >= 0) return (IGemmVariant)g_forced_variant;
+    if (ncols <= 32) return V_128x32;
+    // 1x1 convolutions are short (K / 16 steps per tile) and near the HBM / MFMA balance point: many small tiles hide the prologue and
+    // the `+=` epilogue behind other tiles better than few large ones.  Measured on the 32 1x1 launches of the 16 x 256^2 step
+    // (tools/igemm_variants.py, profiles/round2_igemm_variants.txt): 64x64 wins for every data gradient and for every forward with
+    // K <= 128 (10-30 %); from K = 256 on the forward prefers the large tiles below (weights re-read per tile start to count).
+    static const bool old_rules = env_flag("RUNET_IGEMM_OLD_TILES");      // A/B knob
+    if (!old_rules && k1 > 0 && (kc || k1 <= 128)) return V_64x64;
+    if (!old_rules && up2 && kc && ncols <= 256) return V_64x64;      // same table: 199 -> 175 us (128 -> 256 @ 64^2), 198 -> 184 us (64 -> 128 @ 128^2)
+    if (ncols <= 64) return (P >= 256L * 512) ? V_256x64 : V_128x64;
+    const long blocks128 = (long)cdiv(P, 128) * cdiv(ncols, 128);
+    if (blocks128 >= 512 || (ncols % 128 == 0 && blocks128 >= 256)) return V_128x128;
+    if ((long)cdiv(P, 128) * cdiv(ncols, 64) < 256) return V_64x64;      // few pixels (deep levels): smaller tiles keep every CU busy
+    return V_128x64;
+}
+
+// SIMPLE (see igemm_kernel): every tap of every row inside the source image, no coordinate division, K whole k-steps backed by x and w.
+// That is the plain 1x1 convolution (also the s x s 1x1 GEMMs of geom_z_taps) and "up2", the k2-s2 transposed convolution's data gradient
+// (source pixel (2h + r, 2w + s)).  RUNET_IGEMM_GENERAL=1 (measurement knob): the general loader everywhere.
+struct IGemmRoute { IGemmVariant variant; bool kc, simple; };
+static IGemmRoute igemm_route(const IGemmArgs& a) {
+    static const bool no_simple = env_flag("RUNET_IGEMM_GENERAL");
+    const long P = (long)a.Nimg * a.H * a.W;
+    const bool plain1 = a.KH == 1 && a.KW == 1 && a.a_scale == 1 && a.Hin == a.H && a.Win == a.W;
+    const bool up2 = a.KH == 2 && a.KW == 2 && a.z_taps == 0 && a.a_scale == 2 && a.tdh == 1 && a.tdw == 1 && a.Hin == 2 * a.H && a.Win == 2 * a.W;
+    IGemmRoute r;
+    r.kc = a.w_sn != 1;
+    r.simple = !no_simple && (plain1 || up2) && a.a_div <= 1 && !a.zmode4 && a.bh == 0 && a.bw == 0 && a.K % 16 == 0 && a.Kx >= a.K && a.Kvalid >= a.K &&
+               a.Ncols >= 4 && P > 0;
+    r.variant = pick_variant(P, a.Ncols, (plain1 && a.z_taps == 0) ? a.K : 0, r.kc, up2);      // the z_taps GEMMs follow the general tile rules
+    return r;
+}
+static const char* route_name(const IGemmRoute& r) { return IGEMM_NAMES[r.kc][r.simple][r.variant]; }
+
+// Stats = float*: the statistics epilogue (only instantiated for the n-contiguous general loader, the k4 transposed forward)
+template <int BM, int BN, int WM, int WN, bool KC, bool SIMPLE, typename... Stats>
+static void launch_igemm(const IGemmArgs& a, int gz, hipStream_t st, Stats... stats) {
+    const long P = (long)a.Nimg * a.H * a.W;
+    dim3 grid(cdiv(P, BM), cdiv(a.Ncols, BN), gz);
+    constexpr int LDS_FLOATS = 2 * (BM * 20 + 16 * (BN + 4));
+    static_assert(sizeof...(Stats) == 0 || (BM / WM) * BN * 3 <= LDS_FLOATS, "statistics exchange fits the stages");
+    hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, KC, SIMPLE, Stats...>), grid, dim3(256), LDS_FLOATS * sizeof(float), st, a, stats...);
+}
+static void launch_route(const IGemmArgs& a, const IGemmRoute& r, int gz, hipStream_t st) {
+    with_tile(r.variant, [&](auto t) {
+        using T = decltype(t);
+        if (!r.kc && r.simple) launch_igemm<T::BM, T::BN, T::WM, T::WN, false, true>(a, gz, st);
+        else if (!r.kc) launch_igemm<T::BM, T::BN, T::WM, T::WN, false, false>(a, gz, st);
+        else if (r.simple) launch_igemm<T::BM, T::BN, T::WM, T::WN, true, true>(a, gz, st);
+        else launch_igemm<T::BM, T::BN, T::WM, T::WN, true, false>(a, gz, st);
+    });
+}
+static void dispatch_igemm(const IGemmArgs& a, int gz, hipStream_t st) { launch_route(a, igemm_route(a), gz, st); }
+
+// ------------------------------------------------------------------------------------------ the per-tap split-K weight gradient
+template <int BM, int BN, int WM, int WN>
+static void launch_wgrad(const WGradArgs& a, dim3 grid, hipStream_t st) {
+    const size_t lds = 2 * (16 * (BM + 4) + 16 * (BN + 4)) * sizeof(float);      // two stages of wgrad_kernel's A and B tiles
+    hipLaunchKernelGGL((wgrad_kernel<BM, BN, WM, WN>), grid, dim3(256), lds, st, a);
+}
+// 128 x 128 tiles where both channel counts exceed 64, else 64 x 64; grid = (tiles, taps, splits)
+static int wgrad_tiles(bool big, int cin_w, int cout) { return big ? cdiv(cin_w, 128) * cdiv(cout, 128) : cdiv(cin_w, 64) * cdiv(cout, 64); }
+static void launch_wgrad_tiles(const WGradArgs& a, bool big, int cin_w, int cout, int ntaps, int splits, hipStream_t st) {
+    const dim3 grid(wgrad_tiles(big, cin_w, cout), ntaps, splits);
+    if (big) launch_wgrad<128, 128, 64, 64>(a, grid, st);
+    else launch_wgrad<64, 64, 32, 32>(a, grid, st);
+}
+// dw[i] = sum over the slabs, in a fixed order
+static void reduce_slabs(const float* slabs, float* dw, long wsize, int nsplit, hipStream_t st) {
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, slabs, dw, wsize, nsplit);
+}
+
+struct WGradPlan { bool big; int splits; };
+static WGradPlan wgrad_plan(long P, int cin_w, int cout, int ntaps) {
+    const bool big = (cin_w > 64 && cout > 64);
+    const long base = (long)wgrad_tiles(big, cin_w, cout) * ntaps;
+    long want = (768 + base - 1) / base;            // aim for >= 3 blocks per CU
+    const long maxs = (P + 255) / 256;              // at least 256 pixels per split
+    if (want > maxs) want = maxs;
+    if (want > 64) want = 64;
+    if (want < 1) want = 1;
+    return {big, (int)want};
+}
+// floats of workspace for `splits` partial slabs of a [ntaps][cin_w][cout] gradient (one slab goes straight to dw)
+static long slab_floats(int splits, int ntaps, int cin_w, int cout) { return splits > 1 ? (long)splits * ntaps * cin_w * cout : 0; }
+static long wgrad_workspace(long P, int cin_w, int cout, int ntaps) { return slab_floats(wgrad_plan(P, cin_w, cout, ntaps).splits, ntaps, cin_w, cout); }
+
+// The tail of every per-tap weight gradient: `a` has its geometry; P pixels are summed.  Plans the splits, clamps them to the workspace given,
+// rounds the pixels of a split to whole k-steps, launches and reduces.
+static void launch_wgrad_splitk(WGradArgs a, long P, int cin_w, int cout, int ntaps, float* dw, float* workspace, long workspace_floats, hipStream_t st) {
+    const WGradPlan plan = wgrad_plan(P, cin_w, cout, ntaps);
+    int splits = plan.splits;
+    const long wsize = (long)ntaps * cin_w * cout;
+    if (splits > 1 && (workspace == nullptr || workspace_floats < splits * wsize)) {
+        splits = workspace ? (int)(workspace_floats / wsize) : 1;
+        if (splits < 1) splits = 1;
+    }
+    long pps = (P + splits - 1) / splits;
+    pps = (pps + 15) / 16 * 16;
+    splits = cdiv(P, pps);
+    a.pix_per_split = pps;
+    a.out = (splits > 1) ? workspace : dw;
+    launch_wgrad_tiles(a, plan.big, cin_w, cout, ntaps, splits, st);
+    if (splits > 1) reduce_slabs(workspace, dw, wsize, splits, st);
+}
+
+static WGradArgs wgrad_operands(const float* x, int ldx, const float* dy, int ldy, int n_img, int cin, int cin_w, int cout) {
+    WGradArgs a{};
+    a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy; a.Kci = cin; a.Kvalid = cin_w; a.Nco = cout; a.Nimg = n_img;
+    return a;
+}
+// weight gradient of geom_conv_fwd's convolution: pixels summed = output pixels, tap (r, s) shifts the x pixel
+static long wgrad_geom_conv(WGradArgs& a, const Conv2dGeom& c) {
+    a.H = c.ho; a.W = c.wo; a.Hin = c.hin; a.Win = c.win; a.a_scale = c.stride; a.KH = c.kh; a.KW = c.kw;
+    a.tdh = c.dil_h; a.tdw = c.dil_w; a.bh = -c.pad_h; a.bw = -c.pad_w;
+    a.Hout = c.ho; a.Wout = c.wo; a.o_scale = 1;
+    return (long)a.Nimg * c.ho * c.wo;
+}
+// ... of ConvTranspose2d(k4, s2, p1): pixels summed = input pixels, tap (r, s) shifts the dy pixel (2h - 1 + r, 2w - 1 + s)
+static long wgrad_geom_convt4(WGradArgs& a, int h, int w_) {
+    a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = 4; a.KW = 4;
+    a.tap_on_output = 1; a.o_bh = -1; a.o_bw = -1; a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2;
+    return (long)a.Nimg * h * w_;
+}
+
 }  // namespace
 
 extern "C" int runet_transpose_taps(const float* w, float* wt, int taps, int cin, int cout, void* stream) {
@@ -908,23 +1122,12 @@ extern "C" int runet_igemm_force_variant(int variant) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ 1x1 / 3x3 / k2-s2 transposed (RobustUNet)
+// which device kernel runet_conv_igemm launches for a shape: the same builder and route, without operands (ops.py labels its profile rows with it)
 extern "C" const char* runet_conv_igemm_kernel_name(int n_img, int h, int w_, int cin, int cout, int kh, int mode) {
-    // [k-contiguous weights][SIMPLE loader][tile variant]: the names rocprofv3 prints for the instantiations runet_conv_igemm launches
-    static const char* names[2][2][5] = {
-        {{"igemm_kernel<128, 32, 32, 32, false, false>", "igemm_kernel<256, 64, 64, 64, false, false>", "igemm_kernel<128, 64, 64, 32, false, false>",
-          "igemm_kernel<128, 128, 64, 64, false, false>", "igemm_kernel<64, 64, 32, 32, false, false>"},
-         {"igemm_kernel<128, 32, 32, 32, false, true>", "igemm_kernel<256, 64, 64, 64, false, true>", "igemm_kernel<128, 64, 64, 32, false, true>",
-          "igemm_kernel<128, 128, 64, 64, false, true>", "igemm_kernel<64, 64, 32, 32, false, true>"}},
-        {{"igemm_kernel<128, 32, 32, 32, true, false>", "igemm_kernel<256, 64, 64, 64, true, false>", "igemm_kernel<128, 64, 64, 32, true, false>",
-          "igemm_kernel<128, 128, 64, 64, true, false>", "igemm_kernel<64, 64, 32, 32, true, false>"},
-         {"igemm_kernel<128, 32, 32, 32, true, true>", "igemm_kernel<256, 64, 64, 64, true, true>", "igemm_kernel<128, 64, 64, 32, true, true>",
-          "igemm_kernel<128, 128, 64, 64, true, true>", "igemm_kernel<64, 64, 32, 32, true, true>"}}};
-    const bool kc = (mode == RUNET_CONV_DGRAD || mode == RUNET_CONVT_DGRAD);      // the _T modes read pre-transposed weights with the n-contiguous kernels
-    static const bool no_simple = getenv("RUNET_IGEMM_GENERAL") && atoi(getenv("RUNET_IGEMM_GENERAL")) != 0;
-    // SIMPLE loader (launch_igemm): 1x1 convolutions and the k2-s2 transposed convolution, K a multiple of 16
-    const bool simple = !no_simple && (kh == 1 || kh == 2) && cin % 16 == 0 && cout >= 4;
-    const bool plain1 = kh == 1 && (mode == RUNET_CONV_FWD || mode == RUNET_CONV_DGRAD || mode == RUNET_CONV_DGRAD_T);
-    return names[kc ? 1 : 0][simple ? 1 : 0][pick_variant((long)n_img * h * w_, cout, plain1 ? cin : 0, kc, mode == RUNET_CONVT_DGRAD)];
+    IGemmArgs a = igemm_operands(nullptr, cin, nullptr, nullptr, nullptr, cout, n_img, cin, cin, cout, 0);
+    if (!conv_igemm_args(a, h, w_, kh, kh, 1, mode)) return "unknown mode";
+    return route_name(igemm_route(a));
 }
 
 extern "C" int runet_conv_igemm(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy,
@@ -938,89 +1141,33 @@ extern "C" int runet_conv_igemm(const float* x, int ldx, const float* w, const f
     RUNET_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "pointers must be 16-byte aligned");
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty iteration space");
     RUNET_REQUIRE((kh == 1 && kw == 1) || (kh == 3 && kw == 3) || (kh == 2 && kw == 2), "kernel must be 1x1, 3x3 or 2x2(transposed)");
-    hipStream_t st = (hipStream_t)stream;
-    IGemmArgs a{};
-    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy;
-    a.Nimg = n_img; a.accumulate = accumulate; a.KH = kh; a.KW = kw;
-    int gz = 1;
     switch (mode) {
     case RUNET_CONV_FWD:      // y[N,h,w,cout] = conv(x[N,h,w,cin], w[kh,kw,cin_w,cout]), 'same' padding = dil*(k-1)/2
         RUNET_REQUIRE(kh != 2, "2x2 kernels are transposed-conv only");
         RUNET_REQUIRE(ldy >= cout, "ldy < cout");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin_w; a.Ncols = cout;
-        a.w_tap_stride = (long)cin_w * cout; a.w_sk = cout; a.w_sn = 1;
-        a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1;
-        a.tdh = dil; a.tdw = dil; a.bh = -dil * (kh / 2); a.bw = -dil * (kw / 2);
-        a.Hout = h; a.Wout = w_; a.o_scale = 1;
-        dispatch_igemm<false>(a, gz, st);
         break;
-    case RUNET_CONV_DGRAD:    // dx[N,h,w,cout_w... ] : here `cin` = channels of dy (=conv Cout), `cout` = conv Cin
-        // x := dy [N,h,w,cin], y := dx [N,h,w,cout];  w is the forward weight [kh,kw,cout(conv Cin),cin(conv Cout)]
+    case RUNET_CONV_DGRAD:    // x := dy [N,h,w,cin(=conv Cout)], y := dx [N,h,w,cout(=conv Cin)]; w is the forward weight [kh,kw,cout,cin]
         RUNET_REQUIRE(kh != 2, "use RUNET_CONVT_DGRAD for 2x2");
         RUNET_REQUIRE(cin_w == cin, "dgrad reads every output channel");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
-        a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1;
-        a.tdh = -dil; a.tdw = -dil; a.bh = dil * (kh / 2); a.bw = dil * (kw / 2);
-        a.Hout = h; a.Wout = w_; a.o_scale = 1;
-        dispatch_igemm<true>(a, gz, st);
         break;
     case RUNET_CONV_DGRAD_T:  // as RUNET_CONV_DGRAD with the weight already transposed per tap: w [kh,kw,cin(conv Cout),cout(conv Cin)]
         RUNET_REQUIRE(kh != 2 && cin_w == cin, "dgrad reads every output channel; use RUNET_CONVT_DGRAD_T for 2x2");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = cout; a.w_sn = 1;
-        a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1;
-        a.tdh = -dil; a.tdw = -dil; a.bh = dil * (kh / 2); a.bw = dil * (kw / 2);
-        a.Hout = h; a.Wout = w_; a.o_scale = 1;
-        dispatch_igemm<false>(a, gz, st);
-        break;
-    case RUNET_CONVT_DGRAD_T: // as RUNET_CONVT_DGRAD with w [2,2,cin(convT Cout),cout(convT Cin)]
-        RUNET_REQUIRE(kh == 2 && kw == 2 && cin_w == cin, "transposed conv is 2x2 stride 2");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = cout; a.w_sn = 1;
-        a.H = h; a.W = w_; a.Hin = 2 * h; a.Win = 2 * w_; a.a_scale = 2; a.tdh = 1; a.tdw = 1;
-        a.Hout = h; a.Wout = w_; a.o_scale = 1;
-        dispatch_igemm<false>(a, gz, st);
         break;
     case RUNET_CONVT_FWD:     // y[N,2h,2w,cout] = convT_k2s2(x[N,h,w,cin]); w [2,2,cin,cout]
-        RUNET_REQUIRE(kh == 2 && kw == 2 && cin_w == cin, "transposed conv is 2x2 stride 2");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cin * cout; a.w_sk = cout; a.w_sn = 1;
-        a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = 1; a.KW = 1;
-        a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2; a.z_taps = 2; gz = 4;
-        dispatch_igemm<false>(a, gz, st);
-        break;
     case RUNET_CONVT_DGRAD:   // dx[N,h,w,cout(=convT Cin)] from dy[N,2h,2w,cin(=convT Cout)]; w [2,2,cout,cin]
+    case RUNET_CONVT_DGRAD_T: // as RUNET_CONVT_DGRAD with w [2,2,cin(convT Cout),cout(convT Cin)]
         RUNET_REQUIRE(kh == 2 && kw == 2 && cin_w == cin, "transposed conv is 2x2 stride 2");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
-        a.H = h; a.W = w_; a.Hin = 2 * h; a.Win = 2 * w_; a.a_scale = 2; a.tdh = 1; a.tdw = 1;
-        a.Hout = h; a.Wout = w_; a.o_scale = 1;
-        dispatch_igemm<true>(a, gz, st);
         break;
     default:
         RUNET_REQUIRE(false, "unknown mode");
     }
+    IGemmArgs a = igemm_operands(x, ldx, w, bias, y, ldy, n_img, cin, cin_w, cout, accumulate);
+    const int gz = conv_igemm_args(a, h, w_, kh, kw, dil, mode);
+    dispatch_igemm(a, gz, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }
 
-static int pick_splits(long P, int tiles, int ntaps) {
-    const long base = (long)tiles * ntaps;
-    long want = (768 + base - 1) / base;            // aim for >= 3 blocks per CU
-    long maxs = (P + 255) / 256;                     // at least 256 pixels per split
-    if (want > maxs) want = maxs;
-    if (want > 64) want = 64;
-    if (want < 1) want = 1;
-    return (int)want;
-}
-
-static void wgrad_plan(long P, int cin_w, int cout, int ntaps, bool& big, int& tiles, int& splits) {
-    big = (cin_w > 64 && cout > 64);
-    const int BMt = big ? 128 : 64, BNt = big ? 128 : 64;
-    tiles = cdiv(cin_w, BMt) * cdiv(cout, BNt);
-    splits = pick_splits(P, tiles, ntaps);
-}
-
+// ------------------------------------------------------------------------------------------ its weight gradient: five routes
 static bool use_tile_kernel(int kh, int kw, int dil, int transposed) {
     if (transposed) return kh == 2 && kw == 2;
     return (kh == 1 && kw == 1) || (kh == 3 && kw == 3 && dil == 1);
@@ -1043,66 +1190,58 @@ static int wgrad1x1_rows_per_split(long P, int cin, int cout) {
 // The step time does not move (weight gradients run on the side stream); the GPU does 0.3 ms less work.  RUNET_WGRAD1X1_TILE=1: tile kernel
 // everywhere.  (With RUNET_GEMM_TN_DIRECT=1 the GEMM is the register-direct one, which also serves narrow outputs.)
 static bool wgrad1x1_direct(long P, int cin, int cout) {
-    static const bool off = getenv("RUNET_WGRAD1X1_TILE") && atoi(getenv("RUNET_WGRAD1X1_TILE")) != 0;
-    static const bool direct = getenv("RUNET_GEMM_TN_DIRECT") && atoi(getenv("RUNET_GEMM_TN_DIRECT")) != 0;
+    static const bool off = env_flag("RUNET_WGRAD1X1_TILE");
+    static const bool direct = env_flag("RUNET_GEMM_TN_DIRECT");
     if (off || P * 4 >= (1L << 31)) return false;
     if (direct) return !((long)cin * cout <= 8192 && P >= (1L << 19));
     // RUNET_WGRAD1X1_MIN_NARROW (measurement knob, default 128): channels the NARROWER side needs (the wider one always >= 128)
-    static const int narrow = getenv("RUNET_WGRAD1X1_MIN_NARROW") ? atoi(getenv("RUNET_WGRAD1X1_MIN_NARROW")) : 128;
+    static const int narrow = env_int("RUNET_WGRAD1X1_MIN_NARROW", 128);
     const int lo = cin < cout ? cin : cout, hi = cin < cout ? cout : cin;
     return hi >= 128 && lo >= narrow;
 }
 // ... and of those the ones the split-operand TN GEMM (gemm_split.hip, BF16 matrix cores, fp32-accurate) takes: pixel count a multiple of 16
 static bool wgrad1x1_x3(long P, int cin, int cout) {
-    static const bool off = (getenv("RUNET_NO_X3") && atoi(getenv("RUNET_NO_X3")) != 0) || (getenv("RUNET_GEMM_TN_DIRECT") && atoi(getenv("RUNET_GEMM_TN_DIRECT")) != 0);
+    static const bool off = env_flag("RUNET_NO_X3") || env_flag("RUNET_GEMM_TN_DIRECT");
     return !off && P % 16 == 0;
 }
 
 // the transposed convolution's weight gradient on the split-operand TN GEMM: image width a multiple of 16 (a k-step's rows share an image row),
 // both channel counts >= RUNET_CONVT_WGRAD_X3_MIN [64]
 static bool convt_wgrad_x3(long P, int w_, int cin, int cout) {
-    static const bool off = (getenv("RUNET_NO_X3") && atoi(getenv("RUNET_NO_X3")) != 0) || (getenv("RUNET_NO_CONVT_WGRAD_X3") && atoi(getenv("RUNET_NO_CONVT_WGRAD_X3")) != 0);
-    static const int lo = getenv("RUNET_CONVT_WGRAD_X3_MIN") ? atoi(getenv("RUNET_CONVT_WGRAD_X3_MIN")) : 64;
+    static const bool off = env_flag("RUNET_NO_X3") || env_flag("RUNET_NO_CONVT_WGRAD_X3");
+    static const int lo = env_int("RUNET_CONVT_WGRAD_X3_MIN", 64);
     return !off && w_ % 16 == 0 && P % 16 == 0 && P < (1L << 31) && cin >= lo && cout >= lo;
 }
+// ... its plan: 4 taps = 4 GEMMs over the low-resolution pixels, up to 512 / tiles splits of at least 256 rows; -> rows per split (16-aligned)
+static int convt_wgrad_x3_rows_per_split(long P, int cin, int cout) {
+    const long tiles = (long)cdiv(cin, 128) * cdiv(cout, 128) * 4;
+    long splits = cdiv(512, tiles);
+    const long maxs = P / 256 > 0 ? P / 256 : 1;
+    if (splits > maxs) splits = maxs;
+    return (int)((cdiv(P, splits) + 15) / 16 * 16);
+}
 
+// the largest workspace any route of runet_conv_wgrad may use for the shape (dilation and the knobs are unknown here)
 extern "C" long runet_conv_wgrad_workspace_floats(int n_img, int h, int w_, int cin_w, int cout, int kh, int kw) {
+    const long P = (long)n_img * h * w_;
+    const long generic = wgrad_workspace(P, cin_w, cout, kh * kw);
     if (kh == 1 && kw == 1) {
-        const long P = (long)n_img * h * w_;
         const long direct = (long)cdiv(P, wgrad1x1_rows_per_split(P, cin_w, cout)) * cin_w * cout;
-        TilePlan p = wgrad_tile_plan(n_img, h, w_, cin_w, cout, 1);
-        const long tile = p.splits > 1 ? (long)p.splits * cin_w * cout : 0;
+        const long tile = slab_floats(wgrad_tile_plan(n_img, h, w_, cin_w, cout, 1).splits, 1, cin_w, cout);
         return direct > tile ? direct : tile;
     }
     if (kh == 3 && kw == 3 && cin_w <= 4) return (long)cdiv(h, 4) * n_img * 9 * cin_w * cout + 64L * 9 * cin_w * cout;   // stem kernel slabs
-    if (kh == 2 && kw == 2) {                                // transposed: the split-operand TN plan (up to 512 / tiles splits) or the tile plan below
-        const long P = (long)n_img * h * w_;
-        const long tiles = (long)cdiv(cin_w, 128) * cdiv(cout, 128) * 4;
-        long splits = cdiv(512, tiles);
-        const long maxs = P / 256 > 0 ? P / 256 : 1;
-        if (splits > maxs) splits = maxs;
-        const long x3 = (long)cdiv(P, (cdiv(P, splits) + 15) / 16 * 16) * 4 * cin_w * cout;
-        TilePlan p = wgrad_tile_plan(n_img, h, w_, cin_w, cout, 1);
-        p.splits = cdiv(p.splits, 4); p.tps = cdiv(p.total_tiles, p.splits); p.splits = cdiv(p.total_tiles, p.tps);
-        bool big; int tl, sp;
-        wgrad_plan(P, cin_w, cout, 4, big, tl, sp);
-        const long a = p.splits > 1 ? (long)p.splits * 4 * cin_w * cout : 0;
-        const long b = sp > 1 ? (long)sp * 4 * cin_w * cout : 0;
-        const long m = a > b ? a : b;
+    if (kh == 2 && kw == 2) {                                // transposed: the split-operand TN plan, the tile plan or the generic one
+        const long x3 = (long)cdiv(P, convt_wgrad_x3_rows_per_split(P, cin_w, cout)) * 4 * cin_w * cout;
+        const long tile = slab_floats(wgrad_tile_plan(n_img, h, w_, cin_w, cout, 1, 4).splits, 4, cin_w, cout);
+        const long m = tile > generic ? tile : generic;
         return x3 > m ? x3 : m;
     }
-    if (kh == kw && (kh == 1 || kh == 3 || kh == 2)) {       // dilation unknown here: take the larger of the two plans
-        TilePlan p = wgrad_tile_plan(n_img, h, w_, cin_w, cout, kh == 2 ? 1 : kh);
-        if (kh == 2) { p.splits = cdiv(p.splits, 4); p.tps = cdiv(p.total_tiles, p.splits); p.splits = cdiv(p.total_tiles, p.tps); }
-        bool big; int tiles, splits;
-        wgrad_plan((long)n_img * h * w_, cin_w, cout, kh * kw, big, tiles, splits);
-        const long a = p.splits > 1 ? (long)p.splits * kh * kw * cin_w * cout : 0;
-        const long b = splits > 1 ? (long)splits * kh * kw * cin_w * cout : 0;
-        return a > b ? a : b;
+    if (kh == 3 && kw == 3) {                                // the tile plan (dilation 1) or the generic one
+        const long tile = slab_floats(wgrad_tile_plan(n_img, h, w_, cin_w, cout, 3).splits, 9, cin_w, cout);
+        return tile > generic ? tile : generic;
     }
-    bool big; int tiles, splits;
-    wgrad_plan((long)n_img * h * w_, cin_w, cout, kh * kw, big, tiles, splits);
-    return splits > 1 ? (long)splits * kh * kw * cin_w * cout : 0;
+    return generic;
 }
 
 extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ldy, float* dw, float* workspace,
@@ -1115,17 +1254,17 @@ extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ld
     RUNET_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dw % 16) == 0, "pointers must be 16-byte aligned");
     RUNET_REQUIRE((kh == 1 && kw == 1) || (kh == 3 && kw == 3) || (kh == 2 && kw == 2 && transposed), "unsupported kernel size");
     hipStream_t st = (hipStream_t)stream;
+    const long P = (long)n_img * h * w_;
     if (!transposed && kh == 3 && kw == 3 && dil == 1 && cin == 4 && cout <= 1024 && 256 % (cout / 4) == 0) {      // RGB stem
         const int nblk = cdiv(h, STEM_ROWS) * n_img;
         const long wsize = 9L * cin_w * cout;
         RUNET_REQUIRE(workspace && workspace_floats >= nblk * wsize, "workspace too small for the stem weight gradient");
         hipLaunchKernelGGL(stem_wgrad_kernel, dim3(cdiv(h, STEM_ROWS), n_img), dim3(256), 0, st, x, ldx, dy, ldy, workspace, h, w_, cin_w, cout);
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, nblk);
+        reduce_slabs(workspace, dw, wsize, nblk, st);
         RUNET_CHECK_LAUNCH();
     }
-    if (!transposed && kh == 1 && kw == 1 && cin_w == cin && wgrad1x1_direct((long)n_img * h * w_, cin, cout)) {
+    if (!transposed && kh == 1 && kw == 1 && cin_w == cin && wgrad1x1_direct(P, cin, cout)) {
         // register-direct TN GEMM (gemm.hip): both operands are read from HBM in MFMA operand order, no LDS, no VALU
-        const long P = (long)n_img * h * w_;
         const int rps = wgrad1x1_rows_per_split(P, cin, cout);
         const int splits = cdiv(P, rps);
         const long wsize = (long)cin * cout;
@@ -1134,29 +1273,23 @@ extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ld
                            ? runet_gemm_x3_tn_batched(x, ldx, 0, dy, ldy, 0, splits > 1 ? workspace : dw, 1, (int)P, cin, cout, rps, stream)
                            : runet_gemm_tn_launch(x, ldx, 0, dy, ldy, 0, splits > 1 ? workspace : dw, 1, (int)P, cin, cout, rps, st);
         if (rc) return rc;
-        if (splits > 1) hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, splits);
+        if (splits > 1) reduce_slabs(workspace, dw, wsize, splits, st);
         RUNET_CHECK_LAUNCH();
     }
-    if (transposed && cin_w == cin && convt_wgrad_x3((long)n_img * h * w_, w_, cin, cout)) {
+    if (transposed && cin_w == cin && convt_wgrad_x3(P, w_, cin, cout)) {
         // ConvTranspose2d weight gradient on the split-operand TN GEMM (gemm_split.hip): 4 taps = 4 GEMMs over the low-resolution pixels
-        const long P = (long)n_img * h * w_;
-        const long tiles = (long)cdiv(cin, 128) * cdiv(cout, 128) * 4;
-        long splits = cdiv(512, tiles);
-        const long maxs = P / 256 > 0 ? P / 256 : 1;
-        if (splits > maxs) splits = maxs;
-        const int rps = (int)((cdiv(P, splits) + 15) / 16 * 16);
+        const int rps = convt_wgrad_x3_rows_per_split(P, cin, cout);
         const int ns = cdiv(P, rps);
         const long wsize = 4L * cin * cout;
         if (ns == 1 || (workspace && workspace_floats >= ns * wsize)) {
             const int rc = runet_gemm_x3_tn_convt(x, ldx, dy, ldy, ns > 1 ? workspace : dw, n_img, h, w_, cin, cout, rps, stream);
             if (rc) return rc;
-            if (ns > 1) hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, ns);
+            if (ns > 1) reduce_slabs(workspace, dw, wsize, ns, st);
             RUNET_CHECK_LAUNCH();
         }
     }
     if (use_tile_kernel(kh, kw, dil, transposed)) {
-        TilePlan p = wgrad_tile_plan(n_img, h, w_, cin_w, cout, transposed ? 1 : kh);
-        if (transposed) { p.splits = cdiv(p.splits, 4); p.tps = cdiv(p.total_tiles, p.splits); p.splits = cdiv(p.total_tiles, p.tps); }   // 4 taps ride on grid.z
+        TilePlan p = wgrad_tile_plan(n_img, h, w_, cin_w, cout, transposed ? 1 : kh, transposed ? 4 : 1);
         const long wsize = (long)kh * kw * cin_w * cout;
         if (p.splits > 1 && (workspace == nullptr || workspace_floats < p.splits * wsize)) {
             int s2 = workspace ? (int)(workspace_floats / wsize) : 1;
@@ -1174,46 +1307,12 @@ extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ld
         else if (p.tm == 2) launch_wgrad_tile<1, 2, 1>(t, p, st);
         else if (p.tn == 2) launch_wgrad_tile<1, 1, 2>(t, p, st);
         else launch_wgrad_tile<1, 1, 1>(t, p, st);
-        if (p.splits > 1)
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, p.splits);
+        if (p.splits > 1) reduce_slabs(workspace, dw, wsize, p.splits, st);
         RUNET_CHECK_LAUNCH();
     }
-    WGradArgs a{};
-    a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy;
-    a.Kci = cin; a.Kvalid = cin_w; a.Nco = cout;
-    a.Nimg = n_img; a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = kh; a.KW = kw;
-    if (transposed) {
-        a.tap_on_output = 1; a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2;
-    } else {
-        a.tdh = dil; a.tdw = dil; a.bh = -dil * (kh / 2); a.bw = -dil * (kw / 2);
-        a.Hout = h; a.Wout = w_; a.o_scale = 1;
-    }
-    const long P = (long)n_img * h * w_;
-    const int ntaps = kh * kw;
-    bool big; int tiles, splits;
-    wgrad_plan(P, cin_w, cout, ntaps, big, tiles, splits);
-    const long wsize = (long)ntaps * cin_w * cout;
-    if (splits > 1 && (workspace == nullptr || workspace_floats < splits * wsize)) {
-        splits = workspace ? (int)(workspace_floats / wsize) : 1;
-        if (splits < 1) splits = 1;
-    }
-    long pps = (P + splits - 1) / splits;
-    pps = (pps + 15) / 16 * 16;
-    splits = cdiv(P, pps);
-    a.pix_per_split = pps;
-    a.out = (splits > 1) ? workspace : dw;
-    dim3 grid(tiles, ntaps, splits);
-    if (big) {
-        const size_t lds = 2 * (16 * (128 + 4) * 2) * sizeof(float);
-        hipLaunchKernelGGL((wgrad_kernel<128, 128, 64, 64>), grid, dim3(256), lds, st, a);
-    } else {
-        const size_t lds = 2 * (16 * (64 + 4) * 2) * sizeof(float);
-        hipLaunchKernelGGL((wgrad_kernel<64, 64, 32, 32>), grid, dim3(256), lds, st, a);
-    }
-    if (splits > 1) {
-        const int thr = 256;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, splits);
-    }
+    WGradArgs a = wgrad_operands(x, ldx, dy, ldy, n_img, cin, cin_w, cout);      // what is left: 3x3 with dilation > 1
+    wgrad_geom_conv(a, same_conv(h, w_, kh, kw, dil));
+    launch_wgrad_splitk(a, P, cin_w, cout, kh * kw, dw, workspace, workspace_floats, st);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1222,7 +1321,8 @@ extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ld
 // General (strided / large-kernel / k4 transposed) convolutions for the DeepLabV3+ baseline (/root/reference/Main_Final.py:325-433:
 // Conv2d 7x7 s2 p3, 3x3 s2 p1, 3x3 dilation 6/12/18, ConvTranspose2d k4 s2 p1) and SegFormer-Lite (Extended_Baseline_Comparison.py:645,
 // 677-688: Conv2d 7x7 s4 p3 and the key / value reductions, kernel = stride = 8, 4, 2, no padding).  Same kernels, other geometry: kernels
-// up to 8x8, strides up to 8.
+// up to 8x8, strides up to 8.  FWD: x [n,hin,win,cin] -> y [n,ho,wo,cout];  DGRAD: x := dy [n,ho,wo,cin(=conv Cout)] -> y := dx
+// [n,hin,win,cout(=conv Cin)], w [kh,kw,cout,cin].
 extern "C" int runet_conv2d_general(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int hin,
                                     int win, int cin, int cin_w, int cout, int kh, int kw, int stride, int pad, int dil, int mode,
                                     int accumulate, void* stream) {
@@ -1232,41 +1332,16 @@ extern "C" int runet_conv2d_general(const float* x, int ldx, const float* w, con
     RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
     const int ho = (hin + 2 * pad - dil * (kh - 1) - 1) / stride + 1, wo = (win + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
     RUNET_REQUIRE(ho > 0 && wo > 0, "empty output");
-    hipStream_t st = (hipStream_t)stream;
-    // measurement knob (tools/segformer_step.py --kernels): the kernel = stride data gradient through the general a_div form below
-    static const bool no_live_tap = getenv("RUNET_NO_LIVE_TAP_DGRAD") && atoi(getenv("RUNET_NO_LIVE_TAP_DGRAD")) != 0;
-    IGemmArgs a{};
-    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = accumulate; a.KH = kh; a.KW = kw;
-    a.a_div = 1; a.o_scale = 1;
-    if (mode == RUNET_CONV_FWD) {          // x [n,hin,win,cin] -> y [n,ho,wo,cout]
+    if (mode == RUNET_CONV_FWD) {
         RUNET_REQUIRE(ldx >= cin && ldy >= cout, "bad pixel strides");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin_w; a.Ncols = cout;
-        a.w_tap_stride = (long)cin_w * cout; a.w_sk = cout; a.w_sn = 1;
-        a.H = ho; a.W = wo; a.Hin = hin; a.Win = win; a.a_scale = stride; a.tdh = dil; a.tdw = dil; a.bh = -pad; a.bw = -pad;
-        a.Hout = ho; a.Wout = wo;
-        dispatch_igemm<false>(a, 1, st);
-    } else if (mode == RUNET_CONV_DGRAD && kh == stride && kw == stride && stride > 1 && pad == 0 && dil == 1 && hin == ho * stride &&
-               win == wo * stride && !no_live_tap) {
-        // kernel = stride, no padding (SegFormer-Lite's key / value reductions): each dx pixel has exactly one live tap, the one at its position
-        // modulo the stride, so the data gradient is s^2 GEMMs dy [pixels, cin] . w_tap^T [cin, cout] whose rows land on the pixels
-        // (h * s + r, w * s + c) of tap (r, c) = blockIdx.z: a GEMM plus a permutation, the k2-s2 transposed forward's z_taps form.  The general
-        // form below would run all s^2 taps through the matrix loop for every pixel (a_div masking), s^2 - 1 of them dead.
+    } else if (mode == RUNET_CONV_DGRAD) {
         RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
-        a.H = ho; a.W = wo; a.Hin = ho; a.Win = wo; a.a_scale = 1; a.KH = 1; a.KW = 1;
-        a.Hout = hin; a.Wout = win; a.o_scale = stride; a.z_taps = stride;
-        dispatch_igemm<true>(a, stride * stride, st);
-    } else if (mode == RUNET_CONV_DGRAD) { // x := dy [n,ho,wo,cin(=conv Cout)] -> y := dx [n,hin,win,cout(=conv Cin)]; w [kh,kw,cout,cin]
-        RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
-        a.H = hin; a.W = win; a.Hin = ho; a.Win = wo; a.a_scale = 1; a.tdh = -dil; a.tdw = -dil; a.bh = pad; a.bw = pad; a.a_div = stride;
-        a.Hout = hin; a.Wout = win;
-        dispatch_igemm<true>(a, 1, st);
     } else {
         RUNET_REQUIRE(false, "mode must be RUNET_CONV_FWD or RUNET_CONV_DGRAD");
     }
+    IGemmArgs a = igemm_operands(x, ldx, w, bias, y, ldy, n_img, cin, cin_w, cout, accumulate);
+    const int gz = conv2d_args(a, {hin, win, ho, wo, kh, kw, stride, pad, pad, dil, dil}, mode);
+    dispatch_igemm(a, gz, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1275,32 +1350,21 @@ extern "C" int runet_convt4_igemm(const float* x, int ldx, const float* w, const
                                   int cin, int cout, int mode, int accumulate, void* stream) {
     RUNET_REQUIRE(x && w && y && cin % 4 == 0 && cout % 4 == 0 && cin > 0 && cout > 0, "bad arguments");
     RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
-    hipStream_t st = (hipStream_t)stream;
-    IGemmArgs a{};
-    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = accumulate; a.a_div = 1;
-    a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout; a.H = h; a.W = w_;
-    if (mode == RUNET_CONVT_FWD) {
-        a.w_tap_stride = (long)cin * cout; a.w_sk = cout; a.w_sn = 1;
-        a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = 2; a.KW = 2; a.zmode4 = 1;
-        a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2;
-        dispatch_igemm<false>(a, 4, st);
-    } else if (mode == RUNET_CONVT_DGRAD) {
-        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
-        a.Hin = 2 * h; a.Win = 2 * w_; a.a_scale = 2; a.KH = 4; a.KW = 4; a.tdh = 1; a.tdw = 1; a.bh = -1; a.bw = -1;
-        a.Hout = h; a.Wout = w_; a.o_scale = 1;
-        dispatch_igemm<true>(a, 1, st);
-    } else {
-        RUNET_REQUIRE(false, "mode must be RUNET_CONVT_FWD or RUNET_CONVT_DGRAD");
-    }
+    if (mode != RUNET_CONVT_FWD && mode != RUNET_CONVT_DGRAD) RUNET_REQUIRE(false, "mode must be RUNET_CONVT_FWD or RUNET_CONVT_DGRAD");
+    IGemmArgs a = igemm_operands(x, ldx, w, bias, y, ldy, n_img, cin, cin, cout, accumulate);
+    const int gz = convt4_args(a, h, w_, mode);
+    dispatch_igemm(a, gz, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }
 
 // runet_convt4_igemm(RUNET_CONVT_FWD) + the BatchNorm statistics partials of y for runet_bn_stats_finalize: one part per tile and parity
 // class (the tile's output pixels of one (ph, pw) class), stats [runet_convt4_igemm_stats_parts(...)][cout][3] = (count, mean, M2).
+// Same builder, same route, hence the tile variant, grid and y of the plain call; the loader is the general one (zmode4).
 extern "C" int runet_convt4_igemm_stats_parts(int n_img, int h, int w_, int cout) {
     if (n_img <= 0 || h <= 0 || w_ <= 0 || cout <= 0) return 0;
-    const long P = (long)n_img * h * w_;
-    return 4 * cdiv(P, variant_bm(convt4_fwd_variant(P, cout)));
+    IGemmArgs a = igemm_operands(nullptr, 0, nullptr, nullptr, nullptr, 0, n_img, 4, 4, cout, 0);      // the route of this geometry does not look at cin
+    const int gz = convt4_args(a, h, w_, RUNET_CONVT_FWD);
+    return gz * cdiv((long)n_img * h * w_, variant_bm(igemm_route(a).variant));
 }
 
 extern "C" int runet_convt4_igemm_stats(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int h, int w_,
@@ -1310,27 +1374,18 @@ extern "C" int runet_convt4_igemm_stats(const float* x, int ldx, const float* w,
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0 && ldx >= cin && ldy >= cout, "bad shape");
     RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
     hipStream_t st = (hipStream_t)stream;
-    IGemmArgs a{};      // exactly runet_convt4_igemm's RUNET_CONVT_FWD arguments
-    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = 0; a.a_div = 1;
-    a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout; a.H = h; a.W = w_;
-    a.w_tap_stride = (long)cin * cout; a.w_sk = cout; a.w_sn = 1;
-    a.Hin = h; a.Win = w_; a.a_scale = 1; a.KH = 2; a.KW = 2; a.zmode4 = 1;
-    a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2;
-    switch (convt4_fwd_variant((long)n_img * h * w_, cout)) {
-    case V_128x32: launch_igemm_stats<128, 32, 32, 32>(a, 4, stats, st); break;
-    case V_256x64: launch_igemm_stats<256, 64, 64, 64>(a, 4, stats, st); break;
-    case V_128x64: launch_igemm_stats<128, 64, 64, 32>(a, 4, stats, st); break;
-    case V_128x128: launch_igemm_stats<128, 128, 64, 64>(a, 4, stats, st); break;
-    case V_64x64: launch_igemm_stats<64, 64, 32, 32>(a, 4, stats, st); break;
-    }
+    IGemmArgs a = igemm_operands(x, ldx, w, bias, y, ldy, n_img, cin, cin, cout, 0);
+    const int gz = convt4_args(a, h, w_, RUNET_CONVT_FWD);
+    with_tile(igemm_route(a).variant, [&](auto t) {
+        using T = decltype(t);
+        launch_igemm<T::BM, T::BN, T::WM, T::WN, false, false>(a, gz, st, stats);
+    });
     RUNET_CHECK_LAUNCH();
 }
 
 // weight gradient for the general geometries (per-tap split-K kernel).  transposed4 != 0: ConvTranspose2d(k4,s2,p1), x [n,h,w,cin], dy [n,2h,2w,cout].
 extern "C" long runet_conv_wgrad_general_workspace_floats(int pixels, int cin_w, int cout, int kh, int kw) {
-    bool big; int tiles, splits;
-    wgrad_plan(pixels, cin_w, cout, kh * kw, big, tiles, splits);
-    return splits > 1 ? (long)splits * kh * kw * cin_w * cout : 0;
+    return wgrad_workspace(pixels, cin_w, cout, kh * kw);
 }
 
 extern "C" int runet_conv_wgrad_general(const float* x, int ldx, const float* dy, int ldy, float* dw, float* workspace, long workspace_floats,
@@ -1339,44 +1394,22 @@ extern "C" int runet_conv_wgrad_general(const float* x, int ldx, const float* dy
     RUNET_REQUIRE(x && dy && dw, "null pointer");
     RUNET_REQUIRE(cin % 4 == 0 && cin_w > 0 && cin_w <= cin && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "channel counts / strides must be multiples of 4");
     RUNET_REQUIRE(transposed4 || (kh >= 1 && kh <= 8 && kw >= 1 && kw <= 8 && stride >= 1 && stride <= 8 && pad >= 0 && dil >= 1), "unsupported geometry");
-    hipStream_t st = (hipStream_t)stream;
-    WGradArgs a{};
-    a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy; a.Kci = cin; a.Kvalid = cin_w; a.Nco = cout; a.Nimg = n_img; a.KH = kh; a.KW = kw;
+    if (transposed4) RUNET_REQUIRE(kh == 4 && kw == 4, "transposed4 is the k4-s2-p1 transposed convolution");
+    WGradArgs a = wgrad_operands(x, ldx, dy, ldy, n_img, cin, cin_w, cout);
     long P;
     if (transposed4) {
-        RUNET_REQUIRE(kh == 4 && kw == 4, "transposed4 is the k4-s2-p1 transposed convolution");
-        a.H = hin; a.W = win; a.Hin = hin; a.Win = win; a.a_scale = 1; a.tap_on_output = 1; a.o_bh = -1; a.o_bw = -1;
-        a.Hout = 2 * hin; a.Wout = 2 * win; a.o_scale = 2;
-        P = (long)n_img * hin * win;
+        P = wgrad_geom_convt4(a, hin, win);
     } else {
         const int ho = (hin + 2 * pad - dil * (kh - 1) - 1) / stride + 1, wo = (win + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
-        a.H = ho; a.W = wo; a.Hin = hin; a.Win = win; a.a_scale = stride; a.tdh = dil; a.tdw = dil; a.bh = -pad; a.bw = -pad;
-        a.Hout = ho; a.Wout = wo; a.o_scale = 1;
-        P = (long)n_img * ho * wo;
+        P = wgrad_geom_conv(a, {hin, win, ho, wo, kh, kw, stride, pad, pad, dil, dil});
     }
-    const int ntaps = kh * kw;
-    bool big; int tiles, splits;
-    wgrad_plan(P, cin_w, cout, ntaps, big, tiles, splits);
-    const long wsize = (long)ntaps * cin_w * cout;
-    if (splits > 1 && (workspace == nullptr || workspace_floats < splits * wsize)) {
-        splits = workspace ? (int)(workspace_floats / wsize) : 1;
-        if (splits < 1) splits = 1;
-    }
-    long pps = (P + splits - 1) / splits;
-    pps = (pps + 15) / 16 * 16;
-    splits = cdiv(P, pps);
-    a.pix_per_split = pps;
-    a.out = (splits > 1) ? workspace : dw;
-    dim3 grid(tiles, ntaps, splits);
-    if (big) hipLaunchKernelGGL((wgrad_kernel<128, 128, 64, 64>), grid, dim3(256), 2 * (16 * (128 + 4) * 2) * sizeof(float), st, a);
-    else hipLaunchKernelGGL((wgrad_kernel<64, 64, 32, 32>), grid, dim3(256), 2 * (16 * (64 + 4) * 2) * sizeof(float), st, a);
-    if (splits > 1) hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, splits);
+    launch_wgrad_splitk(a, P, cin_w, cout, kh * kw, dw, workspace, workspace_floats, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }
 
 // Rectangular kernels with per-axis padding and dilation for the ENet baseline (comne.py:482-608: the asymmetric bottleneck's Conv2d (5, 1)
-// padding (2, 0) and (1, 5) padding (0, 2)).  runet_conv2d_general's contract and kernels with (pad_h, pad_w) and (dil_h, dil_w): the geometry
-// struct carries the two axes separately, so this is launcher work only.  Equal pads and dilations give runet_conv2d_general's launches and bits.
+// padding (2, 0) and (1, 5) padding (0, 2)).  runet_conv2d_general's contract with (pad_h, pad_w) and (dil_h, dil_w): both go through
+// conv2d_args, so equal pads and dilations give runet_conv2d_general's launches and bits.
 extern "C" int runet_conv2d_rect(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n_img, int hin, int win,
                                  int cin, int cin_w, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int dil_h, int dil_w, int mode,
                                  int accumulate, void* stream) {
@@ -1388,37 +1421,16 @@ extern "C" int runet_conv2d_rect(const float* x, int ldx, const float* w, const 
     RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
     const int ho = (hin + 2 * pad_h - dil_h * (kh - 1) - 1) / stride + 1, wo = (win + 2 * pad_w - dil_w * (kw - 1) - 1) / stride + 1;
     RUNET_REQUIRE(hin + 2 * pad_h - dil_h * (kh - 1) > 0 && win + 2 * pad_w - dil_w * (kw - 1) > 0 && ho > 0 && wo > 0, "empty output");
-    hipStream_t st = (hipStream_t)stream;
-    static const bool no_live_tap = getenv("RUNET_NO_LIVE_TAP_DGRAD") && atoi(getenv("RUNET_NO_LIVE_TAP_DGRAD")) != 0;
-    IGemmArgs a{};
-    a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.accumulate = accumulate; a.KH = kh; a.KW = kw;
-    a.a_div = 1; a.o_scale = 1;
-    if (mode == RUNET_CONV_FWD) {          // x [n,hin,win,cin] -> y [n,ho,wo,cout]
+    if (mode == RUNET_CONV_FWD) {
         RUNET_REQUIRE(ldx >= cin && ldy >= cout, "bad pixel strides");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin_w; a.Ncols = cout;
-        a.w_tap_stride = (long)cin_w * cout; a.w_sk = cout; a.w_sn = 1;
-        a.H = ho; a.W = wo; a.Hin = hin; a.Win = win; a.a_scale = stride; a.tdh = dil_h; a.tdw = dil_w; a.bh = -pad_h; a.bw = -pad_w;
-        a.Hout = ho; a.Wout = wo;
-        dispatch_igemm<false>(a, 1, st);
-    } else if (mode == RUNET_CONV_DGRAD && kh == stride && kw == stride && stride > 1 && pad_h == 0 && pad_w == 0 && dil_h == 1 && dil_w == 1 &&
-               hin == ho * stride && win == wo * stride && !no_live_tap) {
-        // kernel = stride, no padding: one live tap per dx pixel (runet_conv2d_general's form of it)
+    } else if (mode == RUNET_CONV_DGRAD) {
         RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
-        a.H = ho; a.W = wo; a.Hin = ho; a.Win = wo; a.a_scale = 1; a.KH = 1; a.KW = 1;
-        a.Hout = hin; a.Wout = win; a.o_scale = stride; a.z_taps = stride;
-        dispatch_igemm<true>(a, stride * stride, st);
-    } else if (mode == RUNET_CONV_DGRAD) { // x := dy [n,ho,wo,cin(=conv Cout)] -> y := dx [n,hin,win,cout(=conv Cin)]; w [kh,kw,cout,cin]
-        RUNET_REQUIRE(cin_w == cin && ldx >= cin && ldy >= cout, "bad arguments for the data gradient");
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cout * cin; a.w_sk = 1; a.w_sn = cin;
-        a.H = hin; a.W = win; a.Hin = ho; a.Win = wo; a.a_scale = 1; a.tdh = -dil_h; a.tdw = -dil_w; a.bh = pad_h; a.bw = pad_w; a.a_div = stride;
-        a.Hout = hin; a.Wout = win;
-        dispatch_igemm<true>(a, 1, st);
     } else {
         RUNET_REQUIRE(false, "mode must be RUNET_CONV_FWD or RUNET_CONV_DGRAD");
     }
+    IGemmArgs a = igemm_operands(x, ldx, w, bias, y, ldy, n_img, cin, cin_w, cout, accumulate);
+    const int gz = conv2d_args(a, {hin, win, ho, wo, kh, kw, stride, pad_h, pad_w, dil_h, dil_w}, mode);
+    dispatch_igemm(a, gz, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1447,27 +1459,19 @@ extern "C" int runet_convt3_fwd(const float* x, int ldx, const float* wq, const 
     RUNET_REQUIRE(n_img > 0 && h > 0 && w_ > 0, "empty shape");
     RUNET_REQUIRE(ldx >= cin && ldy >= cout, "bad pixel strides");
     RUNET_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wq % 16) == 0 && ((uintptr_t)y % 16) == 0, "alignment");
-    hipStream_t st = (hipStream_t)stream;
     static const int first_tap[4] = {0, 1, 3, 5};
     for (int cls = 0; cls < 4; ++cls) {
-        const int ph = cls >> 1, pw = cls & 1;
-        IGemmArgs a{};
-        a.x = x; a.ldx = ldx; a.w = wq + (long)first_tap[cls] * cin * cout; a.bias = bias; a.y = y; a.ldy = ldy; a.Nimg = n_img; a.a_div = 1;
-        a.K = (cin + 15) / 16 * 16; a.Kx = cin; a.Kvalid = cin; a.Ncols = cout;
-        a.w_tap_stride = (long)cin * cout; a.w_sk = cout; a.w_sn = 1;
-        a.H = h; a.W = w_; a.Hin = h; a.Win = w_; a.a_scale = 1;
-        a.KH = ph ? 2 : 1; a.KW = pw ? 2 : 1; a.tdh = ph ? -1 : 0; a.tdw = pw ? -1 : 0; a.bh = ph; a.bw = pw;
-        a.Hout = 2 * h; a.Wout = 2 * w_; a.o_scale = 2; a.o_dh = ph; a.o_dw = pw;
-        dispatch_igemm<false>(a, 1, st);
+        IGemmArgs a = igemm_operands(x, ldx, wq + (long)first_tap[cls] * cin * cout, bias, y, ldy, n_img, cin, cin, cout, 0);
+        weights_n_contig(a);
+        const int gz = geom_convt3_class(a, h, w_, cls >> 1, cls & 1);
+        dispatch_igemm(a, gz, (hipStream_t)stream);
     }
     RUNET_CHECK_LAUNCH();
 }
 
 extern "C" long runet_conv_wgrad_rect_workspace_floats(int pixels, int cin_w, int cout, int kh, int kw) {
     if (pixels <= 0 || cin_w <= 0 || cout <= 0 || kh < 1 || kh > 8 || kw < 1 || kw > 8) return -1;
-    bool big; int tiles, splits;
-    wgrad_plan(pixels, cin_w, cout, kh * kw, big, tiles, splits);
-    return splits > 1 ? (long)splits * kh * kw * cin_w * cout : 0;
+    return wgrad_workspace(pixels, cin_w, cout, kh * kw);
 }
 
 extern "C" int runet_conv_wgrad_rect(const float* x, int ldx, const float* dy, int ldy, float* dw, float* workspace, long workspace_floats,
@@ -1483,29 +1487,9 @@ extern "C" int runet_conv_wgrad_rect(const float* x, int ldx, const float* dy, i
     RUNET_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)workspace % 16) == 0, "alignment");
     const int ho = (hin + 2 * pad_h - dil_h * (kh - 1) - 1) / stride + 1, wo = (win + 2 * pad_w - dil_w * (kw - 1) - 1) / stride + 1;
     RUNET_REQUIRE(hin + 2 * pad_h - dil_h * (kh - 1) > 0 && win + 2 * pad_w - dil_w * (kw - 1) > 0 && ho > 0 && wo > 0, "empty output");
-    hipStream_t st = (hipStream_t)stream;
-    WGradArgs a{};
-    a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy; a.Kci = cin; a.Kvalid = cin_w; a.Nco = cout; a.Nimg = n_img; a.KH = kh; a.KW = kw;
-    a.H = ho; a.W = wo; a.Hin = hin; a.Win = win; a.a_scale = stride; a.tdh = dil_h; a.tdw = dil_w; a.bh = -pad_h; a.bw = -pad_w;
-    a.Hout = ho; a.Wout = wo; a.o_scale = 1;
-    const long P = (long)n_img * ho * wo;
-    const int ntaps = kh * kw;
-    bool big; int tiles, splits;
-    wgrad_plan(P, cin_w, cout, ntaps, big, tiles, splits);
-    const long wsize = (long)ntaps * cin_w * cout;
-    if (splits > 1 && (workspace == nullptr || workspace_floats < splits * wsize)) {
-        splits = workspace ? (int)(workspace_floats / wsize) : 1;
-        if (splits < 1) splits = 1;
-    }
-    long pps = (P + splits - 1) / splits;
-    pps = (pps + 15) / 16 * 16;
-    splits = cdiv(P, pps);
-    a.pix_per_split = pps;
-    a.out = (splits > 1) ? workspace : dw;
-    dim3 grid(tiles, ntaps, splits);
-    if (big) hipLaunchKernelGGL((wgrad_kernel<128, 128, 64, 64>), grid, dim3(256), 2 * (16 * (128 + 4) * 2) * sizeof(float), st, a);
-    else hipLaunchKernelGGL((wgrad_kernel<64, 64, 32, 32>), grid, dim3(256), 2 * (16 * (64 + 4) * 2) * sizeof(float), st, a);
-    if (splits > 1) hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(wsize, 32 * 4)), dim3(256), 0, st, workspace, dw, wsize, splits);
+    WGradArgs a = wgrad_operands(x, ldx, dy, ldy, n_img, cin, cin_w, cout);
+    const long P = wgrad_geom_conv(a, {hin, win, ho, wo, kh, kw, stride, pad_h, pad_w, dil_h, dil_w});
+    launch_wgrad_splitk(a, P, cin_w, cout, kh * kw, dw, workspace, workspace_floats, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1514,18 +1498,31 @@ extern "C" int runet_conv_wgrad_rect(const float* x, int ldx, const float* dy, i
 // Batched plain GEMMs on the same kernels (the 36 position-GEMMs of the unfused Winograd F(4x4,3x3) path, conv_winograd4.hip).
 //   runet_gemm_batched   : C[z][rows][n] = A[z][rows][k] . B[z][k][n]                (blockIdx.z = z)
 //   runet_gemm_tn_batched: C[split][z][k][n] = sum over the split's rows of A[z][row][k] * B[z][row][n];  splits = ceil(rows / rows_per_split)
-// which device kernel runet_gemm_batched launches for a shape (live profiling labels must match the rocprofv3 kernel names)
-extern "C" const char* runet_gemm_batched_kernel_name(int batch, int rows, int k, int n) {
-    static const bool old_path = getenv("RUNET_GEMM_OLD") != nullptr;
+// RUNET_GEMM_OLD: A/B switch for tools/bench_gemm.py, set at all, whatever the value
+static bool gemm_old_path() { static const bool old_path = getenv("RUNET_GEMM_OLD") != nullptr; return old_path; }
+// what runet_gemm_batched launches for a shape: an igemm tile variant, or GEMM_NN = gemm.hip's gemm_nn_kernel
+constexpr int GEMM_NN = 5;
+static int gemm_batched_route(int batch, int rows, int n) {
     const long b128 = (long)cdiv(rows, 128) * cdiv(n, 128) * batch;
-    const double per_cu = b128 / 256.0, bal = per_cu / (double)((b128 + 255) / 256);
-    const bool fast = k % 16 == 0 && k >= 16 && n >= 4;       // the FAST / SIMPLE instantiations (last template argument)
-    if (!old_path && bal < 0.8 && n % 64 == 0) return fast ? "igemm_kernel<128, 64, 64, 32, false, true>" : "igemm_kernel<128, 64, 64, 32, false, false>";
-    if (!old_path && n >= 96) return fast ? "gemm_nn_kernel<16, true>" : "gemm_nn_kernel<16, false>";
-    if (n % 128 == 0 && b128 >= 256) return fast ? "igemm_kernel<128, 128, 64, 64, false, true>" : "igemm_kernel<128, 128, 64, 64, false, false>";
-    if (n > 32 && (long)cdiv(rows, 128) * cdiv(n, 64) * batch >= 256) return fast ? "igemm_kernel<128, 64, 64, 32, false, true>" : "igemm_kernel<128, 64, 64, 32, false, false>";
-    if (n > 32) return fast ? "igemm_kernel<64, 64, 32, 32, false, true>" : "igemm_kernel<64, 64, 32, 32, false, false>";
-    return fast ? "igemm_kernel<128, 32, 32, 32, false, true>" : "igemm_kernel<128, 32, 32, 32, false, false>";
+    if (!gemm_old_path()) {
+        // 128x64 tiles where 128x128 tiles would fill the 256 CUs unevenly (e.g. 576 blocks = 2.25 per CU -> 3 rounds for 2.25 of work)
+        const double per_cu = b128 / 256.0, bal = per_cu / (double)((b128 + 255) / 256);
+        if (bal < 0.8 && n % 64 == 0) return V_128x64;
+        if (n >= 96) return GEMM_NN;
+    }
+    if (n % 128 == 0 && b128 >= 256) return V_128x128;      // n % 128 == 0 is n >= 96: reachable only with RUNET_GEMM_OLD set
+    if (n > 32 && (long)cdiv(rows, 128) * cdiv(n, 64) * batch >= 256) return V_128x64;
+    if (n > 32) return V_64x64;
+    return V_128x32;
+}
+
+// which device kernel runet_gemm_batched launches for a shape (live profiling labels must match the rocprofv3 kernel names).  `fast` is the
+// last template argument of either kernel; for the igemm it is what igemm_route finds for these operands, RUNET_IGEMM_GENERAL aside.
+extern "C" const char* runet_gemm_batched_kernel_name(int batch, int rows, int k, int n) {
+    const bool fast = k % 16 == 0 && k >= 16 && n >= 4;
+    const int route = gemm_batched_route(batch, rows, n);
+    if (route == GEMM_NN) return fast ? "gemm_nn_kernel<16, true>" : "gemm_nn_kernel<16, false>";
+    return IGEMM_NAMES[0][fast][route];
 }
 
 extern "C" int runet_gemm_batched(const float* a, int lda, long stride_a, const float* b, long stride_b, float* c, int ldc, long stride_c,
@@ -1534,29 +1531,18 @@ extern "C" int runet_gemm_batched(const float* a, int lda, long stride_a, const 
     RUNET_REQUIRE(k > 0 && k % 4 == 0 && n > 0 && n % 4 == 0 && lda >= k && lda % 4 == 0 && ldc >= n && ldc % 4 == 0, "k, n and the row strides must be multiples of 4");
     RUNET_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0 && ((uintptr_t)c % 16) == 0 && stride_a % 4 == 0 && stride_b % 4 == 0 && stride_c % 4 == 0,
                   "alignment");
-    IGemmArgs g{};
-    g.x = a; g.ldx = lda; g.w = b; g.y = c; g.ldy = ldc; g.K = (k + 15) / 16 * 16; g.Kx = k; g.Kvalid = k; g.Ncols = n;
-    g.w_sk = n; g.w_sn = 1; g.Nimg = 1; g.H = 1; g.W = rows; g.Hin = 1; g.Win = rows; g.a_scale = 1; g.KH = 1; g.KW = 1;
-    g.Hout = 1; g.Wout = rows; g.o_scale = 1; g.zbatch = 1; g.zs_x = stride_a; g.zs_w = stride_b; g.zs_y = stride_c;
     hipStream_t st = (hipStream_t)stream;
-    static const bool old_path = getenv("RUNET_GEMM_OLD") != nullptr;      // A/B switch for tools/bench_gemm.py
-    {   // 128x64 tiles where 128x128 tiles would fill the 256 CUs unevenly (e.g. 576 blocks = 2.25 per CU -> 3 rounds for 2.25 of work)
-        const long b128 = (long)cdiv(rows, 128) * cdiv(n, 128) * batch;
-        const double per_cu = b128 / 256.0, bal = per_cu / (double)((b128 + 255) / 256);
-        if (!old_path && bal < 0.8 && n % 64 == 0) {
-            launch_igemm<128, 64, 64, 32, false>(g, batch, st);
-            RUNET_CHECK_LAUNCH();
-        }
-    }
-    if (!old_path && n >= 96) {
+    const int route = gemm_batched_route(batch, rows, n);
+    if (route == GEMM_NN) {
         runet_gemm_nn_launch(a, lda, stride_a, b, stride_b, c, ldc, stride_c, batch, rows, k, n, st);
         RUNET_CHECK_LAUNCH();
     }
-    const long b128 = (long)cdiv(rows, 128) * cdiv(n, 128) * batch;
-    if (n % 128 == 0 && b128 >= 256) launch_igemm<128, 128, 64, 64, false>(g, batch, st);
-    else if (n > 32 && (long)cdiv(rows, 128) * cdiv(n, 64) * batch >= 256) launch_igemm<128, 64, 64, 32, false>(g, batch, st);
-    else if (n > 32) launch_igemm<64, 64, 32, 32, false>(g, batch, st);
-    else launch_igemm<128, 32, 32, 32, false>(g, batch, st);
+    IGemmArgs g = igemm_operands(a, lda, b, nullptr, c, ldc, 1, k, k, n, 0);
+    weights_n_contig(g);
+    const int gz = geom_gemm_batch(g, rows, batch, stride_a, stride_b, stride_c);
+    IGemmRoute r = igemm_route(g);      // for the loader; the tile is this function's own choice
+    r.variant = (IGemmVariant)route;
+    launch_route(g, r, gz, st);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1567,21 +1553,19 @@ extern "C" int runet_gemm_tn_batched(const float* a, int lda, long stride_a, con
     RUNET_REQUIRE(splits <= 65535, "too many splits");
     RUNET_REQUIRE(k > 0 && k % 4 == 0 && n > 0 && n % 4 == 0 && lda >= k && lda % 4 == 0 && ldb >= n && ldb % 4 == 0, "k, n and the row strides must be multiples of 4");
     RUNET_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0 && ((uintptr_t)c % 16) == 0 && stride_a % 4 == 0 && stride_b % 4 == 0, "alignment");
-    WGradArgs g{};
-    g.x = a; g.ldx = lda; g.dy = b; g.ldy = ldb; g.out = c; g.Kci = k; g.Kvalid = k; g.Nco = n;
-    g.Nimg = 1; g.H = 1; g.W = rows; g.Hin = 1; g.Win = rows; g.a_scale = 1; g.KH = batch; g.KW = 1; g.Hout = 1; g.Wout = rows; g.o_scale = 1;
-    g.tap_bs_x = stride_a; g.tap_bs_dy = stride_b;
-    g.pix_per_split = rows_per_split;
     hipStream_t st = (hipStream_t)stream;
     const bool big = k > 64 && n > 64;
-    static const bool old_path = getenv("RUNET_GEMM_OLD") != nullptr;
-    if (!old_path && big) {
+    if (!gemm_old_path() && big) {
         runet_gemm_tn_launch(a, lda, stride_a, b, ldb, stride_b, c, batch, rows, k, n, rows_per_split, st);
         RUNET_CHECK_LAUNCH();
     }
-    const int tiles = big ? cdiv(k, 128) * cdiv(n, 128) : cdiv(k, 64) * cdiv(n, 64);
-    dim3 grid(tiles, batch, splits);
-    if (big) hipLaunchKernelGGL((wgrad_kernel<128, 128, 64, 64>), grid, dim3(256), 2 * (16 * (128 + 4) * 2) * sizeof(float), st, g);
-    else hipLaunchKernelGGL((wgrad_kernel<64, 64, 32, 32>), grid, dim3(256), 2 * (16 * (64 + 4) * 2) * sizeof(float), st, g);
+    // the batch rides on the tap axis: "tap" t reads a + t stride_a and b + t stride_b, no spatial shift
+    WGradArgs g = wgrad_operands(a, lda, b, ldb, 1, k, k, n);
+    g.out = c;
+    g.H = 1; g.W = rows; g.Hin = 1; g.Win = rows; g.a_scale = 1; g.KH = batch; g.KW = 1; g.Hout = 1; g.Wout = rows; g.o_scale = 1;
+    g.tap_bs_x = stride_a; g.tap_bs_dy = stride_b;
+    g.pix_per_split = rows_per_split;
+    launch_wgrad_tiles(g, big, k, n, batch, splits, st);
     RUNET_CHECK_LAUNCH();
 }
+

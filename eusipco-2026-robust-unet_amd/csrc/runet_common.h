@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -36,6 +37,10 @@ extern "C" void runet_set_error(const char* msg);
     } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Environment knobs (measurement and A/B switches).  Callers keep the value in a function-local static: read once per process.
+static inline bool env_flag(const char* name) { const char* v = getenv(name); return v && atoi(v) != 0; }                 // set and non-zero
+static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 
 // Threads per block of the helpers below that fix a block shape (ew_grid, sum_parts, block_rows_to_part); every kernel file's own TPB.
 constexpr int RUNET_TPB = 256;
