@@ -1,8 +1,9 @@
-// Prediction-side byte kernels (predict_coastline.py:358-363, 387-396, 595-602): u8 scene -> normalised NHWC tiles, arg-max of the head's NHWC
-// output stitched into a u8 scene mask, OpenCV's INTER_NEAREST index rule on u8 masks, and the elliptical dilation minus the mask with its two
-// pixel counts.  All four stream bytes: masks are dense [h][w] u8, every lane owns 16 consecutive mask bytes that are 16-byte aligned IN MEMORY
-// (a row of a 1531-wide mask starts at any alignment, so groups are cut on addresses, not on columns) and writes them with one 16-byte store;
-// only the groups cut by a row end, a tile edge or a core edge fall back to byte stores.
+// Prediction-side byte kernels (predict_coastline.py:358-363, 387-396, 595-602; Main_Final.py:521 for the probability models): u8 scene ->
+// normalised tiles (NHWC-4 for the plain U-Net's stem, planar NCHW for every other model), arg-max of the head's NHWC output or `prob > threshold`
+// of a 1-channel probability map stitched into a u8 scene mask, OpenCV's INTER_NEAREST index rule on u8 masks, and the elliptical dilation minus
+// the mask with its two pixel counts.  All of them stream bytes: masks are dense [h][w] u8, every lane owns 16 consecutive mask bytes that are
+// 16-byte aligned IN MEMORY (a row of a 1531-wide mask starts at any alignment, so groups are cut on addresses, not on columns) and writes them
+// with one 16-byte store; only the groups cut by a row end, a tile edge or a core edge fall back to byte stores.
 #include "runet_common.h"
 #include "../../include/runet_hip.h"
 #include <math.h>
@@ -25,9 +26,10 @@ __device__ __forceinline__ void store_group(unsigned char* row, int x0, int lo, 
     }
 }
 
-// ---- u8 HWC scene -> [n_tiles][T][T][4] fp32, ToTensor + Normalize in their own order of roundings ----
+// ---- u8 HWC scene -> [n_tiles][T][T][4] fp32 (PLANAR: [n_tiles][3][T][T]), ToTensor + Normalize in their own order of roundings ----
 struct NormCoef { float mean[3], std[3]; };
 
+template <bool PLANAR>
 __global__ void scene_to_tiles_kernel(const unsigned char* __restrict__ scene, int h, int w, long row_stride, const int* __restrict__ origins,
                                       int tile, float* __restrict__ out, NormCoef nc) {
 #pragma clang fp contract(off)
@@ -42,7 +44,13 @@ __global__ void scene_to_tiles_kernel(const unsigned char* __restrict__ scene, i
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = ((float)s[c] / 255.0f - nc.mean[c]) / nc.std[c];
     }
-    *reinterpret_cast<f32x4*>(out + ((long)t * tile * tile + p) * 4) = v;
+    if constexpr (PLANAR) {                                      // a wave writes 256 consecutive bytes of each of the three planes
+        const long plane = (long)tile * tile;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[((long)t * 3 + c) * plane + p] = v[c];
+    } else {
+        *reinterpret_cast<f32x4*>(out + ((long)t * tile * tile + p) * 4) = v;
+    }
 }
 
 // ---- arg-max over the head's 4-float pixels, core of each tile -> scene mask ----
@@ -56,10 +64,32 @@ __device__ __forceinline__ int argmax4(const f32x4 v, int classes) {
     return best;
 }
 
-// one wave per core row, 256 address-aligned mask bytes per wave: four coalesced 16-byte logit reads per lane, the class bytes meet in LDS and
+// The two per-pixel rules of the stitch.  `at` = index of the pixel in the network's output counted in pixels (tile, row and column), `to` =
+// index of the same pixel in the scene.
+struct ArgmaxPx {                                                // four coalesced 16-byte logit reads per lane
+    const float* z4;
+    int classes;
+    __device__ __forceinline__ unsigned char operator()(long at, long to) const {
+        return (unsigned char)argmax4(*reinterpret_cast<const f32x4*>(z4 + at * 4), classes);
+    }
+};
+// torch's `prob > threshold` on an fp32 tensor: an ordered compare, so NaN is 0 (land) where arg-max lets NaN win; +Inf is 1, the threshold
+// itself 0.  The soft map takes the probability's bits as they are, NaN included.
+struct ThresholdPx {                                             // four coalesced dword reads (and soft-map writes) per lane
+    const float* prob;
+    float* soft;
+    float threshold;
+    __device__ __forceinline__ unsigned char operator()(long at, long to) const {
+        const float p = prob[at];
+        if (soft) soft[to] = p;
+        return p > threshold ? 1 : 0;
+    }
+};
+
+// one wave per core row, 256 address-aligned mask bytes per wave: the lanes read their pixels coalesced (px), the mask bytes meet in LDS and
 // lanes 0..15 store 16 of them each
-__global__ void argmax_stitch_kernel(const float* __restrict__ z4, int tile, int classes, const int* __restrict__ origins, int halo,
-                                     unsigned char* __restrict__ mask, int h, int w) {
+template <class Px>
+__global__ void stitch_kernel(const Px px, int tile, const int* __restrict__ origins, int halo, unsigned char* __restrict__ mask, int h, int w) {
     __shared__ __attribute__((aligned(16))) unsigned char cls[4][256];
     const int t = blockIdx.z, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long oy = origins[2 * t], ox = origins[2 * t + 1];
@@ -75,12 +105,12 @@ __global__ void argmax_stitch_kernel(const float* __restrict__ z4, int tile, int
         row = mask + y * w;
         const int shift = (int)((uintptr_t)(row + lo) & 15);
         x0 = lo - shift + blockIdx.x * 256;                  // row + x0 is 16-byte aligned
-        const float* zrow = z4 + (((long)t * tile + ly) * tile - ox) * 4;
+        const long at0 = ((long)t * tile + ly) * tile - ox;  // + x: lo <= x < hi keeps x - ox inside [halo, tile - halo)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int q = j * 64 + lane, x = x0 + q;
             unsigned char c = 0;
-            if (x >= lo && x < hi) c = (unsigned char)argmax4(*reinterpret_cast<const f32x4*>(zrow + (long)x * 4), classes);
+            if (x >= lo && x < hi) c = px(at0 + x, y * w + x);
             cls[wave][q] = c;
         }
     }
@@ -218,17 +248,30 @@ extern "C" int runet_ellipse_spans(int k, int* j1, int* j2) {
     return RUNET_OK;
 }
 
-extern "C" int runet_scene_to_tiles(const unsigned char* scene, int h, int w, long row_stride, const int* origins, int n_tiles, int tile,
-                                    float mean0, float mean1, float mean2, float std0, float std1, float std2, float* tiles, void* stream) {
+template <bool PLANAR>
+static int scene_to_tiles_launch(const unsigned char* scene, int h, int w, long row_stride, const int* origins, int n_tiles, int tile,
+                                 const NormCoef& nc, float* tiles, void* stream) {
     RUNET_REQUIRE(scene && origins && tiles, "null pointer");
     RUNET_REQUIRE(h > 0 && w > 0 && row_stride >= 3L * w, "bad scene shape");
     RUNET_REQUIRE(n_tiles > 0 && n_tiles <= 65535 && tile > 0 && tile <= 8192, "bad tile count / size");
-    RUNET_REQUIRE(((uintptr_t)tiles & 15) == 0, "tiles must be 16-byte aligned");
-    RUNET_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "zero std");
-    const NormCoef nc = {{mean0, mean1, mean2}, {std0, std1, std2}};
-    hipLaunchKernelGGL(scene_to_tiles_kernel, dim3(cdiv((long)tile * tile, TPB), n_tiles), dim3(TPB), 0, (hipStream_t)stream, scene, h, w,
-                       row_stride, origins, tile, tiles, nc);
+    RUNET_REQUIRE(((uintptr_t)tiles & (PLANAR ? 3 : 15)) == 0, "tiles must be 16-byte aligned (planar: 4-byte)");
+    RUNET_REQUIRE(nc.std[0] != 0.f && nc.std[1] != 0.f && nc.std[2] != 0.f, "zero std");
+    hipLaunchKernelGGL(scene_to_tiles_kernel<PLANAR>, dim3(cdiv((long)tile * tile, TPB), n_tiles), dim3(TPB), 0, (hipStream_t)stream, scene, h,
+                       w, row_stride, origins, tile, tiles, nc);
     RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_scene_to_tiles(const unsigned char* scene, int h, int w, long row_stride, const int* origins, int n_tiles, int tile,
+                                    float mean0, float mean1, float mean2, float std0, float std1, float std2, float* tiles, void* stream) {
+    return scene_to_tiles_launch<false>(scene, h, w, row_stride, origins, n_tiles, tile, {{mean0, mean1, mean2}, {std0, std1, std2}}, tiles,
+                                        stream);
+}
+
+extern "C" int runet_scene_to_tiles_nchw(const unsigned char* scene, int h, int w, long row_stride, const int* origins, int n_tiles, int tile,
+                                         float mean0, float mean1, float mean2, float std0, float std1, float std2, float* tiles,
+                                         void* stream) {
+    return scene_to_tiles_launch<true>(scene, h, w, row_stride, origins, n_tiles, tile, {{mean0, mean1, mean2}, {std0, std1, std2}}, tiles,
+                                       stream);
 }
 
 extern "C" int runet_argmax_stitch(const float* z4, int n_tiles, int tile, int n_classes, const int* origins, int halo, unsigned char* mask,
@@ -240,8 +283,22 @@ extern "C" int runet_argmax_stitch(const float* z4, int n_tiles, int tile, int n
     RUNET_REQUIRE(((uintptr_t)z4 & 15) == 0, "z4 must be 16-byte aligned");
     const int core = tile - 2 * halo;
     RUNET_REQUIRE(cdiv(core, 4) <= 65535, "core too tall");
-    hipLaunchKernelGGL(argmax_stitch_kernel, dim3(cdiv(core + 15, 256), cdiv(core, 4), n_tiles), dim3(TPB), 0, (hipStream_t)stream, z4, tile,
-                       n_classes, origins, halo, mask, h, w);
+    hipLaunchKernelGGL(stitch_kernel<ArgmaxPx>, dim3(cdiv(core + 15, 256), cdiv(core, 4), n_tiles), dim3(TPB), 0, (hipStream_t)stream,
+                       ArgmaxPx{z4, n_classes}, tile, origins, halo, mask, h, w);
+    RUNET_CHECK_LAUNCH();
+}
+
+extern "C" int runet_threshold_stitch(const float* prob, int n_tiles, int tile, const int* origins, int halo, float threshold,
+                                      unsigned char* mask, float* soft, int h, int w, void* stream) {
+    RUNET_REQUIRE(prob && origins && mask, "null pointer");
+    RUNET_REQUIRE(tile > 0 && tile <= 8192, "tile must be positive (at most 8192)");
+    RUNET_REQUIRE(halo >= 0 && halo < tile - halo, "2 * halo must be smaller than the tile");
+    RUNET_REQUIRE(h > 0 && w > 0 && (long)h * w <= 2147483647L, "bad scene shape: h * w must fit int32");
+    RUNET_REQUIRE(n_tiles > 0 && n_tiles <= 65535, "bad tile count");
+    RUNET_REQUIRE(((uintptr_t)prob & 3) == 0 && ((uintptr_t)soft & 3) == 0, "prob and soft must be 4-byte aligned");
+    const int core = tile - 2 * halo;
+    hipLaunchKernelGGL(stitch_kernel<ThresholdPx>, dim3(cdiv(core + 15, 256), cdiv(core, 4), n_tiles), dim3(TPB), 0, (hipStream_t)stream,
+                       ThresholdPx{prob, soft, threshold}, tile, origins, halo, mask, h, w);
     RUNET_CHECK_LAUNCH();
 }
 

@@ -456,10 +456,14 @@ class RobustUNet(nn.Module):
         for k, rb in self._rbs().items():
             rb.dropout.mask = None if masks is None else masks[k]
 
-    def forward(self, x, return_logits=False):
-        _require_cuda(x)
+    def _check_input(self, x):
+        """raises on an input the kernels do not take (the call baseline.FusedNet's subclasses answer too); reads the shape only"""
         if x.shape[2] % 16 or x.shape[3] % 16:
             raise ValueError("H and W must be multiples of 16 (four 2x2 poolings)")
+
+    def forward(self, x, return_logits=False):
+        _require_cuda(x)
+        self._check_input(x)
         named = self.named_params()
         names = [k for k, _ in named]
         params = [p for _, p in named]

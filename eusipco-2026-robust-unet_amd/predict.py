@@ -1,4 +1,5 @@
-"""Prediction with the plain 2-class U-Net: the reference's `CoastlineExtractor` (predict_coastline.py:336-652) on the gfx950 kernels.
+"""Prediction: the reference's `CoastlineExtractor` (predict_coastline.py:336-652) on the gfx950 kernels, for the plain 2-class U-Net it was
+written for and for every 1-channel probability model of the project (RobustUNet, DeepLabV3Plus and the ten baselines).
 
 Reference pipeline, one image at a time (line numbers of predict_coastline.py):
   1. :358-363, :387  PIL bilinear Resize((512, 512)) -> ToTensor -> Normalize(ImageNet)      host resize, then runet_scene_to_tiles
@@ -8,6 +9,11 @@ Reference pipeline, one image at a time (line numbers of predict_coastline.py):
   5. :605-616        cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), > 10 points,       runet_contours_count / runet_contours_trace (device
                      approxPolyDP(0.002 * arcLength)                                          masks; host: trace_external_contours), host approx_poly_dp
   6. :404-413, :620-652  result dict, two PNG masks (* 255), <base>_coastlines.json           save_extraction_result
+
+A probability model (PROB_MODELS) differs in steps 1-2 only, the two kernels on either side of the network: its tiles are planar NCHW
+(runet_scene_to_tiles_nchw, the input its forward takes) and its mask is the reference's `pred > threshold`, threshold 0.5 (Main_Final.py:521,
+comne.py:622, Extended_Baseline_Comparison.py:758, :920), taken by runet_threshold_stitch; NaN is land.  The same launch can fill a soft
+water map (predict_scene(return_prob=True)).  Which sizes a model takes is asked of the model (`_check_input`), not tabulated here.
 
 Between the upload of the uint8 image and the single download of (water mask, coastline mask, counts, packed contours) nothing returns to
 the host but the two size words the contour tracing needs to allocate (its state count, then its contour and vertex counts).
@@ -61,12 +67,13 @@ def ellipse_element(k):
     return ((cols >= j1[:, None]) & (cols < j2[:, None])).astype(np.uint8)
 
 
-def tile_plan(h, w, tile=512, halo=64):
+def tile_plan(h, w, tile=512, halo=64, multiple=16):
     """-> int32 [n, 2] tile origins (y0, x0).  Cores of side tile - 2 * halo partition the scene from (0, 0): tile t owns the pixels
     [y0 + halo, y0 + tile - halo) x [x0 + halo, x0 + tile - halo) clipped to the scene and reads halo pixels of context around them, so
-    origins start at -halo and the last row / column of tiles may overhang."""
-    if tile <= 0 or tile % 16:
-        raise ValueError("tile must be a positive multiple of 16 (four 2x2 poolings)")
+    origins start at -halo and the last row / column of tiles may overhang.  multiple: what the tile must be a multiple of (16: the U-Nets;
+    the extractor has asked its model by then and passes 1)."""
+    if tile <= 0 or tile % multiple:
+        raise ValueError(f"tile must be a positive multiple of {multiple}" + (" (four 2x2 poolings)" if multiple == 16 else ""))
     if halo < 0 or 2 * halo >= tile:
         raise ValueError("2 * halo must be smaller than the tile")
     if h <= 0 or w <= 0:
@@ -89,14 +96,18 @@ def _dev_u8(a, device):
     return torch.from_numpy(a).to(device)
 
 
-def scene_to_tiles(scene, origins, tile):
-    """scene: device uint8 [H, W, 3]; origins: device int32 [n, 2] -> float32 [n, tile, tile, 4] (ToTensor + Normalize, outside = 0)."""
+def scene_to_tiles(scene, origins, tile, layout="nhwc4"):
+    """scene: device uint8 [H, W, 3]; origins: device int32 [n, 2] -> float32 [n, tile, tile, 4] (ToTensor + Normalize, outside = 0), the
+    plain U-Net's stem input; layout="nchw": the same values as planar [n, 3, tile, tile], the input of every other model's forward."""
+    if layout not in ("nhwc4", "nchw"):
+        raise ValueError("layout must be 'nhwc4' or 'nchw'")
     h, w, _ = scene.shape
     n = origins.shape[0]
-    out = torch.empty((n, tile, tile, 4), device=scene.device, dtype=torch.float32)
+    out = torch.empty((n, tile, tile, 4) if layout == "nhwc4" else (n, 3, tile, tile), device=scene.device, dtype=torch.float32)
     m, s = data.IMAGENET_MEAN, data.IMAGENET_STD
-    check(lib.runet_scene_to_tiles(scene.data_ptr(), h, w, scene.stride(0), origins.data_ptr(), n, tile, m[0], m[1], m[2], s[0], s[1], s[2],
-                                   out.data_ptr(), ops.stream()))
+    fn = lib.runet_scene_to_tiles if layout == "nhwc4" else lib.runet_scene_to_tiles_nchw
+    check(fn(scene.data_ptr(), h, w, scene.stride(0), origins.data_ptr(), n, tile, m[0], m[1], m[2], s[0], s[1], s[2], out.data_ptr(),
+             ops.stream()))
     return out
 
 
@@ -105,6 +116,27 @@ def argmax_stitch(z4, origins, halo, mask, n_classes=2):
     n, tile = z4.shape[0], z4.shape[1]
     check(lib.runet_argmax_stitch(z4.data_ptr(), n, tile, n_classes, origins.data_ptr(), halo, mask.data_ptr(), mask.shape[0], mask.shape[1],
                                   ops.stream()))
+    return mask
+
+
+def threshold_stitch(prob, origins, halo, mask, threshold=0.5, soft=None):
+    """prob: a model's output [n, 1, T, T] (or [n, T, T]), contiguous float32; writes `prob > threshold` (torch's rule on an fp32 tensor: NaN
+    is 0, the threshold itself is 0) of every tile's core into mask (device uint8 [H, W]) and, if given, the cores' probabilities bit for bit
+    into soft (device float32 [H, W])."""
+    if prob.dim() == 4 and prob.shape[1] == 1:
+        prob = prob[:, 0]
+    if prob.dim() != 3 or prob.shape[1] != prob.shape[2] or prob.dtype != torch.float32 or not prob.is_contiguous():
+        raise ValueError("prob must be a contiguous float32 [n, 1, T, T] tensor")
+    if origins.dtype != torch.int32 or tuple(origins.shape) != (prob.shape[0], 2) or not origins.is_contiguous():
+        raise ValueError("origins must be a contiguous int32 [n, 2] tensor, one row per tile")
+    if mask.dtype != torch.uint8 or mask.dim() != 2 or not mask.is_contiguous():
+        raise ValueError("mask must be a contiguous uint8 [H, W] tensor")
+    if soft is not None and (soft.dtype != torch.float32 or soft.shape != mask.shape or not soft.is_contiguous()):
+        raise ValueError("soft must be a contiguous float32 tensor of the mask's shape")
+    if any(t.device != prob.device for t in (origins, mask) + (() if soft is None else (soft,))):
+        raise ValueError("prob, origins, mask and soft must live on one device")
+    check(lib.runet_threshold_stitch(prob.data_ptr(), prob.shape[0], prob.shape[1], origins.data_ptr(), int(halo), float(threshold),
+                                     mask.data_ptr(), None if soft is None else soft.data_ptr(), mask.shape[0], mask.shape[1], ops.stream()))
     return mask
 
 
@@ -376,22 +408,44 @@ def _raise_nonfinite(count):
         raise ValueError(f"the selected bands hold {count} non-finite values: mask them (nodata) before the stretch")
 
 
-class CoastlineExtractor:
-    """Drop-in for the reference's class (predict_coastline.py:336): same constructor and method names, results as described above."""
+PROB_MODELS = {"RobustUNet": "model", "DeepLabV3Plus": "deeplab", "SegNet": "segnet", "YOLOSeg": "yolo", "SegFormerLite": "segformer",
+               "HRNetWater": "hrnet", "WaterNet": "waternet", "MSWNet": "mswnet", "FastSCNN": "fastscnn", "ENet": "enet", "PSPNet": "pspnet"}
 
-    def __init__(self, model_path=None, device="cuda", model=None, input_size=512):
+
+def _is_prob_model(model):
+    """one of the project's models whose forward(x [N, 3, H, W]) returns sigmoid probabilities [N, 1, H, W] (class name -> its module)"""
+    import importlib
+    return any(isinstance(model, getattr(importlib.import_module(f"{__package__}.{mod}"), name)) for name, mod in PROB_MODELS.items())
+
+
+class CoastlineExtractor:
+    """Drop-in for the reference's class (predict_coastline.py:336): same constructor and method names, results as described above.
+    model: a UNet (2-class logits, arg-max) or one of PROB_MODELS (1-channel probabilities, `> threshold`) with its weights loaded."""
+
+    def __init__(self, model_path=None, device="cuda", model=None, input_size=512, threshold=0.5):
         from .unet import UNet
-        if input_size <= 0 or input_size % 16:
-            raise ValueError("input_size must be a positive multiple of 16 (the reference uses 512)")
         self.device = torch.device(device)
         self.input_size = int(input_size)
+        self.threshold = float(threshold)
         if model is None:
             model = UNet(n_channels=3, n_classes=2)
             if model_path and os.path.exists(model_path):
                 model.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True))
-        elif not isinstance(model, UNet):
-            raise TypeError("model must be a UNet (2-class logits); the other models output probabilities")
-        self.model = model.to(self.device).eval()
+        self.prob = not isinstance(model, UNet)
+        if self.prob and not _is_prob_model(model):
+            raise TypeError("model must be a UNet (2-class logits) or one of the project's probability models: " + ", ".join(PROB_MODELS))
+        self.model = model.eval()
+        self._check_size(self.input_size, "input_size")          # before the parameters move: a refused size allocates nothing
+        self.model = model.to(self.device)
+
+    def _check_size(self, size, what):
+        """ValueError unless the model takes size x size inputs: the model's own rule (_check_input), asked on a shape-only tensor"""
+        if size <= 0:
+            raise ValueError(f"{what} must be positive (got {size})")
+        try:
+            self.model._check_input(torch.empty((1, 3, size, size), device="meta"))
+        except ValueError as e:
+            raise ValueError(f"{what} = {size} is not a size {type(self.model).__name__} takes: {e}") from None
 
     # -- network ---------------------------------------------------------------------------------
     def _z4(self, tiles):
@@ -399,52 +453,81 @@ class CoastlineExtractor:
         with torch.no_grad(), ops.precision(self.model.precision):
             return unet_forward(self.model, tiles, save=False, nhwc=True)[0]
 
+    def _prob(self, tiles):
+        with torch.no_grad():
+            p = self.model(tiles)                                # the models apply their own ops.precision
+        n, t = tiles.shape[0], tiles.shape[-1]
+        if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or tuple(p.shape) != (n, 1, t, t) or not p.is_contiguous():
+            raise ValueError(f"{type(self.model).__name__} must return a contiguous float32 [{n}, 1, {t}, {t}] tensor")
+        return p
+
+    def _stitch_tiles(self, scene, origins, tile, halo, mask, soft=None):
+        """tiles -> network -> cores into mask: the one place where the two model families part (tile layout and stitch rule)"""
+        if self.prob:
+            threshold_stitch(self._prob(scene_to_tiles(scene, origins, tile, "nchw")), origins, halo, mask, self.threshold, soft)
+        else:
+            argmax_stitch(self._z4(scene_to_tiles(scene, origins, tile)), origins, halo, mask, self.model.n_classes)
+
     def _predict_resized(self, pil, out=None):
         """steps 1-3: -> device uint8 [H, W] water mask at the image's own size"""
         s = self.input_size
         scene = torch.from_numpy(np.array(data.Resize((s, s))(pil), dtype=np.uint8)).to(self.device)
         origin = torch.zeros((1, 2), device=self.device, dtype=torch.int32)
-        z4 = self._z4(scene_to_tiles(scene, origin, s))
         w, h = pil.size
         same = (h, w) == (s, s)
         pred = out if same and out is not None else torch.empty((s, s), device=self.device, dtype=torch.uint8)
-        argmax_stitch(z4, origin, 0, pred, self.model.n_classes)
+        self._stitch_tiles(scene, origin, s, 0, pred)
         return pred if same else resize_nearest(pred, (h, w), out=out)
 
-    def _predict_tiled(self, scene, tile, halo, batch, out=None):
+    def _predict_tiled(self, scene, tile, halo, batch, out=None, soft=None):
         h, w, _ = scene.shape
-        plan = tile_plan(h, w, tile, halo)
+        plan = tile_plan(h, w, tile, halo, multiple=1)           # the model has been asked about the tile (_check_size)
         if batch < 1:
             raise ValueError("batch must be at least 1")
         origins = torch.from_numpy(plan).to(self.device)
         mask = out if out is not None else torch.empty((h, w), device=self.device, dtype=torch.uint8)
         for i in range(0, len(plan), batch):
             o = origins[i:i + batch]
-            argmax_stitch(self._z4(scene_to_tiles(scene, o, tile)), o, halo, mask, self.model.n_classes)
+            self._stitch_tiles(scene, o, tile, halo, mask, soft)
         return mask
 
-    def predict_scene(self, image=None, tile=512, halo=64, batch=8, as_tensor=False, bands=None, mode="water"):
+    def predict_scene(self, image=None, tile=512, halo=64, batch=8, as_tensor=False, bands=None, mode="water", return_prob=False):
         """Water mask at the scene's own resolution, no resize: tiles of side `tile` whose cores (tile - 2 * halo) partition the scene, `batch`
         tiles per network call.  Each pixel comes from exactly one core.  Beyond the scene the tiles read 0.0 (normalised units).
-        A band raster (_as_bands) is enhanced on the device first (scene.py, `mode`) and goes straight into the tiles."""
+        A band raster (_as_bands) is enhanced on the device first (scene.py, `mode`) and goes straight into the tiles.
+        return_prob (probability models only): -> (mask, prob_map), the float32 [h, w] probabilities of the same cores from the same stitch
+        launch (Extended_Baseline_Comparison.py:954 draws its error maps from it); a device tensor with as_tensor, numpy otherwise."""
+        self._check_size(tile, "tile")
+        if return_prob and not self.prob:
+            raise ValueError("return_prob needs a probability model: a UNet's outputs are logits")
+
+        def soft_map(h, w):
+            return torch.empty((h, w), device=self.device, dtype=torch.float32) if return_prob else None
+
         raster = _as_bands(image, bands)
         if raster is not None:
             r = _scene.load_raster(raster, self.device)
             scene, nonfinite = _scene._enhance(r, mode)
+            soft = soft_map(r.h, r.w)
             if as_tensor:
-                return self._predict_tiled(scene, tile, halo, batch)
+                mask = self._predict_tiled(scene, tile, halo, batch, soft=soft)
+                return (mask, soft) if return_prob else mask
             # water mask | non-finite count: one download
             seg = (r.h * r.w + 15) // 16 * 16
             buf = torch.empty(seg + 16, device=self.device, dtype=torch.uint8)
-            self._predict_tiled(scene, tile, halo, batch, out=buf[:r.h * r.w].view(r.h, r.w))
+            self._predict_tiled(scene, tile, halo, batch, out=buf[:r.h * r.w].view(r.h, r.w), soft=soft)
             buf[seg:seg + 4].view(torch.int32).copy_(nonfinite)
             host = buf.cpu().numpy()
             _raise_nonfinite(int(host[seg:seg + 4].view(np.int32)[0]))
-            return host[:r.h * r.w].reshape(r.h, r.w).copy()
+            mask = host[:r.h * r.w].reshape(r.h, r.w).copy()
+            return (mask, soft.cpu().numpy()) if return_prob else mask
         pil, _ = _load_rgb(image)
         scene = _dev_u8(np.array(pil, dtype=np.uint8), self.device)
-        mask = self._predict_tiled(scene, tile, halo, batch)
-        return mask if as_tensor else mask.cpu().numpy()
+        soft = soft_map(scene.shape[0], scene.shape[1])
+        mask = self._predict_tiled(scene, tile, halo, batch, soft=soft)
+        if not as_tensor:
+            mask, soft = mask.cpu().numpy(), None if soft is None else soft.cpu().numpy()
+        return (mask, soft) if return_prob else mask
 
     # -- reference surface -----------------------------------------------------------------------
     def extract_coastline_contours(self, water_mask, dilation_kernel_size=5):
@@ -467,6 +550,8 @@ class CoastlineExtractor:
         which is enhanced on the device (scene.py, `mode`): tiled, the enhanced scene feeds the tiles directly; resized, it is downloaded
         once for the PIL bilinear resize, the reference's order."""
         ellipse_spans(dilation_size)
+        if tiled:
+            self._check_size(tile, "tile")
         raster = _as_bands(image, bands)
         scene = nonfinite = None
         if raster is not None:

@@ -767,6 +767,15 @@ int runet_up_sigmoid_bwd(const float* dprob, const float* prob, float* dz, int n
  * runet_argmax_stitch: torch.argmax(output, dim=1) (:392) read from the head's NHWC output as it stands (z4 [n_tiles][T][T][4], n_classes
  *   <= 4 valid): the class index of each tile's core (tile minus halo on each side, clipped to the scene) goes into the scene mask.  First
  *   maximal index; NaN is greater than everything, the first NaN wins (torch's CPU order).
+ * runet_scene_to_tiles_nchw: the same arguments and the same arithmetic (one kernel body, the layout is its template parameter), written
+ *   planar as [n_tiles][3][T][T] fp32 - the NCHW input every probability model's forward takes; no fourth channel; tiles 4-byte aligned.
+ * runet_threshold_stitch: the binarisation of the 1-channel sigmoid models, `pred > threshold` with threshold 0.5 (Main_Final.py:521,
+ *   comne.py:622, Extended_Baseline_Comparison.py:758, :920).  prob is [n_tiles][T][T] fp32 (one channel: NCHW and NHWC coincide); for each
+ *   tile's core mask[y][x] = prob > threshold ? 1 : 0, compared in fp32 as torch compares an fp32 tensor with a scalar rounded to fp32.  An
+ *   ordered compare: NaN gives 0 and +Inf gives 1, a probability equal to the threshold gives 0 - UNLIKE runet_argmax_stitch, where NaN wins.
+ *   soft: NULL, or a dense [h][w] fp32 scene map that receives the same cores' probabilities bit for bit, NaN included (the map the
+ *   reference's error / MAE figures are drawn from, Extended_Baseline_Comparison.py:954).  Pixels no core covers are left alone in both.
+ *   Checked on the host before any launch: null pointers, tile <= 0, halo < 0 or 2 * halo >= tile, h * w beyond int32.
  * runet_resize_nearest_u8: cv2.resize(..., INTER_NEAREST) (:395-396) by OpenCV's index rule in IEEE double:
  *   sx = min((int)floor(x * (1.0 / ((double)dw / sw))), sw - 1), likewise for y.  dst 16-byte aligned.
  * runet_dilate_diff_u8: cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)), cv2.dilate and `dilated_mask - water_mask` (:595-602) in one pass
@@ -780,6 +789,10 @@ int runet_scene_to_tiles(const unsigned char* scene, int h, int w, long row_stri
                          float mean1, float mean2, float std0, float std1, float std2, float* tiles, void* stream);
 int runet_argmax_stitch(const float* z4, int n_tiles, int tile, int n_classes, const int* origins, int halo, unsigned char* mask, int h, int w,
                         void* stream);
+int runet_scene_to_tiles_nchw(const unsigned char* scene, int h, int w, long row_stride, const int* origins, int n_tiles, int tile, float mean0,
+                              float mean1, float mean2, float std0, float std1, float std2, float* tiles, void* stream);
+int runet_threshold_stitch(const float* prob, int n_tiles, int tile, const int* origins, int halo, float threshold, unsigned char* mask,
+                           float* soft, int h, int w, void* stream);
 int runet_resize_nearest_u8(const unsigned char* src, int sh, int sw, unsigned char* dst, int dh, int dw, void* stream);
 int runet_dilate_diff_u8(const unsigned char* mask, int h, int w, int k, unsigned char* coast, unsigned char* dilated, int* counts2,
                          void* stream);

@@ -7,13 +7,17 @@
     alternated in windows of back-to-back calls timed with device events (>= 1 s per variant after a warm-up), with the bytes each kernel
     must move (from the shapes) over its time;
   * the post-processing share of one 512^2 prediction;
+  * --model {unet,runet,<baseline>}: the whole-prediction lines above for that model (default unet, the reference's; every other one is a
+    probability model, binarised as `prob > 0.5`), and for those the two kernels of the probability route against their torch composition:
+    planar tiles against the NHWC-4 tiles + `[..., :3].permute(0, 3, 1, 2).contiguous()`, threshold_stitch against `(prob > thr)` plus the
+    copies into the scene maps, with and without the soft map (figures kept in profiles/predict_models.txt);
   * contour tracing (csrc/contours.hip) against the host tracer on the same coastline band, on this box, in interleaved rounds: the band
     of the 512^2 scene above, and the bands of a seeded smooth random field at 2048^2 and 10980^2; device time by device events and by the
     wall clock including its three downloads, the workspace bytes at each size.  Where the host tracer would exceed --host-budget seconds
     it is timed on the top-left 2048^2 crop instead, and the report says so.
 
 Not a bench line of the contract (bench.py measures the Robust U-Net training metric); the figures are kept in profiles/predict_postprocess.txt.
-  python tools/bench_predict.py [--what all|path|kernels|contours] [--window 0.5] [--host-budget 20] [--out FILE]
+  python tools/bench_predict.py [--what all|path|kernels|contours] [--model unet] [--window 0.5] [--host-budget 20] [--out FILE]
 """
 import argparse
 import importlib
@@ -74,6 +78,55 @@ def windows(fns, window_s):
     return [t / (2 * r) for t, r in zip(tot, reps)], [2 * r for r in reps]
 
 
+MODELS = {"unet": "UNet", "runet": "RobustUNet", **{k.lower(): k for k in P.PROB_MODELS if k != "RobustUNet"}}
+
+
+def timed_cases(size, cases, window_s):
+    rows = []
+    for name, hip, stock, nbytes in cases:
+        (t_hip, t_stock), (r_hip, r_stock) = windows((hip, stock), window_s)
+        rows.append({"size": size, "kernel": name, "hip_us": round(t_hip * 1e6, 2), "torch_us": round(t_stock * 1e6, 2),
+                     "torch_over_hip": round(t_stock / t_hip, 2), "bytes_min": nbytes, "hip_GBps": round(nbytes / t_hip * 1e-9, 1),
+                     "calls": [r_hip, r_stock]})
+        say(f"  {size:5d}^2  {name:34s} HIP {t_hip * 1e6:9.2f} us  {nbytes / t_hip * 1e-9:8.1f} GB/s   torch ops {t_stock * 1e6:9.2f} us"
+            f"   torch / HIP = {t_stock / t_hip:6.2f}   ({r_hip} / {r_stock} calls)")
+    return rows
+
+
+def prob_kernel_rows(size, window_s):
+    """the two kernels of the probability route on one size x size tile (halo 0), as kernel_rows does for the other four"""
+    h = w = size
+    scene, _ = scene_u8(h, w, size)
+    sd = torch.from_numpy(scene).to(DEV)
+    origin = torch.zeros((1, 2), device=DEV, dtype=torch.int32)
+    thr = 0.5
+    prob = torch.rand((1, 1, h, w), device=DEV)
+    prob[0, 0, ::7, ::5] = float("nan")
+    prob[0, 0, 1::7, ::5] = thr
+    mask, soft = torch.empty((h, w), device=DEV, dtype=torch.uint8), torch.empty((h, w), device=DEV)
+    t_mask, t_soft = torch.empty_like(mask), torch.empty_like(soft)
+
+    def t_planar():
+        return P.scene_to_tiles(sd, origin, size)[..., :3].permute(0, 3, 1, 2).contiguous()
+
+    def t_threshold():
+        return t_mask.copy_(prob[0, 0] > thr)
+
+    def t_threshold_soft():
+        t_soft.copy_(prob[0, 0])
+        return t_mask.copy_(prob[0, 0] > thr)
+
+    assert torch.equal(P.scene_to_tiles(sd, origin, size, "nchw").view(torch.int32), t_planar().view(torch.int32))
+    assert torch.equal(P.threshold_stitch(prob, origin, 0, mask, thr, soft=soft), t_threshold_soft())
+    assert torch.equal(soft.view(torch.int32), t_soft.view(torch.int32))
+    return timed_cases(size, [
+        ("scene_to_tiles nchw", lambda: P.scene_to_tiles(sd, origin, size, "nchw"), t_planar, 3 * h * w + 12 * h * w),
+        ("threshold_stitch", lambda: P.threshold_stitch(prob, origin, 0, mask, thr), t_threshold, 4 * h * w + h * w),
+        ("threshold_stitch + soft map", lambda: P.threshold_stitch(prob, origin, 0, mask, thr, soft=soft), t_threshold_soft,
+         4 * h * w + h * w + 4 * h * w),
+    ], window_s)
+
+
 def kernel_rows(size, window_s):
     h = w = size
     scene, water = scene_u8(h, w, size)
@@ -122,20 +175,12 @@ def kernel_rows(size, window_s):
     c_ref, n_ref = t_dilate()
     c_got, n_got, _ = P.dilate_diff(wd, k, coast=coast, counts=counts)
     assert torch.equal(c_got, c_ref) and n_got.tolist() == n_ref.tolist()
-    rows = []
-    for name, hip, stock, nbytes in cases:
-        (t_hip, t_stock), (r_hip, r_stock) = windows((hip, stock), window_s)
-        rows.append({"size": size, "kernel": name, "hip_us": round(t_hip * 1e6, 2), "torch_us": round(t_stock * 1e6, 2),
-                     "torch_over_hip": round(t_stock / t_hip, 2), "bytes_min": nbytes, "hip_GBps": round(nbytes / t_hip * 1e-9, 1),
-                     "calls": [r_hip, r_stock]})
-        say(f"  {size:5d}^2  {name:34s} HIP {t_hip * 1e6:9.2f} us  {nbytes / t_hip * 1e-9:8.1f} GB/s   torch ops {t_stock * 1e6:9.2f} us"
-            f"   torch / HIP = {t_stock / t_hip:6.2f}   ({r_hip} / {r_stock} calls)")
-    return rows
+    return timed_cases(size, cases, window_s)
 
 
-def path_rows(window_s):
+def path_rows(window_s, model="unet"):
     torch.manual_seed(0)
-    ex = pkg.CoastlineExtractor(model=pkg.UNet(3, 2), device="cuda:0", input_size=512)
+    ex = pkg.CoastlineExtractor(model=pkg.UNet(3, 2) if model == "unet" else getattr(pkg, MODELS[model])(), device="cuda:0", input_size=512)
     scene, _ = scene_u8(512, 512, 1)
     from PIL import Image
     pil = Image.fromarray(scene)
@@ -160,20 +205,25 @@ def path_rows(window_s):
     # the four post-processing kernels of that prediction, back to back on the device
     sd = torch.from_numpy(scene).to(DEV)
     origin = torch.zeros((1, 2), device=DEV, dtype=torch.int32)
-    tiles = P.scene_to_tiles(sd, origin, 512)
-    z4 = ex._z4(tiles)
+    tiles = P.scene_to_tiles(sd, origin, 512, "nchw" if ex.prob else "nhwc4")
+    net = ex._prob if ex.prob else ex._z4
+    z4 = net(tiles)
     water, coast = torch.empty((512, 512), device=DEV, dtype=torch.uint8), torch.empty((512, 512), device=DEV, dtype=torch.uint8)
     counts = torch.empty(2, device=DEV, dtype=torch.int32)
 
     def post():
-        P.scene_to_tiles(sd, origin, 512)
-        P.argmax_stitch(z4, origin, 0, water, 2)
+        if ex.prob:
+            P.scene_to_tiles(sd, origin, 512, "nchw")
+            P.threshold_stitch(z4, origin, 0, water, ex.threshold)
+        else:
+            P.scene_to_tiles(sd, origin, 512)
+            P.argmax_stitch(z4, origin, 0, water, 2)
         P.dilate_diff(water, 5, coast=coast, counts=counts)
 
-    (t_post, t_net), _ = windows((post, lambda: ex._z4(tiles)), window_s)
+    (t_post, t_net), _ = windows((post, lambda: net(tiles)), window_s)
     out["post_us_512"], out["network_us_512"] = round(t_post * 1e6, 2), round(t_net * 1e6, 2)
     out["post_share_of_prediction"] = round(t_post / dt, 5)
-    say(f"  of which on the device: network {t_net * 1e3:.3f} ms, normalise + arg-max + dilation difference {t_post * 1e6:.1f} us "
+    say(f"  of which on the device: network {t_net * 1e3:.3f} ms, normalise + {'threshold' if ex.prob else 'arg-max'} + dilation difference {t_post * 1e6:.1f} us "
         f"= {100 * t_post / dt:.2f} % of the prediction")
     res = ex.extract_coastline_from_image(scene)
     t0 = time.perf_counter()
@@ -266,6 +316,8 @@ def contour_rows(sizes, host_budget):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="all", choices=("all", "path", "kernels", "contours"))
+    ap.add_argument("--model", default="unet", choices=sorted(MODELS), help="the model of the whole-prediction lines; any but unet also "
+                    "times the two kernels of the probability route")
     ap.add_argument("--host-budget", type=float, default=20.0, help="seconds one host tracing run may take before it moves to a 2048^2 crop")
     ap.add_argument("--window", type=float, default=0.5, help="seconds per timed window (two windows per variant)")
     ap.add_argument("--out", help="also write the text report here")
@@ -276,10 +328,11 @@ def main():
     say(f"prediction path on {torch.cuda.get_device_name(0)}; device-event windows of >= {2 * a.window:.1f} s per variant, alternated")
     if a.what in ("all", "kernels"):
         say("kernels (HIP = csrc/coastline.hip; torch ops = the same step composed from stock device ops, results checked equal first):")
-        res["kernels"] = kernel_rows(512, a.window) + kernel_rows(4096, a.window)
+        res["kernels"] = (kernel_rows(512, a.window) + kernel_rows(4096, a.window) if a.model == "unet" else
+                          prob_kernel_rows(512, a.window) + prob_kernel_rows(4096, a.window))
     if a.what in ("all", "path"):
-        say("prediction (fp32, seeded untrained UNet(3, 2)):")
-        res["path"] = path_rows(a.window)
+        say(f"prediction (fp32, seeded untrained {MODELS[a.model]}):")
+        res["path"] = path_rows(a.window, a.model)
     if a.what in ("all", "contours"):
         say("contour tracing (csrc/contours.hip against predict.trace_external_contours on the same band, results checked equal):")
         res["contours"] = contour_rows((512, 2048, 10980), a.host_budget)
