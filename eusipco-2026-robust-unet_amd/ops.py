@@ -6,6 +6,7 @@ channel slice of a wider concat buffer).  All launches go to torch's current HIP
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -50,6 +51,11 @@ def stream():
     if o is not None:
         return o
     return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
+
+
+def _ptr(t):
+    """Device address of an optional tensor (None -> a null pointer)."""
+    return t.data_ptr() if t is not None else None
 
 
 # ---- operand precision of the matrix-core kernels.  "f32": the reference's arithmetic (fp32 MFMA, Winograd forms included).
@@ -257,21 +263,14 @@ def bf16_weights(w_hwio, transpose=False):
 
 def _igemm_bf16(mode, x, w_hwio, bias, out, n, h, wd, cin, cout, kh, kw, dil, accumulate, transpose):
     wp = bf16_weights(w_hwio, transpose)
-    prof = _PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_lp("runet_conv_igemm_{}")(x.data_ptr(), ld(x), wp.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out),
-                                    n, h, wd, cin, cout, kh, kw, dil, mode, int(accumulate), stream()))
-    if prof:
-        e1.record()
-        taps = 4 if kh == 2 else kh * kw
-        fl = 2.0 * n * h * wd * taps * cin * cout
-        opix = 4 * n * h * wd if mode == CONVT_FWD else n * h * wd          # pixels written (mode CONVT_DGRAD reads 4x the pixels instead)
-        ipix = 4 * n * h * wd if mode == CONVT_DGRAD else n * h * wd
-        nbytes = 4.0 * (ipix * cin + opix * cout) + 2.0 * taps * cin * cout
-        name = ("conv3x3_{}_kernel" if (kh == 3 and dil == 1 and mode in (CONV_FWD, CONV_DGRAD)) else "igemm_{}_kernel").format(_PRECISION)
-        _PROFILE.append((name, fl, fl, e0, e1, nbytes))
+    taps = 4 if kh == 2 else kh * kw
+    fl = 2.0 * n * h * wd * taps * cin * cout
+    opix = 4 * n * h * wd if mode == CONVT_FWD else n * h * wd          # pixels written (mode CONVT_DGRAD reads 4x the pixels instead)
+    ipix = 4 * n * h * wd if mode == CONVT_DGRAD else n * h * wd
+    name = "conv3x3_{}_kernel" if (kh == 3 and dil == 1 and mode in (CONV_FWD, CONV_DGRAD)) else "igemm_{}_kernel"
+    with _timed(lambda: name.format(_PRECISION), fl, fl, 4.0 * (ipix * cin + opix * cout) + 2.0 * taps * cin * cout):
+        check(_lp("runet_conv_igemm_{}")(x.data_ptr(), ld(x), wp.data_ptr(), _ptr(bias), out.data_ptr(), ld(out),
+                                        n, h, wd, cin, cout, kh, kw, dil, mode, int(accumulate), stream()))
     return out
 
 
@@ -341,18 +340,32 @@ def stop_conv_profile(prof):
             "bytes_per_s": nb / t if nb else None, "bytes_per_launch": nb / n if nb else None}
 
 
-def _igemm(mode, x, ldx, w, bias, y, ldy, n, h, wd, cin, cin_w, cout, kh, kw, dil, accumulate):
-    if _PROFILE is None:
-        check(lib.runet_conv_igemm(x, ldx, w, bias, y, ldy, n, h, wd, cin, cin_w, cout, kh, kw, dil, mode, accumulate, stream()))
-        return
+@contextlib.contextmanager
+def _span(name, flops, exec_flops, nbytes):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    check(lib.runet_conv_igemm(x, ldx, w, bias, y, ldy, n, h, wd, cin, cin_w, cout, kh, kw, dil, mode, accumulate, stream()))
+    yield
     e1.record()
-    taps = 4 if kh == 2 else kh * kw
-    name = lib.runet_conv_igemm_kernel_name(n, h, wd, min(cin, cin_w), cout, kh, mode).decode()
-    fl = 2.0 * n * h * wd * taps * min(cin, cin_w) * cout
-    _PROFILE.append((name, fl, fl, e0, e1))
+    _PROFILE.append((name() if callable(name) else name, flops, exec_flops, e0, e1) + (() if nbytes is None else (nbytes,)))
+
+
+_UNTIMED = contextlib.nullcontext()
+
+
+def _timed(name, flops, exec_flops, nbytes=None):
+    """with _timed(...): ...the launches of one line of the live profile...   Without a profile this does nothing; with one, HIP events are
+    recorded before and behind the body and (name, algorithmic FLOPs, executed FLOPs, events[, algorithmic HBM bytes]) is appended to it.
+    name: a string, or a callable (called only when profiling, so it may ask the library for the kernel's name)."""
+    return _UNTIMED if _PROFILE is None else _span(name, flops, exec_flops, nbytes)
+
+
+def _igemm(mode, x, w, bias, out, n, h, wd, cin, cin_w, cout, kh, kw, dil, accumulate):
+    """w: the weight tensor in the layout `mode` reads (transposed_weights for the *_DGRAD_T modes)."""
+    fl = 2.0 * n * h * wd * (4 if kh == 2 else kh * kw) * min(cin, cin_w) * cout
+    with _timed(lambda: lib.runet_conv_igemm_kernel_name(n, h, wd, min(cin, cin_w), cout, kh, mode).decode(), fl, fl):
+        check(lib.runet_conv_igemm(x.data_ptr(), ld(x), w.data_ptr(), _ptr(bias), out.data_ptr(), ld(out), n, h, wd, cin, cin_w, cout, kh, kw, dil,
+                                   mode, int(accumulate), stream()))
+    return out
 
 
 USE_WINOGRAD = os.environ.get("RUNET_NO_WINOGRAD", "0") != "1"
@@ -403,8 +416,7 @@ def stem_conv(x, w3, w1=None, stats3=None, stats1=None):
     _, _, cin_w, cout = w3.shape
     y3 = empty_nhwc(n, h, w, cout, x)
     y1 = empty_nhwc(n, h, w, cout, x) if w1 is not None else None
-    args = (x.data_ptr(), ld(x), w3.data_ptr(), w1.data_ptr() if w1 is not None else None, y3.data_ptr(), ld(y3),
-            y1.data_ptr() if y1 is not None else None, ld(y1) if y1 is not None else 0, n, h, w, cin_w, cout)
+    args = (x.data_ptr(), ld(x), w3.data_ptr(), _ptr(w1), y3.data_ptr(), ld(y3), _ptr(y1), ld(y1) if y1 is not None else 0, n, h, w, cin_w, cout)
     if EPILOGUE_STATS and stats3 is not None and (w1 is None or stats1 is not None):
         parts = lib.runet_stem_conv_stats_parts(n, h, w)
         s3 = _stats_buf(stats3, parts, cout, x.device)
@@ -467,21 +479,14 @@ def _stats_buf(stats, nparts, c, dev):
 def _conv_x3(mode, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate, stats=None):
     """h, w: the image the 1x1 convolution runs over; the low-resolution side for the transposed modes."""
     wp = conv_x3_weights(w_hwio, mode)
-    prof = _PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if stats is not None and EPILOGUE_STATS and mode == CONV_FWD:
-        sp = _stats_buf(stats, lib.runet_conv_x3_stats_parts(n, h, w), cout, x.device)
-        check(lib.runet_conv_x3_stats(x.data_ptr(), ld(x), wp.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out), n, h, w,
-                                      cin, cout, mode, int(accumulate), sp, stream()))
-    else:
-        check(lib.runet_conv_x3(x.data_ptr(), ld(x), wp.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out), n, h, w,
-                                cin, cout, mode, int(accumulate), stream()))
-    if prof:
-        e1.record()
-        fl = 2.0 * n * h * w * (4 if mode in (CONVT_FWD, CONVT_DGRAD) else 1) * cin * cout
-        _PROFILE.append((lib.runet_conv_x3_kernel_name(n, h, w, cout, mode).decode(), fl, fl, e0, e1))
+    fl = 2.0 * n * h * w * (4 if mode in (CONVT_FWD, CONVT_DGRAD) else 1) * cin * cout
+    with _timed(lambda: lib.runet_conv_x3_kernel_name(n, h, w, cout, mode).decode(), fl, fl):
+        args = (x.data_ptr(), ld(x), wp.data_ptr(), _ptr(bias), out.data_ptr(), ld(out), n, h, w, cin, cout, mode, int(accumulate))
+        if stats is not None and EPILOGUE_STATS and mode == CONV_FWD:
+            sp = _stats_buf(stats, lib.runet_conv_x3_stats_parts(n, h, w), cout, x.device)
+            check(lib.runet_conv_x3_stats(*args, sp, stream()))
+        else:
+            check(lib.runet_conv_x3(*args, stream()))
     return out
 
 
@@ -501,45 +506,10 @@ def _conv1x1_stream_case(mode, x, cin, cin_w, cout, kh=1, kw=1, out=None):
 
 def _conv1x1_stream(mode, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate):
     """w_hwio: the module's forward weight in both modes (the data gradient reads it transposed)."""
-    args = (x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out), n, h, w, cin, cout,
-            mode, int(accumulate), stream())
-    if _PROFILE is None:
-        check(lib.runet_conv1x1_stream(*args))
-        return out
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(lib.runet_conv1x1_stream(*args))
-    e1.record()
     fl = 2.0 * n * h * w * cin * cout
-    _PROFILE.append((lib.runet_conv1x1_stream_kernel_name(cin, cout, int(accumulate)).decode(), fl, fl, e0, e1))
-    return out
-
-
-def conv_fwd(x, w_hwio, bias=None, out=None, dil=1, accumulate=False, keep_v=None, stats=None, pre=None):
-    """stats: dict; when the kernel that serves this convolution can take the BatchNorm statistics of its output in its epilogue it fills
-    stats["part"] / stats["nparts"] (blocks.bn_coeff(fused=stats) then skips its pass over the tensor), otherwise leaves it empty.
-    pre = (scale, shift, factor_nc or None), only where fuses_act_input(x, w_hwio): the convolution of max(x * scale + shift, 0) * factor."""
-    n, h, w, cin = x.shape
-    kh, kw, cin_w, cout = w_hwio.shape
-    if pre is not None:
-        assert fuses_act_input(x, w_hwio) and dil == 1
-        return wino4_conv(x, wino4_weights(w_hwio), bias, out=out, accumulate=accumulate, keep_v=keep_v, dil=dil, pre=pre, stats=stats)
-    if _bf16_case(cin, cin_w):
-        if out is None:
-            out = empty_nhwc(n, h, w, cout, x)
-        return _igemm_bf16(CONV_FWD, x, w_hwio, bias, out, n, h, w, cin, cout, kh, kw, dil, accumulate, False)
-    if _wino4_case(h, w, kh, dil, cin, cout, cin_w):
-        return wino4_conv(x, wino4_weights(w_hwio), bias, out=out, accumulate=accumulate, keep_v=keep_v, dil=dil, stats=stats)
-    if _wino_case(h, w, kh, dil, cin, cout, cin_w, n, ld(x), ld(out) if out is not None else cout):
-        return wino_conv(x, wino_weights(w_hwio), bias, out=out, accumulate=accumulate, stats=stats)
-    if out is None:
-        out = empty_nhwc(n, h, w, cout, x)
-    if kh == 1 and _conv_x3_case(x, cin, cin_w, cout):
-        return _conv_x3(CONV_FWD, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate, stats=stats)
-    if dil == 1 and _conv1x1_stream_case(CONV_FWD, x, cin, cin_w, cout, kh, kw, out):
-        return _conv1x1_stream(CONV_FWD, x, w_hwio, bias, out, n, h, w, cin, cout, accumulate)
-    _igemm(CONV_FWD, x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None,
-           out.data_ptr(), ld(out), n, h, w, cin, cin_w, cout, kh, kw, dil, int(accumulate))
+    with _timed(lambda: lib.runet_conv1x1_stream_kernel_name(cin, cout, int(accumulate)).decode(), fl, fl):
+        check(lib.runet_conv1x1_stream(x.data_ptr(), ld(x), w_hwio.data_ptr(), _ptr(bias), out.data_ptr(), ld(out), n, h, w, cin, cout,
+                                       mode, int(accumulate), stream()))
     return out
 
 
@@ -575,21 +545,14 @@ def wino_conv(x, U, bias=None, out=None, accumulate=False, stats=None):
     nn_ = U.kn[1] if x3 else U.shape[2]
     if out is None:
         out = empty_nhwc(n, h, w, nn_, x)
-    if _PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if x3 and stats is not None and EPILOGUE_STATS:
-        sp = _stats_buf(stats, lib.runet_wino_conv_x3_stats_parts(n, h, w), nn_, x.device)
-        check(lib.runet_wino_conv_x3_stats(x.data_ptr(), ld(x), U.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out),
-                                           n, h, w, k, nn_, int(accumulate), sp, stream()))
-    else:
-        fn = lib.runet_wino_conv_x3 if x3 else lib.runet_wino_conv
-        check(fn(x.data_ptr(), ld(x), U.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out),
-                 n, h, w, k, nn_, int(accumulate), stream()))
-    if _PROFILE is not None:
-        e1.record()
-        fl = 2.0 * n * h * w * 9 * k * nn_
-        _PROFILE.append(("wino_conv_x3_kernel" if x3 else "wino_conv_kernel", fl, fl * 16.0 / 36.0, e0, e1))
+    fl = 2.0 * n * h * w * 9 * k * nn_
+    with _timed("wino_conv_x3_kernel" if x3 else "wino_conv_kernel", fl, fl * 16.0 / 36.0):
+        args = (x.data_ptr(), ld(x), U.data_ptr(), _ptr(bias), out.data_ptr(), ld(out), n, h, w, k, nn_, int(accumulate))
+        if x3 and stats is not None and EPILOGUE_STATS:
+            sp = _stats_buf(stats, lib.runet_wino_conv_x3_stats_parts(n, h, w), nn_, x.device)
+            check(lib.runet_wino_conv_x3_stats(*args, sp, stream()))
+        else:
+            check((lib.runet_wino_conv_x3 if x3 else lib.runet_wino_conv)(*args, stream()))
     return out
 
 
@@ -602,54 +565,155 @@ def wino_ok(h, w, cin, cout):
 FUSE_BN_INPUT = os.environ.get("RUNET_NO_FUSED_BN_INPUT", "0") != "1"
 
 
-def fuses_act_input(t, w_hwio):
-    """conv_fwd(t, w, pre=(scale, shift, factor)) is available: the 3x3 convolution takes the unfused F(4x4) path in fp32."""
-    n, h, w, cin = t.shape
-    kh, kw, cin_w, cout = w_hwio.shape
-    return FUSE_BN_INPUT and not _bf16_case(cin, cin_w) and _wino4_case(h, w, kh, 1, cin, cout, cin_w)
+# ---- dispatch: which kernel serves a convolution.  One route function per family (conv_route: 1x1 / 3x3 forward and data gradient, convt_route:
+# k2-s2 transposed, wgrad_route: weight gradients) evaluates the *_case predicates in the order of this table, first match wins; the wrappers
+# compute the route and launch it, and fuses_act_input / fuses_bn_bwd_input ask the same function.  k / n: channels read / written (a data
+# gradient reads the weight's output channels); "full": the weight has a row per channel read (all but the RGB stem); wg: the weight gradient.
+# Each knob is described, with its measurements, where it is defined.
+#   route      csrc/                           condition                                                                   off with
+#   lowp       conv_bf16.hip                   inside ops.precision("bf16" / "fp16"): full, k >= 8 (_bf16_case)            -
+#   wino4      conv_winograd4.hip + a GEMM of  3x3, full, k and n >= 128, <= 128^2 pixels, h and w % (4 dil) == 0          RUNET_NO_WINOGRAD4, RUNET_NO_WINOGRAD; dilated ones
+#                gemm_split / conv_igemm.hip     (_wino4_case); wg: and n >= 16                                              alone: RUNET_NO_WINOGRAD4_DILATED
+#   wino4_adj  the same, adjoint output        a data gradient on route wino4 with k % 16 == 0 (_x3_case)                  RUNET_NO_W4_ADJOINT, RUNET_NO_X3
+#   stem       conv_stem.hip                   wg of the RGB stem: 4-channel tensor, 1..3 weight rows (_stem_case)         RUNET_NO_STEM_KERNELS
+#   wino2      conv_winograd_x3.hip, or        3x3, dilation 1, full, even h and w, k >= 16; forward / data gradient:      RUNET_NO_WINOGRAD; the split-operand form alone:
+#                conv_winograd.hip               also k % 16 == 0 and 32-bit offsets (_wino_case)                            RUNET_NO_WINO_X3, RUNET_NO_X3
+#   x3         conv_x3.hip                     1x1 / transposed, full, k % 16 == 0, taps x k >= 128 (_conv_x3_case);       RUNET_NO_CONV_X3, RUNET_NO_X3; the narrow
+#                                                transposed forward: also n < 128 from n = 32 on                             transposed forward alone: RUNET_NO_CONVT_X3_NARROW
+#   stream1x1  conv1x1_stream.hip              1x1, full, k and n <= 128, aligned (_conv1x1_stream_case, wg:               RUNET_NO_CONV1X1_STREAM; wg: off unless
+#                                                _conv1x1_wgrad_stream_case)                                                 RUNET_CONV1X1_WGRAD_STREAM=1
+#   igemm      conv_igemm.hip                  everything else                                                             -
+_DGRAD_T = {CONV_DGRAD: CONV_DGRAD_T, CONVT_DGRAD: CONVT_DGRAD_T}
 
 
-def fuses_bn_bwd_input(dy, w_hwio):
-    """conv_dgrad(dy, w, keep_z=..., bn=...) is available: the data gradient takes the adjoint F(4x4) path (Z shared with the weight gradient)."""
-    n, h, w, cout = dy.shape
-    kh, kw, cin, cout_w = w_hwio.shape
-    return (FUSE_BN_INPUT and cout_w == cout and not _bf16_case(cout, cout) and _wino4_case(h, w, kh, 1, cout, cin, cout) and USE_W4_ADJOINT
-            and _x3_case(cout) and cin >= 16)
+def _geometry(mode, x, w_hwio):
+    """-> (images, h, w, k, k_w, n, kh, kw) of a convolution in `mode` (x = dy for the data gradients, w_hwio the forward weight in every mode):
+    h x w the image the taps run over (the low-resolution side of a transposed convolution), k / n the channels read / written, k_w the
+    rows the weight has for the channels read."""
+    n_img, h, w, k = x.shape
+    kh, kw, k_w, n = w_hwio.shape
+    if mode in _DGRAD_T:
+        k_w, n = k, k_w
+        if mode == CONVT_DGRAD:
+            h, w = h // 2, w // 2
+    return n_img, h, w, k, k_w, n, kh, kw
+
+
+def conv_route(mode, x, w_hwio, out=None, dil=1, g=None):
+    """Route of conv_fwd (mode CONV_FWD) / conv_dgrad (CONV_DGRAD, x = dy).  out = None: a fresh dense tensor.  g: _geometry(mode, x,
+    w_hwio) where the caller has it."""
+    n_img, h, w, k, k_w, n, kh, kw = g or _geometry(mode, x, w_hwio)
+    if _bf16_case(k, k_w):
+        return "lowp"
+    if _wino4_case(h, w, kh, dil, k, n, k_w):
+        return "wino4_adj" if mode == CONV_DGRAD and USE_W4_ADJOINT and _x3_case(k) else "wino4"
+    if kh == 3 and _wino_case(h, w, kh, dil, k, n, k_w, n_img, ld(x), ld(out) if out is not None else n):
+        return "wino2"
+    if kh == 1 and _conv_x3_case(x, k, k_w, n):
+        return "x3"
+    if dil == 1 and _conv1x1_stream_case(mode, x, k, k_w, n, kh, kw, out):
+        return "stream1x1"
+    return "igemm"
+
+
+def convt_route(mode, x, w_hwio, g=None):
+    """Route of convt_fwd (mode CONVT_FWD) / convt_dgrad (CONVT_DGRAD, x = dy: four taps inside the contraction).  g: as for conv_route."""
+    _, _, _, k, k_w, n, _, _ = g or _geometry(mode, x, w_hwio)
+    if _bf16_case(k, k_w):
+        return "lowp"
+    if (_conv_x3_case(x, k, k_w, n, taps=4 if mode == CONVT_DGRAD else 1)
+            or (mode == CONVT_FWD and CONVT_X3_NARROW and n >= 32 and _conv_x3_case(x, k, k_w, max(n, CONV_X3_WIDE_N)))):
+        return "x3"
+    return "igemm"
+
+
+def wgrad_route(x, dy, kh, kw, cin_w, dil, out):
+    """Route of conv_wgrad; cin_w: rows of the weight, out: the gradient tensor [kh, kw, cin_w, cout]."""
+    _, h, w, cin = x.shape
+    cout = dy.shape[3]
+    if _bf16_case(cin, cin_w):
+        return "lowp"
+    if _wino4_case(h, w, kh, dil, cin, cout, cin_w) and cout >= 16:
+        return "wino4"
+    if _stem_case(cin, cin_w, cout, kh, dil):
+        return "stem"
+    if USE_WINOGRAD and kh == 3 and dil == 1 and cin_w == cin and h % 2 == 0 and w % 2 == 0 and cin >= 16:
+        return "wino2"
+    if dil == 1 and _conv1x1_wgrad_stream_case(x, dy, cin, cin_w, cout, kh, kw, out):
+        return "stream1x1"
+    return "igemm"
+
+
+def fuses_act_input(t, w_hwio, route=None):
+    """conv_fwd(t, w, pre=(scale, shift, factor)) is available: the 3x3 convolution takes the unfused F(4x4) path in fp32.
+    route: conv_route(CONV_FWD, t, w_hwio) where the caller has it."""
+    return FUSE_BN_INPUT and (route or conv_route(CONV_FWD, t, w_hwio)) == "wino4"
+
+
+def fuses_bn_bwd_input(dy, w_hwio, route=None):
+    """conv_dgrad(dy, w, keep_z=..., bn=...) is available: the data gradient takes the adjoint F(4x4) path (Z shared with the weight gradient).
+    route: conv_route(CONV_DGRAD, dy, w_hwio) where the caller has it."""
+    _, _, cin, cout_w = w_hwio.shape
+    return FUSE_BN_INPUT and cout_w == dy.shape[3] and (route or conv_route(CONV_DGRAD, dy, w_hwio)) == "wino4_adj" and cin >= 16
+
+
+def _launch_gemm(route, mode, x, w_hwio, bias, out, g, dil=1, accumulate=False, stats=None):
+    """The routes that are one launch: lowp, x3, stream1x1, igemm, in any of the four modes.  g: _geometry(mode, x, w_hwio)."""
+    n, h, w, k, k_w, nn, kh, kw = g
+    if out is None:
+        out = empty_nhwc(n, 2 * h, 2 * w, nn, x) if mode == CONVT_FWD else empty_nhwc(n, h, w, nn, x)
+    if route == "lowp":
+        return _igemm_bf16(mode, x, w_hwio, bias, out, n, h, w, k, nn, kh, kw, dil, accumulate, mode in _DGRAD_T)
+    if route == "x3":
+        return _conv_x3(mode, x, w_hwio, bias, out, n, h, w, k, nn, accumulate, stats=stats)
+    if route == "stream1x1":
+        return _conv1x1_stream(mode, x, w_hwio, bias, out, n, h, w, k, nn, accumulate)
+    if USE_TRANSPOSED_DGRAD and mode in _DGRAD_T:
+        return _igemm(_DGRAD_T[mode], x, transposed_weights(w_hwio), bias, out, n, h, w, k, k_w, nn, kh, kw, dil, accumulate)
+    return _igemm(mode, x, w_hwio, bias, out, n, h, w, k, k_w, nn, kh, kw, dil, accumulate)
+
+
+def conv_fwd(x, w_hwio, bias=None, out=None, dil=1, accumulate=False, keep_v=None, stats=None, pre=None):
+    """stats: dict; when the kernel that serves this convolution can take the BatchNorm statistics of its output in its epilogue it fills
+    stats["part"] / stats["nparts"] (blocks.bn_coeff(fused=stats) then skips its pass over the tensor), otherwise leaves it empty.
+    pre = (scale, shift, factor_nc or None), only where fuses_act_input(x, w_hwio): the convolution of max(x * scale + shift, 0) * factor."""
+    g = _geometry(CONV_FWD, x, w_hwio)
+    route = conv_route(CONV_FWD, x, w_hwio, out, dil, g)
+    if pre is not None:
+        assert fuses_act_input(x, w_hwio, route) and dil == 1
+    if route == "wino4":
+        return wino4_conv(x, wino4_weights(w_hwio), bias, out=out, accumulate=accumulate, keep_v=keep_v, dil=dil, pre=pre, stats=stats)
+    if route == "wino2":
+        return wino_conv(x, wino_weights(w_hwio), bias, out=out, accumulate=accumulate, stats=stats)
+    return _launch_gemm(route, CONV_FWD, x, w_hwio, bias, out, g, dil, accumulate, stats)
 
 
 def conv_dgrad(dy, w_hwio, out=None, dil=1, accumulate=False, keep_z=None, bn=None):
     """keep_z: dict that receives {"Z": ...} when the layer takes the adjoint F(4x4) path - hand it to conv_wgrad(..., z=...) of the same layer.
     bn = dict(x, mean, invstd, scale, shift, sums, m_total, mask), only where fuses_bn_bwd_input(dy, w_hwio): the data gradient of
     blocks.bn_bwd_apply(dy, x, ..., relu_shift=shift) without that tensor being written; the weight gradient must then take keep_z's Z."""
-    n, h, w, cout = dy.shape
-    kh, kw, cin, cout_w = w_hwio.shape
-    assert cout_w == cout
+    assert w_hwio.shape[3] == dy.shape[3]
+    g = _geometry(CONV_DGRAD, dy, w_hwio)
+    route = conv_route(CONV_DGRAD, dy, w_hwio, out, dil, g)
     if bn is not None:
-        assert fuses_bn_bwd_input(dy, w_hwio) and dil == 1 and keep_z is not None
+        assert fuses_bn_bwd_input(dy, w_hwio, route) and dil == 1 and keep_z is not None
+    if route == "wino4_adj":
         return wino4_dgrad_adj(dy, w_hwio, out=out, accumulate=accumulate, dil=dil, keep_z=keep_z, bn=bn)
-    if _bf16_case(cout, cout):
-        if out is None:
-            out = empty_nhwc(n, h, w, cin, dy)
-        return _igemm_bf16(CONV_DGRAD, dy, w_hwio, None, out, n, h, w, cout, cin, kh, kw, dil, accumulate, True)
-    if _wino4_case(h, w, kh, dil, cout, cin, cout):
-        if USE_W4_ADJOINT and _x3_case(cout):
-            return wino4_dgrad_adj(dy, w_hwio, out=out, accumulate=accumulate, dil=dil, keep_z=keep_z)
+    if route == "wino4":
         return wino4_conv(dy, wino4_weights(w_hwio, dgrad=True), None, out=out, accumulate=accumulate, dil=dil)
-    if _wino_case(h, w, kh, dil, cout, cin, cout, n, ld(dy), ld(out) if out is not None else cin):
+    if route == "wino2":
         return wino_conv(dy, wino_weights(w_hwio, dgrad=True), None, out=out, accumulate=accumulate)
-    if out is None:
-        out = empty_nhwc(n, h, w, cin, dy)
-    if kh == 1 and _conv_x3_case(dy, cout, cout, cin):
-        return _conv_x3(CONV_DGRAD, dy, w_hwio, None, out, n, h, w, cout, cin, accumulate)
-    if dil == 1 and _conv1x1_stream_case(CONV_DGRAD, dy, cout, cout, cin, kh, kw, out):
-        return _conv1x1_stream(CONV_DGRAD, dy, w_hwio, None, out, n, h, w, cout, cin, accumulate)
-    if USE_TRANSPOSED_DGRAD:
-        _igemm(CONV_DGRAD_T, dy.data_ptr(), ld(dy), transposed_weights(w_hwio).data_ptr(), None, out.data_ptr(), ld(out), n, h, w,
-               cout, cout, cin, kh, kw, dil, int(accumulate))
-    else:
-        _igemm(CONV_DGRAD, dy.data_ptr(), ld(dy), w_hwio.data_ptr(), None, out.data_ptr(), ld(out), n, h, w,
-               cout, cout, cin, kh, kw, dil, int(accumulate))
-    return out
+    return _launch_gemm(route, CONV_DGRAD, dy, w_hwio, None, out, g, dil, accumulate)
+
+
+def convt_fwd(x, w_hwio, bias=None, out=None):
+    g = _geometry(CONVT_FWD, x, w_hwio)
+    return _launch_gemm(convt_route(CONVT_FWD, x, w_hwio, g), CONVT_FWD, x, w_hwio, bias, out, g)
+
+
+def convt_dgrad(dy, w_hwio, out=None, accumulate=False):
+    g = _geometry(CONVT_DGRAD, dy, w_hwio)
+    return _launch_gemm(convt_route(CONVT_DGRAD, dy, w_hwio, g), CONVT_DGRAD, dy, w_hwio, None, out, g, accumulate=accumulate)
 
 
 # ---- weight gradients on a side stream: nothing in the backward chain waits for them (only the optimizer / the gradient all-reduce do),
@@ -800,112 +864,65 @@ def _conv1x1_wgrad_stream_case(x, dy, cin, cin_w, cout, kh=1, kw=1, out=None):
             and ld(dy) % 4 == 0 and dy.data_ptr() % 16 == 0 and (out is None or (out.is_contiguous() and out.data_ptr() % 16 == 0)))
 
 
+def _wgrad_side(body, tensors, on_side=True):
+    """Run a weight gradient's launches: inside the backward pass (wgrad_side_stream active) on the weight-gradient stream, unless the
+    caller asked for on_side=False, else here.  tensors: everything the body reads or writes - _on_side keeps them alive up to the join."""
+    return _on_side(body, tensors) if on_side and _side.get("active") is not None else body()
+
+
 def conv_wgrad(x, dy, kh, kw, cin_w=None, dil=1, out=None, v=None, on_side=True, z=None):
-    if on_side and _side.get("active") is not None:
-        if out is None:
-            out = torch.empty((kh, kw, x.shape[3] if cin_w is None else cin_w, dy.shape[3]), device=x.device, dtype=torch.float32)
-        return _on_side(lambda: _conv_wgrad(x, dy, kh, kw, cin_w, dil, out, v, z), (x, dy, out, v, z))
-    return _conv_wgrad(x, dy, kh, kw, cin_w, dil, out, v, z)
+    cin_w = x.shape[3] if cin_w is None else cin_w
+    if out is None:
+        out = torch.empty((kh, kw, cin_w, dy.shape[3]), device=x.device, dtype=torch.float32)
+    return _wgrad_side(lambda: _conv_wgrad(x, dy, kh, kw, cin_w, dil, out, v, z), (x, dy, out, v, z), on_side)
 
 
-def _conv_wgrad(x, dy, kh, kw, cin_w=None, dil=1, out=None, v=None, z=None):
+_WGRAD_NAME = {"wino2": "wino_wgrad_direct_kernel(+reduce)", "stream1x1": "conv1x1_wgrad_stream_kernel(+sum)",
+               "igemm": "wgrad_tile_kernel/wgrad_kernel(+reduce)"}
+
+
+def _conv_wgrad(x, dy, kh, kw, cin_w, dil, out, v, z):
     n, h, w, cin = x.shape
     cout = dy.shape[3]
-    cin_w = cin if cin_w is None else cin_w
-    if out is None:
-        out = torch.empty((kh, kw, cin_w, cout), device=x.device, dtype=torch.float32)
-    if _bf16_case(cin, cin_w):
+    route = wgrad_route(x, dy, kh, kw, cin_w, dil, out)
+    if route == "lowp":
         return _wgrad_bf16(x, dy, out, n, h, w, cin, cout, kh, kw, dil, 0)
-    if _wino4_case(h, w, kh, dil, cin, cout, cin_w) and cout >= 16:
+    if route == "wino4":
         return wino4_wgrad(x, dy, out=out, v=v, dil=dil, z=z)
-    if _stem_case(cin, cin_w, cout, kh, dil):
+    ends = (x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr())
+    if route == "stem":
         ws = workspace(lib.runet_stem_wgrad_workspace_floats(n, h, w, cin_w, cout, kh), x.device)
-        check(lib.runet_stem_wgrad(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin_w, cout, kh,
-                                   stream()))
+        check(lib.runet_stem_wgrad(*ends, ws.data_ptr(), ws.numel(), n, h, w, cin_w, cout, kh, stream()))
         return out
-    prof = _PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if USE_WINOGRAD and kh == 3 and dil == 1 and cin_w == cin and h % 2 == 0 and w % 2 == 0 and cin >= 16:
-        name = "wino_wgrad_direct_kernel(+reduce)"
-        nws = lib.runet_wino_wgrad_workspace_floats(n, h, w, cin, cout)
-        ws = workspace(nws, x.device)
-        check(lib.runet_wino_wgrad(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin, cout, stream()))
-    elif dil == 1 and _conv1x1_wgrad_stream_case(x, dy, cin, cin_w, cout, kh, kw, out):
-        name = "conv1x1_wgrad_stream_kernel(+sum)"
-        ws = workspace(lib.runet_conv1x1_wgrad_stream_workspace_floats(n, h, w, cin, cout), x.device)
-        check(lib.runet_conv1x1_wgrad_stream(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin, cout,
-                                             stream()))
-    else:
-        name = "wgrad_tile_kernel/wgrad_kernel(+reduce)"
-        nws = lib.runet_conv_wgrad_workspace_floats(n, h, w, cin_w, cout, kh, kw)
-        ws = workspace(nws, x.device)
-        check(lib.runet_conv_wgrad(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   n, h, w, cin, cin_w, cout, kh, kw, dil, 0, stream()))
-    if prof:
-        e1.record()
-        fl = 2.0 * n * h * w * kh * kw * cin_w * cout
-        _PROFILE.append((name, fl, fl * 16.0 / 36.0 if name.startswith("wino") else fl, e0, e1))
+    fl = 2.0 * n * h * w * kh * kw * cin_w * cout
+    with _timed(_WGRAD_NAME[route], fl, fl * 16.0 / 36.0 if route == "wino2" else fl):
+        if route == "wino2":
+            ws = workspace(lib.runet_wino_wgrad_workspace_floats(n, h, w, cin, cout), x.device)
+            check(lib.runet_wino_wgrad(*ends, ws.data_ptr(), ws.numel(), n, h, w, cin, cout, stream()))
+        elif route == "stream1x1":
+            ws = workspace(lib.runet_conv1x1_wgrad_stream_workspace_floats(n, h, w, cin, cout), x.device)
+            check(lib.runet_conv1x1_wgrad_stream(*ends, ws.data_ptr(), ws.numel(), n, h, w, cin, cout, stream()))
+        else:
+            ws = workspace(lib.runet_conv_wgrad_workspace_floats(n, h, w, cin_w, cout, kh, kw), x.device)
+            check(lib.runet_conv_wgrad(*ends, ws.data_ptr(), ws.numel(), n, h, w, cin, cin_w, cout, kh, kw, dil, 0, stream()))
     return out
 
 
 def _wgrad_bf16(x, dy, out, n, h, w, cin, cout, kh, kw, dil, transposed):
-    prof = _PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    nws = _lp("runet_conv_wgrad_{}_workspace_floats")(n, h, w, cin, cout, kh, kw, dil, transposed)
-    ws = workspace(nws, x.device)
-    check(_lp("runet_conv_wgrad_{}")(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin, cout,
-                                    kh, kw, dil, transposed, stream()))
-    if prof:
-        e1.record()
-        fl = 2.0 * n * h * w * kh * kw * cin * cout
-        nbytes = 4.0 * n * h * w * (cin + (4 if transposed else 1) * cout) + 4.0 * kh * kw * cin * cout
-        _PROFILE.append((f"wgrad_{_PRECISION}_kernel", fl, fl, e0, e1, nbytes))      # the span includes the slab reduce
-    return out
-
-
-def convt_fwd(x, w_hwio, bias=None, out=None):
-    n, h, w, cin = x.shape
-    _, _, cin_w, cout = w_hwio.shape
-    if out is None:
-        out = empty_nhwc(n, 2 * h, 2 * w, cout, x)
-    if _bf16_case(cin, cin_w):
-        return _igemm_bf16(CONVT_FWD, x, w_hwio, bias, out, n, h, w, cin, cout, 2, 2, 1, False, False)
-    if _conv_x3_case(x, cin, cin_w, cout) or (CONVT_X3_NARROW and cout >= 32 and _conv_x3_case(x, cin, cin_w, max(cout, CONV_X3_WIDE_N))):
-        return _conv_x3(CONVT_FWD, x, w_hwio, bias, out, n, h, w, cin, cout, False)
-    _igemm(CONVT_FWD, x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None,
-           out.data_ptr(), ld(out), n, h, w, cin, cin_w, cout, 2, 2, 1, 0)
-    return out
-
-
-def convt_dgrad(dy, w_hwio, out=None, accumulate=False):
-    n, h2, w2, cout = dy.shape
-    _, _, cin, cout_w = w_hwio.shape
-    h, w = h2 // 2, w2 // 2
-    if out is None:
-        out = empty_nhwc(n, h, w, cin, dy)
-    if _bf16_case(cout, cout):
-        return _igemm_bf16(CONVT_DGRAD, dy, w_hwio, None, out, n, h, w, cout, cin, 2, 2, 1, accumulate, True)
-    if _conv_x3_case(dy, cout, cout, cin, taps=4):
-        return _conv_x3(CONVT_DGRAD, dy, w_hwio, None, out, n, h, w, cout, cin, accumulate)
-    if USE_TRANSPOSED_DGRAD:
-        _igemm(CONVT_DGRAD_T, dy.data_ptr(), ld(dy), transposed_weights(w_hwio).data_ptr(), None, out.data_ptr(), ld(out), n, h, w,
-               cout, cout, cin, 2, 2, 1, int(accumulate))
-    else:
-        _igemm(CONVT_DGRAD, dy.data_ptr(), ld(dy), w_hwio.data_ptr(), None, out.data_ptr(), ld(out), n, h, w,
-               cout, cout, cin, 2, 2, 1, int(accumulate))
+    fl = 2.0 * n * h * w * kh * kw * cin * cout
+    nbytes = 4.0 * n * h * w * (cin + (4 if transposed else 1) * cout) + 4.0 * kh * kw * cin * cout
+    with _timed(lambda: f"wgrad_{_PRECISION}_kernel", fl, fl, nbytes):      # the span includes the slab reduce
+        nws = _lp("runet_conv_wgrad_{}_workspace_floats")(n, h, w, cin, cout, kh, kw, dil, transposed)
+        ws = workspace(nws, x.device)
+        check(_lp("runet_conv_wgrad_{}")(x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), out.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, cin, cout,
+                                        kh, kw, dil, transposed, stream()))
     return out
 
 
 def convt_wgrad(x, dy, out=None):
-    if _side.get("active") is not None:
-        if out is None:
-            out = torch.empty((2, 2, x.shape[3], dy.shape[3]), device=x.device, dtype=torch.float32)
-        return _on_side(lambda: _convt_wgrad(x, dy, out), (x, dy, out))
-    return _convt_wgrad(x, dy, out)
+    if out is None:
+        out = torch.empty((2, 2, x.shape[3], dy.shape[3]), device=x.device, dtype=torch.float32)
+    return _wgrad_side(lambda: _convt_wgrad(x, dy, out), (x, dy, out))
 
 
 def _convt_wgrad(x, dy, out=None):
@@ -1044,7 +1061,7 @@ def conv_general_fwd(x, w_hwio, bias, stride, pad, dil=1, out=None):
     ho, wo = conv_out_hw(h, w, kh, stride, pad, dil)
     if out is None:
         out = empty_nhwc(n, ho, wo, cout, x)
-    check(lib.runet_conv2d_general(x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
+    check(lib.runet_conv2d_general(x.data_ptr(), ld(x), w_hwio.data_ptr(), _ptr(bias), out.data_ptr(),
                                    ld(out), n, h, w, cin, cin_w, cout, kh, kw, stride, pad, dil, CONV_FWD, 0, stream()))
     return out
 
@@ -1081,10 +1098,10 @@ def convt4_fwd(x, w_hwio, bias, out=None, stats=None):
         out = empty_nhwc(n, 2 * h, 2 * w, cout, x)
     if stats is not None and EPILOGUE_STATS and cout >= 32:
         sp = _stats_buf(stats, lib.runet_convt4_igemm_stats_parts(n, h, w, cout), cout, x.device)
-        check(lib.runet_convt4_igemm_stats(x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
+        check(lib.runet_convt4_igemm_stats(x.data_ptr(), ld(x), w_hwio.data_ptr(), _ptr(bias), out.data_ptr(),
                                            ld(out), n, h, w, cin, cout, sp, stream()))
         return out
-    check(lib.runet_convt4_igemm(x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out),
+    check(lib.runet_convt4_igemm(x.data_ptr(), ld(x), w_hwio.data_ptr(), _ptr(bias), out.data_ptr(), ld(out),
                                  n, h, w, cin, cout, CONVT_FWD, 0, stream()))
     return out
 
@@ -1128,7 +1145,7 @@ def conv_rect_fwd(x, w_hwio, bias, stride, pad, dil=1, out=None):
     ho, wo = conv_rect_out_hw(h, w, kh, kw, stride, pad, dil)
     if out is None:
         out = empty_nhwc(n, ho, wo, cout, x)
-    check(lib.runet_conv2d_rect(x.data_ptr(), ld(x), w_hwio.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), ld(out),
+    check(lib.runet_conv2d_rect(x.data_ptr(), ld(x), w_hwio.data_ptr(), _ptr(bias), out.data_ptr(), ld(out),
                                 n, h, w, cin, cin_w, cout, kh, kw, stride, ph, pw, dh, dw, CONV_FWD, 0, stream()))
     return out
 
@@ -1163,9 +1180,7 @@ def conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil=1, cin_w=None, out=None, on_
     cin_w = x.shape[3] if cin_w is None else cin_w
     if out is None:
         out = torch.empty((kh, kw, cin_w, dy.shape[3]), device=x.device, dtype=torch.float32)
-    if on_side and _side.get("active") is not None:
-        return _on_side(lambda: _conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil, cin_w, out), (x, dy, out))
-    return _conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil, cin_w, out)
+    return _wgrad_side(lambda: _conv_rect_wgrad(x, dy, kh, kw, stride, pad, dil, cin_w, out), (x, dy, out), on_side)
 
 
 # RUNET_NO_CONVT3_CLASSES=1: the k3-s2 transposed forward as the data gradient of the stride-2 convolution (9 taps per output pixel, 1 / 2 / 4 live)
@@ -1194,7 +1209,7 @@ def convt3_fwd(x, w_t3, bias=None, out=None, classes=None):
     cout = w_t3.shape[3]
     if out is None:
         out = empty_nhwc(n, 2 * h, 2 * w, cout, x)
-    bp = bias.data_ptr() if bias is not None else None
+    bp = _ptr(bias)
     if CONVT3_CLASSES if classes is None else classes:
         check(lib.runet_convt3_fwd(x.data_ptr(), ld(x), convt3_class_weights(w_t3).data_ptr(), bp, out.data_ptr(), ld(out), n, h, w, cin, cout, stream()))
         return out
@@ -1222,9 +1237,7 @@ def convt3_wgrad(x, dy, out=None, on_side=True):
     if out is None:
         out = torch.empty((3, 3, cin, cout), device=x.device, dtype=torch.float32)
     gt = torch.empty((3, 3, cout, cin), device=x.device, dtype=torch.float32)
-    if on_side and _side.get("active") is not None:
-        return _on_side(lambda: _convt3_wgrad(x, dy, gt, out), (x, dy, gt, out))
-    return _convt3_wgrad(x, dy, gt, out)
+    return _wgrad_side(lambda: _convt3_wgrad(x, dy, gt, out), (x, dy, gt, out), on_side)
 
 
 # ------------------------------------------------------------------------------- Winograd F(4x4,3x3), unfused (deep layers)
@@ -1287,7 +1300,7 @@ def wino4_conv(x, U, bias=None, out=None, accumulate=False, keep_v=None, dil=1, 
     nn_ = U.kn[1] if x3 else U.shape[2]
     if out is None:
         out = empty_nhwc(n, h, w, nn_, x)
-    bp = bias.data_ptr() if bias is not None else None
+    bp = _ptr(bias)
     t = n * (h // 4) * (w // 4)
     sparts = lib.runet_wino4_output_stats_parts(n, h, w, nn_, dil) if (stats is not None and EPILOGUE_STATS) else 0
     if _PROFILE is None and keep_v is None and pre is None and sparts == 0:
@@ -1308,20 +1321,14 @@ def wino4_conv(x, U, bias=None, out=None, accumulate=False, keep_v=None, dil=1, 
         check(lib.runet_wino4_input(x.data_ptr(), ld(x), k, n, h, w, dil, 0, V, stream()))
     else:
         sc, sh, fac = pre
-        check(lib.runet_wino4_input_act(x.data_ptr(), ld(x), k, n, h, w, dil, sc.data_ptr(), sh.data_ptr(), fac.data_ptr() if fac is not None else None,
+        check(lib.runet_wino4_input_act(x.data_ptr(), ld(x), k, n, h, w, dil, sc.data_ptr(), sh.data_ptr(), _ptr(fac),
                                         V, stream()))
-    if _PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if x3:
-        check(lib.runet_gemm_x3_batched(V, k, t * k, U.data_ptr(), M, nn_, t * nn_, 36, t, k, nn_, stream()))
-    else:
-        check(lib.runet_gemm_batched(V, k, t * k, U.data_ptr(), k * nn_, M, nn_, t * nn_, 36, t, k, nn_, stream()))
-    if _PROFILE is not None:
-        e1.record()
-        fl = 2.0 * 36 * t * k * nn_          # the position-GEMMs' own FLOPs; the convolution they implement is 4x that in direct-conv FLOPs
-        kname = lib.runet_gemm_x3_kernel_name(36, t, k, nn_) if x3 else lib.runet_gemm_batched_kernel_name(36, t, k, nn_)
-        _PROFILE.append((kname.decode(), 4.0 * fl, fl, e0, e1))
+    fl = 2.0 * 36 * t * k * nn_              # the position-GEMMs' own FLOPs; the convolution they implement is 4x that in direct-conv FLOPs
+    with _timed(lambda: (lib.runet_gemm_x3_kernel_name if x3 else lib.runet_gemm_batched_kernel_name)(36, t, k, nn_).decode(), 4.0 * fl, fl):
+        if x3:
+            check(lib.runet_gemm_x3_batched(V, k, t * k, U.data_ptr(), M, nn_, t * nn_, 36, t, k, nn_, stream()))
+        else:
+            check(lib.runet_gemm_batched(V, k, t * k, U.data_ptr(), k * nn_, M, nn_, t * nn_, 36, t, k, nn_, stream()))
     if sparts > 0:
         sp = _stats_buf(stats, sparts, nn_, x.device)
         check(lib.runet_wino4_output_stats(M, nn_, n, h, w, bp, out.data_ptr(), ld(out), int(accumulate), sp, stream()))
@@ -1351,16 +1358,11 @@ def wino4_dgrad_adj(dy, w_hwio, out=None, accumulate=False, dil=1, keep_z=None, 
     else:
         bx, mk = bn["x"], bn.get("mask")
         check(lib.runet_wino4_input_bn_bwd(dy.data_ptr(), ld(dy), bx.data_ptr(), ld(bx), cout, n, h, w, dil, bn["mean"].data_ptr(), bn["invstd"].data_ptr(),
-                                           bn["scale"].data_ptr(), bn["shift"].data_ptr(), bn["sums"].data_ptr(), mk.data_ptr() if mk is not None else None,
+                                           bn["scale"].data_ptr(), bn["shift"].data_ptr(), bn["sums"].data_ptr(), _ptr(mk),
                                            int(bn["m_total"]), Z, stream()))
-    if _PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.runet_gemm_x3_batched(Z, cout, t * cout, Ua.data_ptr(), M, cin, t * cin, 36, t, cout, cin, stream()))
-    if _PROFILE is not None:
-        e1.record()
-        fl = 2.0 * 36 * t * cout * cin
-        _PROFILE.append((lib.runet_gemm_x3_kernel_name(36, t, cout, cin).decode(), 4.0 * fl, fl, e0, e1))
+    fl = 2.0 * 36 * t * cout * cin
+    with _timed(lambda: lib.runet_gemm_x3_kernel_name(36, t, cout, cin).decode(), 4.0 * fl, fl):
+        check(lib.runet_gemm_x3_batched(Z, cout, t * cout, Ua.data_ptr(), M, cin, t * cin, 36, t, cout, cin, stream()))
     check(lib.runet_wino4_output_adj(M, cin, n, h, w, dil, out.data_ptr(), ld(out), int(accumulate), stream()))
     return out
 
@@ -1392,17 +1394,10 @@ def wino4_wgrad(x, dy, out=None, v=None, dil=1, z=None):
     else:
         assert z.numel() == 36 * t * cout
         Z = z.data_ptr()
-    if _PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if x3:
-        check(lib.runet_gemm_x3_tn_batched(V, cin, t * cin, Z, cout, t * cout, dU, 36, t, cin, cout, rps, stream()))
-    else:
-        check(lib.runet_gemm_tn_batched(V, cin, t * cin, Z, cout, t * cout, dU, 36, t, cin, cout, rps, stream()))
-    if _PROFILE is not None:
-        e1.record()
-        fl = 2.0 * 36 * t * cin * cout
-        _PROFILE.append(("gemm_tn_x3_kernel" if x3 else ("gemm_tn_kernel<true>" if t % 16 == 0 else "gemm_tn_kernel<false>"), 4.0 * fl, fl, e0, e1))
+    fl = 2.0 * 36 * t * cin * cout
+    with _timed("gemm_tn_x3_kernel" if x3 else ("gemm_tn_kernel<true>" if t % 16 == 0 else "gemm_tn_kernel<false>"), 4.0 * fl, fl):
+        fn = lib.runet_gemm_x3_tn_batched if x3 else lib.runet_gemm_tn_batched
+        check(fn(V, cin, t * cin, Z, cout, t * cout, dU, 36, t, cin, cout, rps, stream()))
     check(lib.runet_wino4_wgrad_output(dU, -(-t // rps), cin, cout, out.data_ptr(), stream()))
     return out
 
