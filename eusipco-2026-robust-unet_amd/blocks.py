@@ -214,6 +214,15 @@ def bn_bwd_apply(dy, x, mean, invstd, scale, use, m_total, act=None, mask=None, 
     return out
 
 
+def dx_sums(sums, training, sync=None, count=0):
+    """Which sums enter a BatchNorm backward's dx, given its LOCAL (dgamma | dbeta) sums over `count` elements -> (use, m_total): zeros in eval
+    mode (the batch-statistics terms vanish); the local sums with m_total 0 (the kernel divides by its own element count); or, under SyncBN,
+    the all-reduced sums with the global count."""
+    if not training:
+        return zeros(sums.numel(), sums.device), 0
+    return (sums, 0) if sync is None else sync.reduce_sums(sums, count)
+
+
 def bn_backward(dy, x, mean, invstd, scale, sums, act=None, mask=None, out=None, sync=None, relu_shift=None, training=True):
     """sums: [2c] destination for (dgamma | dbeta), always the LOCAL sums.  act/mask: fused relu(+dropout) backward from the saved
     activation; relu_shift (the forward's shift vector, with `scale` the forward's scale): the same from x alone, act is not read.
@@ -222,10 +231,7 @@ def bn_backward(dy, x, mean, invstd, scale, sums, act=None, mask=None, out=None,
     terms, while dgamma / dbeta keep their form (sums over dy * xhat and dy).  -> dx"""
     n, h, w, c = x.shape
     bn_bwd_reduce(dy, x, mean, invstd, scale, sums, act, mask, relu_shift)
-    if not training:
-        use, m_total = zeros(2 * c, x.device), 0
-    else:
-        use, m_total = (sums, 0) if sync is None else sync.reduce_sums(sums, n * h * w)
+    use, m_total = dx_sums(sums, training, sync, n * h * w)
     return bn_bwd_apply(dy, x, mean, invstd, scale, use, m_total, act, mask, out, relu_shift)
 
 
@@ -264,6 +270,10 @@ def chan_sum(x, out):
 
 def vec(n, device):
     return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
 
 # ------------------------------------------------------------------------------- Conv2d -> BatchNorm2d -> ReLU (the baselines' step)
@@ -385,16 +395,9 @@ def rb_forward(x, p: RBParams, training, mask=None, save=True, stats_hook=None, 
         if pool:
             pooled = ops.empty_nhwc(n, h // 2, w // 2, c, x)
             pool_idx = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.uint8)
-    if relu_bits is not None or pooled is not None:
-        check(lib.runet_rb_out_ex(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r),
-                                  ss.data_ptr() if ss is not None else None, hs.data_ptr() if hs is not None else None, out.data_ptr(),
-                                  ops.ld(out), relu_bits.data_ptr() if relu_bits is not None else None,
-                                  pooled.data_ptr() if pooled is not None else None, ops.ld(pooled) if pooled is not None else 0,
-                                  pool_idx.data_ptr() if pool_idx is not None else None, n, h, w, c, st))
-    else:
-        check(lib.runet_rb_out(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r),
-                               ss.data_ptr() if ss is not None else None, hs.data_ptr() if hs is not None else None, out.data_ptr(),
-                               ops.ld(out), P, hw, c, st))
+    check(lib.runet_rb_out_ex(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r), _ptr(ss), _ptr(hs),
+                              out.data_ptr(), ops.ld(out), _ptr(relu_bits), _ptr(pooled), ops.ld(pooled) if pooled is not None else 0, _ptr(pool_idx),
+                              n, h, w, c, st))
     if pool and pooled is None:
         pooled, pool_idx = maxpool_forward(out)
     if not save:
@@ -431,28 +434,35 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None
     relu_bits = ctx.get("relu_bits") if _edge("bwd1") else None
     if dpool is not None and not _edge("bwd1"):
         dout, dpool = maxpool_backward(dpool, pool_idx, dx=dout), None
-    if dpool is not None or relu_bits is not None:
-        check(lib.runet_rb_bwd1_ex(dout.data_ptr(), ops.ld(dout), dpool.data_ptr() if dpool is not None else None,
-                                   ops.ld(dpool) if dpool is not None else 0, pool_idx.data_ptr() if dpool is not None else None,
-                                   out.data_ptr(), ops.ld(out), relu_bits.data_ptr() if relu_bits is not None else None, t2.data_ptr(), ops.ld(t2),
-                                   A.data_ptr(), B.data_ptr(), sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), n, h, w, c, st))
-    else:
-        check(lib.runet_rb_bwd1(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(),
-                                sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), P, hw, c, st))
+    check(lib.runet_rb_bwd1_ex(dout.data_ptr(), ops.ld(dout), _ptr(dpool), ops.ld(dpool) if dpool is not None else 0,
+                               pool_idx.data_ptr() if dpool is not None else None, out.data_ptr(), ops.ld(out), _ptr(relu_bits), t2.data_ptr(),
+                               ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), n, h, w, c, st))
     dsm = torch.empty((P, 2), device=dev, dtype=torch.float32)
     dwsa = sink.buf(pre, [("sa.conv1.weight", (7, 7, 2, 1))])
     ws = scratch(lib.runet_sa_conv7_bwd_workspace_floats(n, h, w), dev)
     check(lib.runet_sa_conv7_bwd(smap.data_ptr(), dq.data_ptr(), p.wsa.data_ptr(), dsm.data_ptr(), dwsa.data_ptr(), ws.data_ptr(), n, h, w, st))
     sdu, sdut = sm.f(n * c), sm.f(n * c)
     sync, tr = ctx["sync"], ctx["training"]
-    sums_s_fused = None
-    if p.ws is not None and FUSED_SHORTCUT_BN_SUMS and not (sync is not None and tr):
-        # dv is the shortcut BatchNorm's incoming gradient: its backward reduction rides in this pass (one read of r instead of a pass over dv and r)
-        sums_s_fused = sink.buf(pre, [("shortcut.1.weight", (c,)), ("shortcut.1.bias", (c,))])
+    # The shortcut BatchNorm's backward (blocks with a convolution shortcut: dv, final since rb_bwd1, is its incoming gradient and r its input)
+    # is decided here, once:
+    #   sc_sums  where its local sums come from - "bwd2": runet_rb_bwd2_bn takes them in its pass over dv (one read of r instead of a pass
+    #            over dv and r); "early" / "late": bn_bwd_reduce(dv, r), in front of rb_bwd3 when something there waits for the sums (bn2's
+    #            all-reduce, which they share under SyncBN, or rb_bwd3_sc), else behind conv1's gradients
+    #   sc_bwd3  where dr is produced - inside runet_rb_bwd3_sc, written over dv (training mode), or by bn_bwd_apply behind conv1's gradients
+    has_sc = p.ws is not None
+    synced = sync is not None and tr
+    sc_bwd3 = has_sc and tr and _edge("bwd3")
+    sc_sums = None if not has_sc else "bwd2" if (FUSED_SHORTCUT_BN_SUMS and not synced) else "early" if (synced or sc_bwd3) else "late"
+    sums_s = sink.buf(pre, [("shortcut.1.weight", (c,)), ("shortcut.1.bias", (c,))]) if has_sc else None
+
+    def sc_reduce():
+        bn_bwd_reduce(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], sums_s)
+
+    if sc_sums == "bwd2":
         ws = scratch(lib.runet_rb_bwd2_bn_workspace_floats(n, hw, c), dev)
         check(lib.runet_rb_bwd2_bn(dv.data_ptr(), ops.ld(dv), t2.data_ptr(), ops.ld(t2), sa.data_ptr(), dsm.data_ptr(), amax.data_ptr(), r.data_ptr(),
                                    ops.ld(r), ctx["mean_s"].data_ptr(), ctx["invstd_s"].data_ptr(), n, hw, c, ws.data_ptr(), ws.numel(),
-                                   sdu.data_ptr(), sdut.data_ptr(), sums_s_fused.data_ptr(), st))
+                                   sdu.data_ptr(), sdut.data_ptr(), sums_s.data_ptr(), st))
     else:
         ws = _ws(n, hw, c, dev)
         check(lib.runet_rb_bwd2(dv.data_ptr(), ops.ld(dv), t2.data_ptr(), ops.ld(t2), sa.data_ptr(), dsm.data_ptr(), amax.data_ptr(), n, hw, c,
@@ -467,34 +477,20 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None
                            ctx["tval"].data_ptr(), ctx["mean2"].data_ptr(), ctx["invstd2"].data_ptr(), n, c, cr, ws.data_ptr(),
                            davg.data_ptr(), dmx.data_ptr(), sums2.data_ptr(), dw0p.data_ptr(), dw2p.data_ptr(), st))
     dt2 = ops.empty_nhwc(n, h, w, c, x)
-    use_s = None
-    if not tr:
-        use2, m_total = zeros(2 * c, dev), 0
-    elif sync is None:
-        use2, m_total = sums2, 0
-    elif p.ws is not None:                   # SyncBN: the shortcut BatchNorm's sums (dv is final since rb_bwd1) share bn2's all-reduce
-        sums_s = sink.buf(pre, [("shortcut.1.weight", (c,)), ("shortcut.1.bias", (c,))])
-        bn_bwd_reduce(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], sums_s)
+    if sc_sums == "early":
+        sc_reduce()
+    if has_sc and synced:                    # SyncBN: the shortcut BatchNorm's sums share bn2's all-reduce
         (use2, m_total), (use_s, m_s) = sync.reduce_sums_many([sums2, sums_s], [P, P])
     else:
-        use2, m_total = sync.reduce_sums(sums2, P)
-    # the shortcut BatchNorm's backward rides in rb_bwd3 (training mode): its sums, over the dv that is final since rb_bwd1, are taken here
-    # instead of after conv1's gradients, and rb_bwd3 writes dr over dv.  Eval mode keeps the separate path.
-    dr = None
-    if p.ws is not None and tr and _edge("bwd3"):
-        if use_s is None:
-            if sums_s_fused is not None:
-                use_s, m_s = sums_s_fused, 0
-            else:
-                sums_s = sink.buf(pre, [("shortcut.1.weight", (c,)), ("shortcut.1.bias", (c,))])
-                bn_bwd_reduce(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], sums_s)
-                use_s, m_s = (sums_s, 0) if sync is None else sync.reduce_sums(sums_s, P)
+        use2, m_total = dx_sums(sums2, tr, sync, P)
+        # use_s is chosen here and read later: in training mode it IS sums_s, which a "late" reduce fills only behind conv1's gradients
+        use_s, m_s = dx_sums(sums_s, tr) if has_sc else (None, 0)
+    if sc_bwd3:
         check(lib.runet_rb_bwd3_sc(dv.data_ptr(), ops.ld(dv), t2.data_ptr(), ops.ld(t2), sa.data_ptr(), dsm.data_ptr(), amax.data_ptr(),
                                    ctx["ca"].data_ptr(), davg.data_ptr(), dmx.data_ptr(), ctx["idx"].data_ptr(), ctx["mean2"].data_ptr(),
                                    ctx["invstd2"].data_ptr(), ctx["s2"].data_ptr(), use2.data_ptr(), dt2.data_ptr(), ops.ld(dt2), r.data_ptr(),
                                    ops.ld(r), ctx["mean_s"].data_ptr(), ctx["invstd_s"].data_ptr(), ctx["ss"].data_ptr(), use_s.data_ptr(), m_s,
                                    P, hw, c, m_total, st))
-        dr = dv
     else:
         check(lib.runet_rb_bwd3(dv.data_ptr(), ops.ld(dv), t2.data_ptr(), ops.ld(t2), sa.data_ptr(), dsm.data_ptr(), amax.data_ptr(),
                                 ctx["ca"].data_ptr(), davg.data_ptr(), dmx.data_ptr(), ctx["idx"].data_ptr(), ctx["mean2"].data_ptr(),
@@ -515,10 +511,7 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None
         # conv1 on the adjoint F(4x4) path: the BatchNorm-backward dx rides in the loads of Z = A dt1 A^T, which both of conv1's gradients read
         # - dt1 itself is never written (two passes over the tensor and one launch less)
         bn_bwd_reduce(da1, t1, ctx["mean1"], ctx["invstd1"], ctx["s1"], sums1, None, ctx["mask"], ctx["h1"])
-        if not tr:
-            use1, m1 = zeros(2 * c, dev), 0
-        else:
-            use1, m1 = (sums1, 0) if sync is None else sync.reduce_sums(sums1, P)
+        use1, m1 = dx_sums(sums1, tr, sync, P)
         bn1 = dict(x=t1, mean=ctx["mean1"], invstd=ctx["invstd1"], scale=ctx["s1"], shift=ctx["h1"], sums=use1, m_total=m1, mask=ctx["mask"])
         if p.ws is not None:
             dx1 = ops.conv_dgrad(da1, p.w1, keep_z=kz1, bn=bn1)
@@ -535,16 +528,10 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None
                    z=kz1.get("Z"))
     ctx["v1"] = None
     dx = None
-    if p.ws is not None:
-        if dr is not None:
-            pass                                       # rb_bwd3 has written it
-        elif use_s is not None:
-            dr = bn_bwd_apply(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], use_s, m_s, out=dv)
-        elif sums_s_fused is not None:
-            dr = bn_bwd_apply(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], sums_s_fused if tr else zeros(2 * c, dev), 0, out=dv)
-        else:
-            sums_s = sink.buf(pre, [("shortcut.1.weight", (c,)), ("shortcut.1.bias", (c,))])
-            dr = bn_backward(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], sums_s, out=dv, sync=sync, training=tr)
+    if has_sc:
+        if sc_sums == "late":
+            sc_reduce()
+        dr = dv if sc_bwd3 else bn_bwd_apply(dv, r, ctx["mean_s"], ctx["invstd_s"], ctx["ss"], use_s, m_s, out=dv)
         ops.conv_wgrad(x, dr, 1, 1, cin_w=p.cin_w, out=sink.buf(pre, [("shortcut.0.weight", (1, 1, p.cin_w, c))]))
         if need_dx:
             dx = dx1
@@ -773,47 +760,43 @@ def gate_backward(gc, up, skip, p: UpGateParams, datt, dup, sink, pre=""):
     sync, tr = gc["sync"], gc["training"]
     ds = bn_backward(dsbn, gc["s"], gc["mean_p"], gc["invstd_p"], gc["sp"], sums_p, out=dsbn, sync=sync, training=tr)
     dpre = ops.empty_nhwc(n, h, w, f, skip)
-    fused_sums = FUSED_GATE_BN_SUMS and not (sync is not None and tr)
-    if fused_sums:
-        # the gate's two BatchNorm-backward reductions ride in the kernel that produces their incoming gradient
+    g1, x1 = gc["g1"], gc["x1"]
+    bn_g, bn_x = (gc["mean_g"], gc["invstd_g"], gc["sg"]), (gc["mean_x"], gc["invstd_x"], gc["sx"])
+    synced = sync is not None and tr
+    # where the two branches' BatchNorm-backward sums come from, and which sums enter dx (dx_sums): taken in the kernel that produces their
+    # incoming gradient (runet_ag_bwd2_bn); SyncBN - two reductions, ready together, one all-reduce; or plain - each branch's own bn_backward
+    if FUSED_GATE_BN_SUMS and not synced:
         ws = scratch(lib.runet_ag_bwd2_bn_workspace_floats(P, f), dev)
-        check(lib.runet_ag_bwd2_bn(ds.data_ptr(), gc["g1"].data_ptr(), ops.ld(gc["g1"]), gc["x1"].data_ptr(), ops.ld(gc["x1"]), gc["sg"].data_ptr(),
-                                   gc["hg"].data_ptr(), gc["sx"].data_ptr(), gc["hx"].data_ptr(), p.wpsi.data_ptr(), gc["mean_g"].data_ptr(),
-                                   gc["invstd_g"].data_ptr(), gc["mean_x"].data_ptr(), gc["invstd_x"].data_ptr(), dpre.data_ptr(), ops.ld(dpre),
-                                   ws.data_ptr(), ws.numel(), dwpsi_db.data_ptr(), sums_g.data_ptr(), sums_x.data_ptr(), P, f, st))
-        use_g, use_x = (sums_g, sums_x) if tr else (zeros(2 * f, dev), zeros(2 * f, dev))
-        dg1 = bn_bwd_apply(dpre, gc["g1"], gc["mean_g"], gc["invstd_g"], gc["sg"], use_g, 0)
-        ops.conv_wgrad(up, dg1, 1, 1, out=wg_b[:cg * f])
-        chan_sum(dg1, wg_b[cg * f:])
-        ops.conv_dgrad(dg1, p.wg, out=dup, accumulate=True)
-        del dg1
-        dx1 = bn_bwd_apply(dpre, gc["x1"], gc["mean_x"], gc["invstd_x"], gc["sx"], use_x, 0, out=dpre)
-        ops.conv_wgrad(skip, dx1, 1, 1, out=wx_b[:c * f])
-        chan_sum(dx1, wx_b[c * f:])
-        ops.conv_dgrad(dx1, p.wx, out=dskip, accumulate=True)
-        return dskip
-    ws = _ws(n, h * w, f, dev)
-    check(lib.runet_ag_bwd2(ds.data_ptr(), gc["g1"].data_ptr(), ops.ld(gc["g1"]), gc["x1"].data_ptr(), ops.ld(gc["x1"]), gc["sg"].data_ptr(),
-                            gc["hg"].data_ptr(), gc["sx"].data_ptr(), gc["hx"].data_ptr(), p.wpsi.data_ptr(), dpre.data_ptr(), ops.ld(dpre),
-                            ws.data_ptr(), dwpsi_db.data_ptr(), P, f, st))
-    if sync is not None and tr:              # SyncBN: both BatchNorms' sums are ready here - one all-reduce
-        bn_bwd_reduce(dpre, gc["g1"], gc["mean_g"], gc["invstd_g"], gc["sg"], sums_g)
-        bn_bwd_reduce(dpre, gc["x1"], gc["mean_x"], gc["invstd_x"], gc["sx"], sums_x)
-        (use_g, m_g), (use_x, m_x) = sync.reduce_sums_many([sums_g, sums_x], [P, P])
-        dg1 = bn_bwd_apply(dpre, gc["g1"], gc["mean_g"], gc["invstd_g"], gc["sg"], use_g, m_g)
+        check(lib.runet_ag_bwd2_bn(ds.data_ptr(), g1.data_ptr(), ops.ld(g1), x1.data_ptr(), ops.ld(x1), gc["sg"].data_ptr(), gc["hg"].data_ptr(),
+                                   gc["sx"].data_ptr(), gc["hx"].data_ptr(), p.wpsi.data_ptr(), gc["mean_g"].data_ptr(), gc["invstd_g"].data_ptr(),
+                                   gc["mean_x"].data_ptr(), gc["invstd_x"].data_ptr(), dpre.data_ptr(), ops.ld(dpre), ws.data_ptr(), ws.numel(),
+                                   dwpsi_db.data_ptr(), sums_g.data_ptr(), sums_x.data_ptr(), P, f, st))
+        use_g, use_x = dx_sums(sums_g, tr), dx_sums(sums_x, tr)
     else:
-        dg1 = bn_backward(dpre, gc["g1"], gc["mean_g"], gc["invstd_g"], gc["sg"], sums_g, training=tr)
-    ops.conv_wgrad(up, dg1, 1, 1, out=wg_b[:cg * f])
-    chan_sum(dg1, wg_b[cg * f:])
-    ops.conv_dgrad(dg1, p.wg, out=dup, accumulate=True)
-    del dg1
-    if sync is not None and tr:
-        dx1 = bn_bwd_apply(dpre, gc["x1"], gc["mean_x"], gc["invstd_x"], gc["sx"], use_x, m_x, out=dpre)
-    else:
-        dx1 = bn_backward(dpre, gc["x1"], gc["mean_x"], gc["invstd_x"], gc["sx"], sums_x, out=dpre, training=tr)
-    ops.conv_wgrad(skip, dx1, 1, 1, out=wx_b[:c * f])
-    chan_sum(dx1, wx_b[c * f:])
-    ops.conv_dgrad(dx1, p.wx, out=dskip, accumulate=True)
+        ws = _ws(n, h * w, f, dev)
+        check(lib.runet_ag_bwd2(ds.data_ptr(), g1.data_ptr(), ops.ld(g1), x1.data_ptr(), ops.ld(x1), gc["sg"].data_ptr(), gc["hg"].data_ptr(),
+                                gc["sx"].data_ptr(), gc["hx"].data_ptr(), p.wpsi.data_ptr(), dpre.data_ptr(), ops.ld(dpre), ws.data_ptr(),
+                                dwpsi_db.data_ptr(), P, f, st))
+        use_g = use_x = None
+        if synced:
+            bn_bwd_reduce(dpre, g1, *bn_g, sums_g)
+            bn_bwd_reduce(dpre, x1, *bn_x, sums_x)
+            use_g, use_x = sync.reduce_sums_many([sums_g, sums_x], [P, P])
+
+    def branch(t, bn, sums, use, src, wt, wb, dsrc, out=None):
+        """One 1x1 branch: the gradient of its convolution's output t (dpre through its BatchNorm), its weight and bias gradients, and its
+        data gradient accumulated into dsrc.  use: (sums, m_total) that enter dx, None: the branch reduces its own (plain mode)"""
+        if use is None:
+            d = bn_backward(dpre, t, *bn, sums, out=out, training=tr)
+        else:
+            d = bn_bwd_apply(dpre, t, *bn, *use, out=out)
+        nw = src.shape[3] * f
+        ops.conv_wgrad(src, d, 1, 1, out=wb[:nw])
+        chan_sum(d, wb[nw:])
+        ops.conv_dgrad(d, wt, out=dsrc, accumulate=True)
+
+    branch(g1, bn_g, sums_g, use_g, up, p.wg, wg_b, dup)
+    branch(x1, bn_x, sums_x, use_x, skip, p.wx, wx_b, dskip, out=dpre)
     return dskip
 
 
@@ -884,7 +867,7 @@ def bn_backward_pooled(dpool, idx, x, mean, invstd, scale, sums, relu_shift, tra
     check(lib.runet_bn_bwd_reduce_pooled(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), n, h, w, c, mean.data_ptr(),
                                          invstd.data_ptr(), _ws(n, h * w, c, x.device).data_ptr(), sums.data_ptr(), scale.data_ptr(),
                                          relu_shift.data_ptr(), st))
-    use = sums if training else zeros(2 * c, x.device)
+    use = dx_sums(sums, training)[0]
     dx = ops.empty_nhwc(n, h, w, c, x)
     check(lib.runet_bn_bwd_apply_pooled(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), dx.data_ptr(), ops.ld(dx), n, h, w, c,
                                         mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), use.data_ptr(), 0, relu_shift.data_ptr(), st))
@@ -914,7 +897,7 @@ def bn_backward_leaky(dy, x, mean, invstd, scale, sums, shift, slope, training=T
     st = ops.stream()
     check(lib.runet_bn_bwd_reduce_leaky(dy.data_ptr(), ops.ld(dy), x.data_ptr(), ops.ld(x), n, hw, c, mean.data_ptr(), invstd.data_ptr(),
                                         _ws(n, hw, c, x.device).data_ptr(), sums.data_ptr(), scale.data_ptr(), shift.data_ptr(), float(slope), st))
-    use = sums if training else zeros(2 * c, x.device)
+    use = dx_sums(sums, training)[0]
     if out is None:
         out = ops.empty_nhwc(n, h, w, c, x)
     check(lib.runet_bn_bwd_apply_leaky(dy.data_ptr(), ops.ld(dy), x.data_ptr(), ops.ld(x), out.data_ptr(), ops.ld(out), n * hw, hw, c,
@@ -944,7 +927,7 @@ def bn_backward_pooled_leaky(dpool, idx, x, mean, invstd, scale, sums, shift, sl
     check(lib.runet_bn_bwd_reduce_pooled_leaky(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), n, h, w, c, mean.data_ptr(),
                                                invstd.data_ptr(), _ws(n, h * w, c, x.device).data_ptr(), sums.data_ptr(), scale.data_ptr(),
                                                shift.data_ptr(), float(slope), st))
-    use = sums if training else zeros(2 * c, x.device)
+    use = dx_sums(sums, training)[0]
     dx = ops.empty_nhwc(n, h, w, c, x)
     check(lib.runet_bn_bwd_apply_pooled_leaky(dpool.data_ptr(), ops.ld(dpool), idx.data_ptr(), x.data_ptr(), ops.ld(x), dx.data_ptr(), ops.ld(dx), n,
                                               h, w, c, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), use.data_ptr(), 0, shift.data_ptr(),
@@ -1043,7 +1026,7 @@ def hr_head_backward(dprob, prob, t, scale, shift, w, mean, invstd, saved=None, 
         ws = scratch(lib.runet_hr_head_bwd_workspace_floats(n, h, wd, c), dev)
         check(lib.runet_hr_head_bwd_reduce(dz.data_ptr(), t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), w.data_ptr(), mean.data_ptr(),
                                            invstd.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), n, h, wd, c, st))
-        use = out if training else zeros(2 * c, dev)
+        use = dx_sums(out, training)[0]
         dt = ops.empty_nhwc(n, h, wd, c, t)
         check(lib.runet_hr_head_bwd_apply(dz.data_ptr(), t.data_ptr(), ops.ld(t), w.data_ptr(), dt.data_ptr(), ops.ld(dt), n, h, wd, c, mean.data_ptr(),
                                           invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), use.data_ptr(), 0, st))
@@ -1079,7 +1062,7 @@ def bn_bilinear_backward(dy, x, mean, invstd, scale, sums, s, training=True, fus
     ws = scratch(lib.runet_bilinear_nhwc_bwd_sums_workspace_floats(n, h, w, c), x.device)
     check(lib.runet_bilinear_nhwc_bwd_sums(dy.data_ptr(), ops.ld(dy), x.data_ptr(), ops.ld(x), mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), ops.ld(g),
                                            ws.data_ptr(), ws.numel(), sums.data_ptr(), n, h, w, s, c, ops.stream()))
-    use = sums if training else zeros(2 * c, x.device)
+    use = dx_sums(sums, training)[0]
     return bn_bwd_apply(g, x, mean, invstd, scale, use, 0, out=g)
 
 
@@ -1167,7 +1150,7 @@ def water_index_backward(ctx, g):
         ws = scratch(lib.runet_water_index_workspace_floats(n, h, w), dev)
         check(lib.runet_water_index_bwd_reduce(*src, g.data_ptr(), ldg, *c1, scale.data_ptr(), shift.data_ptr(), *c2, mean.data_ptr(), invstd.data_ptr(),
                                                ws.data_ptr(), ws.numel(), out_red.data_ptr(), st))
-        use = out_red if training else zeros(2 * WI_MID, dev)
+        use = dx_sums(out_red, training)[0]
         check(lib.runet_water_index_bwd_apply(*src, g.data_ptr(), ldg, *c1, scale.data_ptr(), shift.data_ptr(), *c2, mean.data_ptr(), invstd.data_ptr(),
                                               use.data_ptr(), 0, ws.data_ptr(), ws.numel(), out_app.data_ptr(), st))
         return out_red, out_app
@@ -1369,7 +1352,7 @@ def ms_stem_backward(ctx, de, G, pre="", want_dt=False):
     sums = torch.empty(2 * c, device=dev, dtype=torch.float32)
     ws = scratch(lib.runet_ms_stem_workspace_floats(n, h, w), dev)
     check(lib.runet_ms_stem_bwd_reduce(*src, *wts, *vec, ws.data_ptr(), ws.numel(), sums.data_ptr(), st))
-    use = sums if ctx["training"] else zeros(2 * c, dev)
+    use = dx_sums(sums, ctx["training"])[0]
     dt = torch.empty((n, h, w, c), device=dev, dtype=torch.float32)
     check(lib.runet_ms_stem_bwd_apply(*src, *wts, *vec, use.data_ptr(), 0, dt.data_ptr(), c, st))
     _ms_bn_grads(sums, q, G, pre)
@@ -1734,7 +1717,7 @@ def enet_tail_backward(dout, out, t3, st3, idn=None, st_d=None, mask=None, train
         check(lib.runet_enet_tail_bwd_reduce(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), t3.data_ptr(), ops.ld(t3), p(idn), ldi,
                                              m3.data_ptr(), i3.data_ptr(), p(md), p(idv), p(mask), ws.data_ptr(), ws.numel(), sums.data_ptr(), n, h, w,
                                              c, ops.stream()))
-        use = sums if training else zeros(4 * c, dev)
+        use = dx_sums(sums, training)[0]
         dt3, did = ops.empty_nhwc(n, h, w, c, t3), ops.empty_nhwc(n, h, w, c, t3)
         check(lib.runet_enet_tail_bwd_apply(dout.data_ptr(), ops.ld(dout), out.data_ptr(), ops.ld(out), t3.data_ptr(), ops.ld(t3), p(idn), ldi,
                                             m3.data_ptr(), i3.data_ptr(), s3.data_ptr(), p(md), p(idv), p(sd), p(mask), use.data_ptr(), 0,
@@ -1885,7 +1868,7 @@ def psp_head_backward(dprob, prob, t, scale, shift, mask, w, mean, invstd, saved
         ws = scratch(lib.runet_psp_head_bwd_workspace_floats(n, h, wd, c), dev)
         check(lib.runet_psp_head_bwd_reduce(dz.data_ptr(), t.data_ptr(), ops.ld(t), scale.data_ptr(), shift.data_ptr(), mp, w.data_ptr(), mean.data_ptr(),
                                             invstd.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), n, h, wd, c, st))
-        use = out if training else zeros(2 * c, dev)
+        use = dx_sums(out, training)[0]
         dt = ops.empty_nhwc(n, h, wd, c, t)
         check(lib.runet_psp_head_bwd_apply(dz.data_ptr(), t.data_ptr(), ops.ld(t), mp, w.data_ptr(), dt.data_ptr(), ops.ld(dt), n, h, wd, c, mean.data_ptr(),
                                            invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), use.data_ptr(), 0, st))

@@ -271,41 +271,11 @@ __global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_out_pool_kernel(const fl
     }
 }
 
-// ---- backward 1: dv = dout*(out>0) (written), dq[p] = (sum_c dv*u) * sa*(1-sa)
-__global__ __launch_bounds__(TPB) void rb_bwd1_kernel(const float* __restrict__ dout, int lddo, const float* __restrict__ out,
-                                                      int ldo, const float* __restrict__ t2, int ld, const float* __restrict__ A,
-                                                      const float* __restrict__ B, const float* __restrict__ sa,
-                                                      float* __restrict__ dv, int lddv, float* __restrict__ dq, long P, int HW, int C) {
-    const int sub = threadIdx.x & (LPP - 1);
-    for (long p = (long)blockIdx.x * PPB + (threadIdx.x / LPP); p < P; p += (long)gridDim.x * PPB) {
-        const int n = (int)(p / HW);
-        float s = 0.f;
-        for (int c = sub * 4; c < C; c += LPP * 4) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(dout + p * lddo + c);
-            f32x4 o = {1.f, 1.f, 1.f, 1.f};      // out == NULL: no ReLU behind the attention (standalone SpatialAttention)
-            if (out) o = *reinterpret_cast<const f32x4*>(out + p * ldo + c);
-            const f32x4 t = *reinterpret_cast<const f32x4*>(t2 + p * ld + c);
-            const f32x4 a = *reinterpret_cast<const f32x4*>(A + (long)n * C + c);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(B + (long)n * C + c);
-            f32x4 d;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                d[q] = o[q] > 0.f ? g[q] : 0.f;
-                s += d[q] * (t[q] * a[q] + b[q]);
-            }
-            *reinterpret_cast<f32x4*>(dv + p * lddv + c) = d;
-        }
-        s = grp_sum16(s);
-        if (sub == 0) {
-            const float v = sa[p];
-            dq[p] = s * v * (1.f - v);
-        }
-    }
-}
-
-// rb_bwd1 at the block edges.  POOL: the incoming gradient is g = dout + the pooled gradient's term, rebuilt from (dpool, pidx) by pooled_grad4 -
-// the one addition runet_maxpool2_bwd(accumulate=1) performs on dout, which is left unmodified.  BITS: the ReLU mask comes from rb_out's
-// relu_bits (a byte per 4 channels) instead of a read of `out`; else from `out` (NULL: no ReLU) as in rb_bwd1_kernel.  W: full-resolution width.
+// ---- backward 1: dv = g*(out>0) (written), dq[p] = (sum_c dv*u) * sa*(1-sa)
+// g = dout, and the block edges ride along.  POOL: g = dout + the pooled gradient's term, rebuilt from (dpool, pidx) by pooled_grad4 - the one
+// addition runet_maxpool2_bwd(accumulate=1) performs on dout, which is left unmodified.  BITS: the ReLU mask comes from rb_out's relu_bits (a
+// byte per 4 channels) instead of a read of `out`; else from `out` (NULL: no ReLU behind the attention - standalone SpatialAttention).
+// W: full-resolution width (POOL only).
 template <bool POOL, bool BITS>
 __global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_bwd1_ex_kernel(const float* __restrict__ dout, int lddo, const float* __restrict__ dpool, int ldp,
                                                          const unsigned char* __restrict__ pidx, const float* __restrict__ out, int ldo,
@@ -399,16 +369,23 @@ __global__ __launch_bounds__(256) void sa_conv7_bwd_kernel(const float* __restri
         dw_part[blk * 98 + threadIdx.x] = acc;
     }
 }
-__global__ void reduce_rows_kernel(const float* __restrict__ part, long nrows, int ncols, float* __restrict__ out) {
-    // out[c] = sum_r part[r][c]; one block of 256 threads per column group of 1 (small ncols)
-    const int c = blockIdx.x;
+// The final pass of the partial reductions, by one block of 256 threads: column `col` of part[nrows][ncols] summed over the rows -
+// thread-strided rows in double, wave_sum_d, the four waves' sums left in red[4] behind a barrier; thread 0 combines them in wave order
+// with sum4.  The order is the result's bits.  (rb_bwd2_bn_final runs the same steps for its two adjacent columns in one loop.)
+__device__ __forceinline__ double sum4(const double* red) { return red[0] + red[1] + red[2] + red[3]; }
+__device__ __forceinline__ void col_sum_rows(const float* __restrict__ part, long nrows, int ncols, int col, double* red) {
     double acc = 0;
-    for (long r = threadIdx.x; r < nrows; r += blockDim.x) acc += part[r * ncols + c];
+    for (long r = threadIdx.x; r < nrows; r += blockDim.x) acc += part[r * ncols + col];
     acc = wave_sum_d(acc);
-    __shared__ double red[4];
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) out[c] = (float)(red[0] + red[1] + red[2] + red[3]);
+}
+// out[c] = sum_r part[r][c]; one block per column (small ncols)
+__global__ void reduce_rows_kernel(const float* __restrict__ part, long nrows, int ncols, float* __restrict__ out) {
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    col_sum_rows(part, nrows, ncols, c, red);
+    if (threadIdx.x == 0) out[c] = (float)sum4(red);
 }
 
 // ---- backward 2: per-(n,c) sums of du and du*t2;  du = dv*sa + dsm0/C + dsm1*[c == amax]
@@ -483,6 +460,7 @@ __global__ void rb_bwd2_final(const float* __restrict__ part, int N, int C, int 
 }
 // the shortcut BatchNorm's (dgamma | dbeta) from the partials of rb_bwd2_partial<true>: one block per channel over all (image, chunk) rows
 __global__ void rb_bwd2_bn_final(const float* __restrict__ part, long nrows, int C, float* __restrict__ sums_s) {
+    // its two columns are adjacent in a row: one loop over the part rows for both, each summed in col_sum_rows' order
     const int c = blockIdx.x;
     double a = 0, b = 0;
     for (long rw = threadIdx.x; rw < nrows; rw += blockDim.x) { a += part[(rw * C + c) * 4 + 2]; b += part[(rw * C + c) * 4 + 3]; }
@@ -491,8 +469,8 @@ __global__ void rb_bwd2_bn_final(const float* __restrict__ part, long nrows, int
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        sums_s[C + c] = (float)(red[0][0] + red[0][1] + red[0][2] + red[0][3]);      // dbeta  = sum dv
-        sums_s[c] = (float)(red[1][0] + red[1][1] + red[1][2] + red[1][3]);          // dgamma = sum dv * rhat
+        sums_s[C + c] = (float)sum4(red[0]);      // dbeta  = sum dv
+        sums_s[c] = (float)sum4(red[1]);          // dgamma = sum dv * rhat
     }
 }
 
@@ -793,15 +771,11 @@ __global__ __launch_bounds__(TPB) void ag_bwd2_partial(const float* __restrict__
 // column sums of ag_bwd2_partial<true>'s partials to their three destinations: (dwpsi | dbpsi), W_g.1's (dgamma | dbeta), W_x.1's (dgamma | dbeta)
 __global__ void ag_bwd2_bn_final(const float* __restrict__ part, long nrows, int F, float* __restrict__ dwpsi_db, float* __restrict__ sums_g,
                                  float* __restrict__ sums_x) {
-    const int c = blockIdx.x, NC = 4 * F + 1;
-    double acc = 0;
-    for (long r = threadIdx.x; r < nrows; r += blockDim.x) acc += part[r * NC + c];
-    acc = wave_sum_d(acc);
     __shared__ double red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    const int c = blockIdx.x, NC = 4 * F + 1;
+    col_sum_rows(part, nrows, NC, c, red);
     if (threadIdx.x == 0) {
-        const float v = (float)(red[0] + red[1] + red[2] + red[3]);
+        const float v = (float)sum4(red);
         if (c <= F) dwpsi_db[c] = v;
         else if (c < 2 * F + 1) sums_g[c - (F + 1)] = v;                                  // dgamma of W_g.1
         else if (c < 3 * F + 1) { sums_g[F + c - (2 * F + 1)] = v; sums_x[F + c - (2 * F + 1)] = v; }      // dbeta of both
@@ -873,15 +847,30 @@ inline int px_grid(long P) {
     if (b < 1) b = 1;
     return (int)b;
 }
-inline int stream_chunks(int HW, int C, int& ppc) {
+// The chunk plans of the kernels whose thread owns 4 channels and every rows-th pixel of its chunk.  A plan is the grid, and with it the
+// order of every partial sum, so each is written once.
+// rb_out / rb_bwd3: about 16 K elements of the hw x C image per block; `px` is the count that is divided into chunks - hw itself, or the
+// hw / 4 windows of the pooled form (whose block then covers the same share of the tensor).  -> chunks per image, ppc = px per chunk
+inline int stream_chunks(int hw, int px, int C, int& ppc) {
     const int rows = TPB / (C / 4);
-    long per_img = ((long)HW * C + 16383) / 16384;
-    const long maxc = (HW + rows - 1) / rows;
+    long per_img = ((long)hw * C + 16383) / 16384;
+    const long maxc = (px + rows - 1) / rows;
     if (per_img > maxc) per_img = maxc;
     if (per_img > 4096) per_img = 4096;
     if (per_img < 1) per_img = 1;
-    ppc = (int)((HW + per_img - 1) / per_img);
-    return (int)((HW + ppc - 1) / ppc);
+    ppc = (int)((px + per_img - 1) / per_img);
+    return (int)((px + ppc - 1) / ppc);
+}
+// rb_bwd2: about 32 K elements per block, at most 1024 per image; the workspace holds a row per (image, chunk)
+inline long rb_bwd2_chunks(int hw, int c, int& ppc) {
+    const int rows = TPB / (c / 4);
+    long per_img = ((long)hw * c + 32767) / 32768;
+    if (per_img > 1024) per_img = 1024;
+    const long maxc = (hw + rows - 1) / rows;
+    if (per_img > maxc) per_img = maxc;
+    if (per_img < 1) per_img = 1;
+    ppc = (int)((hw + per_img - 1) / per_img);
+    return per_img;
 }
 inline void chunking(long P, int C, long& chunks, long& ppc) {
     chunks = (P * C + 32767) / 32768;
@@ -889,6 +878,83 @@ inline void chunking(long P, int C, long& chunks, long& ppc) {
     if (chunks < 1) chunks = 1;
     ppc = (P + chunks - 1) / chunks;
     chunks = (P + ppc - 1) / ppc;
+}
+// dynamic LDS of the partial-reduction kernels: ncols floats per pixel row group of the block
+inline size_t part_lds(int c, int ncols) { return (size_t)(TPB / (c / 4)) * ncols * sizeof(float); }
+
+// ---- One host launcher per pass.  The entry points below keep their own RUNET_REQUIRE lines - a refusal's text names the entry point and
+// quotes the condition, both part of the ABI - and hand every plan and launch to these.  NULL optional arguments select the plain kernel.
+void launch_rb_out(const float* t2, int ld, const float* A, const float* B, const float* sa, const float* r, int ldr, const float* rs,
+                   const float* rh, float* out, int ldo, unsigned char* relu_bits, float* pooled, int ldp, unsigned char* pool_idx, int n_img,
+                   int hw, int w, int c, void* stream) {
+    int ppc;
+    const int chunks = stream_chunks(hw, pooled ? hw / 4 : hw, c, ppc);
+    const dim3 grid(chunks, n_img);
+    if (pooled)
+        hipLaunchKernelGGL(relu_bits ? rb_out_pool_kernel<true> : rb_out_pool_kernel<false>, grid, dim3(TPB), 0, (hipStream_t)stream, t2, ld, A, B, sa, r,
+                           ldr, rs, rh, out, ldo, relu_bits, pooled, ldp, pool_idx, hw, w, c, ppc);
+    else if (relu_bits)
+        hipLaunchKernelGGL(rb_out_bits_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, relu_bits, hw, c, ppc);
+    else      // without the bits argument: as one template with it, this kernel read slower than the parent's
+        hipLaunchKernelGGL(rb_out_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, hw, c, ppc);
+}
+
+void launch_rb_bwd1(const float* dout, int lddo, const float* dpool, int ldp, const unsigned char* pool_idx, const float* out, int ldo,
+                    const unsigned char* relu_bits, const float* t2, int ld, const float* A, const float* B, const float* sa, float* dv, int lddv,
+                    float* dq, int n_img, int hw, int w, int c, void* stream) {
+    if (n_img < 1) return;                                  // runet_rb_bwd1 with no pixels: nothing to do, as before
+    int gx = px_grid(hw);                                   // about px_grid(pixels) blocks in all, as (pixel groups, images)
+    if (gx > 8192 / n_img) gx = 8192 / n_img > 0 ? 8192 / n_img : 1;
+    auto kernel = dpool ? (relu_bits ? rb_bwd1_ex_kernel<true, true> : rb_bwd1_ex_kernel<true, false>)
+                        : (relu_bits ? rb_bwd1_ex_kernel<false, true> : rb_bwd1_ex_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(gx, n_img), dim3(TPB), 0, (hipStream_t)stream, dout, lddo, dpool, ldp, pool_idx, out, ldo, relu_bits, t2, ld, A, B, sa,
+                       dv, lddv, dq, hw, w, c);
+}
+
+// BN: 4 values per (image, chunk, channel) instead of 2, and the final pass of the shortcut BatchNorm's sums
+template <bool BN>
+void launch_rb_bwd2(const float* dv, int lddv, const float* t2, int ld, const float* sa, const float* dsm, const int* amax, const float* r, int ldr,
+                    const float* mean_s, const float* invstd_s, int n_img, int hw, int c, float* workspace, float* sdu, float* sdut, float* sums_s,
+                    void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    constexpr int NV = BN ? 4 : 2;
+    int ppc;
+    const long per_img = rb_bwd2_chunks(hw, c, ppc);
+    hipLaunchKernelGGL(rb_bwd2_partial<BN>, dim3((int)per_img, n_img), dim3(TPB), part_lds(c, c * NV), st, dv, lddv, t2, ld, sa, dsm, amax, hw, c, ppc,
+                       workspace, r, ldr, mean_s, invstd_s);
+    hipLaunchKernelGGL(rb_bwd2_final, dim3(cdiv((long)n_img * c, 128)), dim3(128), 0, st, workspace, n_img, c, (int)per_img, NV, sdu, sdut);
+    if constexpr (BN) hipLaunchKernelGGL(rb_bwd2_bn_final, dim3(c), dim3(256), 0, st, workspace, (long)n_img * per_img, c, sums_s);
+}
+
+// sc: the shortcut BatchNorm's backward rides along, dr written over dv; NULL: dv is only read
+void launch_rb_bwd3(float* dv, int lddv, const float* t2, int ld, const float* sa, const float* dsm, const int* amax, const float* ca,
+                    const float* davg, const float* dmx, const int* idx, const float* mean2, const float* invstd2, const float* s2,
+                    const float* sums2, float* dt2, int lddt, long pixels, int hw, int c, long m_total, const RbScArgs* sc, void* stream) {
+    int ppc;
+    const int chunks = stream_chunks(hw, hw, c, ppc);
+    const dim3 grid(chunks, (int)(pixels / hw));
+    const float inv_m = 1.0f / (float)(m_total > 0 ? m_total : pixels);
+    if (sc)
+        hipLaunchKernelGGL(rb_bwd3_sc_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, dv, lddv, t2, ld, sa, dsm, amax, ca, davg, dmx, idx, mean2, invstd2,
+                           s2, sums2, dt2, lddt, hw, c, ppc, inv_m, *sc);
+    else
+        hipLaunchKernelGGL(rb_bwd3_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, dv, lddv, t2, ld, sa, dsm, amax, ca, davg, dmx, idx, mean2, invstd2, s2,
+                           sums2, dt2, lddt, hw, c, ppc, inv_m);
+}
+
+// BN: 4f + 1 columns instead of f + 1, scattered by the final pass to (dwpsi | dbpsi), sums_g and sums_x
+template <bool BN>
+void launch_ag_bwd2(const float* ds, const float* g1, int ldg, const float* x1, int ldx, const float* sg, const float* hg, const float* sx,
+                    const float* hx, const float* wpsi, const float* mean_g, const float* invstd_g, const float* mean_x, const float* invstd_x,
+                    float* dpre, int ldp, float* workspace, float* dwpsi_db, float* sums_g, float* sums_x, long pixels, int f, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int nc = BN ? 4 * f + 1 : f + 1;
+    long chunks, ppc;
+    chunking(pixels, f, chunks, ppc);
+    hipLaunchKernelGGL(ag_bwd2_partial<BN>, dim3((int)chunks), dim3(TPB), part_lds(f, nc), st, ds, g1, ldg, x1, ldx, sg, hg, sx, hx, wpsi, dpre, ldp,
+                       pixels, f, ppc, workspace, mean_g, invstd_g, mean_x, invstd_x);
+    if constexpr (BN) hipLaunchKernelGGL(ag_bwd2_bn_final, dim3(nc), dim3(256), 0, st, workspace, chunks, f, dwpsi_db, sums_g, sums_x);
+    else hipLaunchKernelGGL(reduce_rows_kernel, dim3(nc), dim3(256), 0, st, workspace, chunks, nc, dwpsi_db);
 }
 }  // namespace
 
@@ -926,10 +992,7 @@ extern "C" int runet_rb_out(const float* t2, int ld, const float* A, const float
     RUNET_REQUIRE(t2 && A && B && sa && r && out, "null pointer");
     REQ_C4(c);
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    int ppc;
-    const int chunks = stream_chunks(hw, c, ppc);
-    hipLaunchKernelGGL(rb_out_kernel, dim3(chunks, (int)(pixels / hw)), dim3(TPB), 0, (hipStream_t)stream, t2, ld, A, B, sa, r, ldr, rs, rh, out,
-                       ldo, hw, c, ppc);
+    launch_rb_out(t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, nullptr, nullptr, 0, nullptr, (int)(pixels / hw), hw, 0, c, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -937,8 +1000,8 @@ extern "C" int runet_rb_bwd1(const float* dout, int lddo, const float* out, int 
                              const float* B, const float* sa, float* dv, int lddv, float* dq, long pixels, int hw, int c, void* stream) {
     RUNET_REQUIRE(dout && t2 && A && B && sa && dv && dq, "null pointer");
     REQ_C4(c);
-    hipLaunchKernelGGL(rb_bwd1_kernel, dim3(px_grid(pixels)), dim3(TPB), 0, (hipStream_t)stream, dout, lddo, out, ldo, t2, ld, A, B, sa, dv, lddv,
-                       dq, pixels, hw, c);
+    RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
+    launch_rb_bwd1(dout, lddo, nullptr, 0, nullptr, out, ldo, nullptr, t2, ld, A, B, sa, dv, lddv, dq, (int)(pixels / hw), hw, 0, c, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -951,34 +1014,11 @@ extern "C" int runet_rb_out_ex(const float* t2, int ld, const float* A, const fl
     RUNET_REQUIRE(n_img >= 1 && h >= 1 && w >= 1, "bad shape");
     RUNET_REQUIRE((pooled == nullptr) == (pool_idx == nullptr), "pooled and pool_idx come together");
     RUNET_REQUIRE((long)h * w < (1L << 31), "image too large");
-    hipStream_t st = (hipStream_t)stream;
-    const int hw = h * w;
-    int ppc;
-    if (!pooled) {
-        const int chunks = stream_chunks(hw, c, ppc);
-        if (relu_bits)
-            hipLaunchKernelGGL(rb_out_bits_kernel, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, relu_bits, hw, c, ppc);
-        else
-            hipLaunchKernelGGL(rb_out_kernel, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, hw, c, ppc);
-        RUNET_CHECK_LAUNCH();
+    if (pooled) {
+        RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0, "h and w must be even");
+        RUNET_REQUIRE(ldp >= c && ldp % 4 == 0, "bad pooled stride");
     }
-    RUNET_REQUIRE(h % 2 == 0 && w % 2 == 0, "h and w must be even");
-    RUNET_REQUIRE(ldp >= c && ldp % 4 == 0, "bad pooled stride");
-    // a block's share of the tensor as in the plain form, counted in 2x2 windows
-    const int rows = TPB / (c / 4), hwo = hw / 4;
-    long per_img = ((long)hw * c + 16383) / 16384;
-    const long maxc = (hwo + rows - 1) / rows;
-    if (per_img > maxc) per_img = maxc;
-    if (per_img > 4096) per_img = 4096;
-    if (per_img < 1) per_img = 1;
-    ppc = (int)((hwo + per_img - 1) / per_img);
-    const int chunks = (hwo + ppc - 1) / ppc;
-    if (relu_bits)
-        hipLaunchKernelGGL(rb_out_pool_kernel<true>, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, relu_bits, pooled,
-                           ldp, pool_idx, hw, w, c, ppc);
-    else
-        hipLaunchKernelGGL(rb_out_pool_kernel<false>, dim3(chunks, n_img), dim3(TPB), 0, st, t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, nullptr, pooled,
-                           ldp, pool_idx, hw, w, c, ppc);
+    launch_rb_out(t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, relu_bits, pooled, ldp, pool_idx, n_img, h * w, w, c, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -992,20 +1032,7 @@ extern "C" int runet_rb_bwd1_ex(const float* dout, int lddo, const float* dpool,
     RUNET_REQUIRE(n_img >= 1 && h >= 1 && w >= 1 && (long)h * w < (1L << 31), "bad shape");
     RUNET_REQUIRE((dpool == nullptr) == (pool_idx == nullptr), "dpool and pool_idx come together");
     RUNET_REQUIRE(!dpool || (h % 2 == 0 && w % 2 == 0 && ldp >= c && ldp % 4 == 0), "pooled gradient: h and w must be even, stride a multiple of 4");
-    hipStream_t st = (hipStream_t)stream;
-    const int hw = h * w;
-    const long pixels = (long)n_img * hw;
-    int gx = px_grid(hw);                                   // about px_grid(pixels) blocks in all, as (pixel groups, images)
-    if (gx > 8192 / n_img) gx = 8192 / n_img > 0 ? 8192 / n_img : 1;
-    const dim3 grid(gx, n_img);
-#define RB_BWD1_EX(POOL, BITS)                                                                                                              \
-    hipLaunchKernelGGL((rb_bwd1_ex_kernel<POOL, BITS>), grid, dim3(TPB), 0, st, dout, lddo, dpool, ldp, pool_idx, out, ldo, relu_bits, t2, ld, A, B, \
-                       sa, dv, lddv, dq, hw, w, c)
-    if (dpool && relu_bits) RB_BWD1_EX(true, true);
-    else if (dpool) RB_BWD1_EX(true, false);
-    else if (relu_bits) RB_BWD1_EX(false, true);
-    else hipLaunchKernelGGL(rb_bwd1_kernel, dim3(px_grid(pixels)), dim3(TPB), 0, st, dout, lddo, out, ldo, t2, ld, A, B, sa, dv, lddv, dq, pixels, hw, c);
-#undef RB_BWD1_EX
+    launch_rb_bwd1(dout, lddo, dpool, ldp, pool_idx, out, ldo, relu_bits, t2, ld, A, B, sa, dv, lddv, dq, n_img, h * w, w, c, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1025,31 +1052,10 @@ extern "C" int runet_rb_bwd2(const float* dv, int lddv, const float* t2, int ld,
                              int n_img, int hw, int c, float* workspace, float* sdu, float* sdut, void* stream) {
     RUNET_REQUIRE(dv && t2 && sa && dsm && amax && workspace && sdu && sdut, "null pointer");
     REQ_C4(c);
-    hipStream_t st = (hipStream_t)stream;
-    const int rows = TPB / (c / 4);
-    long per_img = ((long)hw * c + 32767) / 32768;
-    if (per_img > 1024) per_img = 1024;
-    const long maxc = (hw + rows - 1) / rows;
-    if (per_img > maxc) per_img = maxc;
-    if (per_img < 1) per_img = 1;
-    const int ppc = (int)((hw + per_img - 1) / per_img);
-    const size_t lds = (size_t)rows * c * 2 * sizeof(float);
-    hipLaunchKernelGGL(rb_bwd2_partial<false>, dim3((int)per_img, n_img), dim3(TPB), lds, st, dv, lddv, t2, ld, sa, dsm, amax, hw, c, ppc, workspace,
-                       nullptr, 0, nullptr, nullptr);
-    hipLaunchKernelGGL(rb_bwd2_final, dim3(cdiv((long)n_img * c, 128)), dim3(128), 0, st, workspace, n_img, c, (int)per_img, 2, sdu, sdut);
+    launch_rb_bwd2<false>(dv, lddv, t2, ld, sa, dsm, amax, nullptr, 0, nullptr, nullptr, n_img, hw, c, workspace, sdu, sdut, nullptr, stream);
     RUNET_CHECK_LAUNCH();
 }
 
-static long rb_bwd2_chunks(int hw, int c, int& ppc) {
-    const int rows = TPB / (c / 4);
-    long per_img = ((long)hw * c + 32767) / 32768;
-    if (per_img > 1024) per_img = 1024;
-    const long maxc = (hw + rows - 1) / rows;
-    if (per_img > maxc) per_img = maxc;
-    if (per_img < 1) per_img = 1;
-    ppc = (int)((hw + per_img - 1) / per_img);
-    return per_img;
-}
 extern "C" long runet_rb_bwd2_bn_workspace_floats(int n_img, int hw, int c) {
     int ppc;
     return (long)n_img * rb_bwd2_chunks(hw, c, ppc) * c * 4 + 64;
@@ -1062,16 +1068,9 @@ extern "C" int runet_rb_bwd2_bn(const float* dv, int lddv, const float* t2, int 
     RUNET_REQUIRE(dv && t2 && sa && dsm && amax && r && mean_s && invstd_s && workspace && sdu && sdut && sums_s, "null pointer");
     REQ_C4(c);
     RUNET_REQUIRE(ldr >= c && ldr % 4 == 0 && workspace_floats >= runet_rb_bwd2_bn_workspace_floats(n_img, hw, c), "bad stride / workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    int ppc;
-    const long per_img = rb_bwd2_chunks(hw, c, ppc);
-    const int rows = TPB / (c / 4);
-    const size_t lds = (size_t)rows * c * 4 * sizeof(float);
+    const size_t lds = part_lds(c, 4 * c);
     RUNET_REQUIRE(lds <= 64 * 1024, "LDS budget");
-    hipLaunchKernelGGL(rb_bwd2_partial<true>, dim3((int)per_img, n_img), dim3(TPB), lds, st, dv, lddv, t2, ld, sa, dsm, amax, hw, c, ppc, workspace, r, ldr,
-                       mean_s, invstd_s);
-    hipLaunchKernelGGL(rb_bwd2_final, dim3(cdiv((long)n_img * c, 128)), dim3(128), 0, st, workspace, n_img, c, (int)per_img, 4, sdu, sdut);
-    hipLaunchKernelGGL(rb_bwd2_bn_final, dim3(c), dim3(256), 0, st, workspace, (long)n_img * per_img, c, sums_s);
+    launch_rb_bwd2<true>(dv, lddv, t2, ld, sa, dsm, amax, r, ldr, mean_s, invstd_s, n_img, hw, c, workspace, sdu, sdut, sums_s, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1102,10 +1101,8 @@ extern "C" int runet_rb_bwd3(const float* dv, int lddv, const float* t2, int ld,
     RUNET_REQUIRE(dv && t2 && sa && dsm && amax && ca && davg && dmx && idx && mean2 && invstd2 && s2 && sums2 && dt2, "null pointer");
     REQ_C4(c);
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
-    int ppc;
-    const int chunks = stream_chunks(hw, c, ppc);
-    hipLaunchKernelGGL(rb_bwd3_kernel, dim3(chunks, (int)(pixels / hw)), dim3(TPB), 0, (hipStream_t)stream, dv, lddv, t2, ld, sa, dsm, amax, ca, davg,
-                       dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, hw, c, ppc, 1.0f / (float)(m_total > 0 ? m_total : pixels));
+    launch_rb_bwd3(const_cast<float*>(dv), lddv, t2, ld, sa, dsm, amax, ca, davg, dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, pixels, hw, c, m_total,
+                   nullptr, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1120,11 +1117,8 @@ extern "C" int runet_rb_bwd3_sc(float* dv, int lddv, const float* t2, int ld, co
     REQ_C4(c);
     RUNET_REQUIRE(pixels % hw == 0, "pixels must be a whole number of images");
     RUNET_REQUIRE(ldr >= c && ldr % 4 == 0, "bad stride");
-    int ppc;
-    const int chunks = stream_chunks(hw, c, ppc);
     const RbScArgs sc{r, ldr, mean_s, invstd_s, scale_s, sums_s, 1.0f / (float)(m_total_s > 0 ? m_total_s : pixels)};
-    hipLaunchKernelGGL(rb_bwd3_sc_kernel, dim3(chunks, (int)(pixels / hw)), dim3(TPB), 0, (hipStream_t)stream, dv, lddv, t2, ld, sa, dsm, amax, ca, davg,
-                       dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, hw, c, ppc, 1.0f / (float)(m_total > 0 ? m_total : pixels), sc);
+    launch_rb_bwd3(dv, lddv, t2, ld, sa, dsm, amax, ca, davg, dmx, idx, mean2, invstd2, s2, sums2, dt2, lddt, pixels, hw, c, m_total, &sc, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1159,14 +1153,8 @@ extern "C" int runet_ag_bwd2(const float* ds, const float* g1, int ldg, const fl
                              float* dwpsi_db, long pixels, int f, void* stream) {
     RUNET_REQUIRE(ds && g1 && x1 && sg && hg && sx && hx && wpsi && dpre && workspace && dwpsi_db, "null pointer");
     REQ_C4(f);
-    hipStream_t st = (hipStream_t)stream;
-    long chunks, ppc;
-    chunking(pixels, f, chunks, ppc);
-    const int rows = TPB / (f / 4);
-    const size_t lds = (size_t)rows * (f + 1) * sizeof(float);
-    hipLaunchKernelGGL(ag_bwd2_partial<false>, dim3((int)chunks), dim3(TPB), lds, st, ds, g1, ldg, x1, ldx, sg, hg, sx, hx, wpsi, dpre, ldp, pixels, f, ppc,
-                       workspace, nullptr, nullptr, nullptr, nullptr);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(f + 1), dim3(256), 0, st, workspace, chunks, f + 1, dwpsi_db);
+    launch_ag_bwd2<false>(ds, g1, ldg, x1, ldx, sg, hg, sx, hx, wpsi, nullptr, nullptr, nullptr, nullptr, dpre, ldp, workspace, dwpsi_db, nullptr, nullptr,
+                          pixels, f, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1186,15 +1174,10 @@ extern "C" int runet_ag_bwd2_bn(const float* ds, const float* g1, int ldg, const
                   sums_g && sums_x, "null pointer");
     REQ_C4(f);
     RUNET_REQUIRE(workspace_floats >= runet_ag_bwd2_bn_workspace_floats(pixels, f), "workspace too small (runet_ag_bwd2_bn_workspace_floats)");
-    hipStream_t st = (hipStream_t)stream;
-    long chunks, ppc;
-    chunking(pixels, f, chunks, ppc);
-    const int rows = TPB / (f / 4);
-    const size_t lds = (size_t)rows * (4 * f + 1) * sizeof(float);
+    const size_t lds = part_lds(f, 4 * f + 1);
     RUNET_REQUIRE(lds <= 64 * 1024, "LDS budget");
-    hipLaunchKernelGGL(ag_bwd2_partial<true>, dim3((int)chunks), dim3(TPB), lds, st, ds, g1, ldg, x1, ldx, sg, hg, sx, hx, wpsi, dpre, ldp, pixels, f, ppc,
-                       workspace, mean_g, invstd_g, mean_x, invstd_x);
-    hipLaunchKernelGGL(ag_bwd2_bn_final, dim3(4 * f + 1), dim3(256), 0, st, workspace, chunks, f, dwpsi_db, sums_g, sums_x);
+    launch_ag_bwd2<true>(ds, g1, ldg, x1, ldx, sg, hg, sx, hx, wpsi, mean_g, invstd_g, mean_x, invstd_x, dpre, ldp, workspace, dwpsi_db, sums_g, sums_x,
+                         pixels, f, stream);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1213,9 +1196,7 @@ extern "C" int runet_outc_bwd(const float* dprob, const float* prob, const float
     hipStream_t st = (hipStream_t)stream;
     long chunks, ppc;
     chunking(pixels, c, chunks, ppc);
-    const int rows = TPB / (c / 4);
-    const size_t lds = (size_t)rows * (c + 1) * sizeof(float);
-    hipLaunchKernelGGL(outc_bwd_partial, dim3((int)chunks), dim3(TPB), lds, st, dprob, prob, x, ld, w, dx, lddx, pixels, c, ppc, workspace);
+    hipLaunchKernelGGL(outc_bwd_partial, dim3((int)chunks), dim3(TPB), part_lds(c, c + 1), st, dprob, prob, x, ld, w, dx, lddx, pixels, c, ppc, workspace);
     hipLaunchKernelGGL(reduce_rows_kernel, dim3(c + 1), dim3(256), 0, st, workspace, chunks, c + 1, dw_db);
     RUNET_CHECK_LAUNCH();
 }

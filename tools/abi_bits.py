@@ -1,7 +1,9 @@
 """Bit fingerprints of the entry points whose results rest on a fixed summation order: the two-stage reductions (chunk partials, then the
-ordered final pass sum_parts of csrc/runet_common.h), the gather adjoints of the bilinear resizes, and every entry point of csrc/norm_act.hip
-(BatchNorm statistics, apply and backward: Chan combines in chunk order, first-occurrence max / min, explicit FMAs).  Every case fills seeded inputs, calls
-the entry point once through the package's binding and prints one SHA-256 per output tensor.  Two builds of the library compute the same
+ordered final pass sum_parts of csrc/runet_common.h), the gather adjoints of the bilinear resizes, every entry point of csrc/norm_act.hip
+(BatchNorm statistics, apply and backward: Chan combines in chunk order, first-occurrence max / min, explicit FMAs) and every entry point of
+csrc/attention.hip (the residual-block tail and the attention gate: chunk plans, 16-lane pixel sums, the ordered final passes; ATT_SHAPES
+below).  Every case fills seeded inputs, calls
+the entry point once through the package's binding and prints one SHA-256 per output tensor (per case for attention.hip).  Two builds of the library compute the same
 bits exactly when their printouts are equal line for line; RUNET_HIP_LIB selects the build (see _lib.py), one fresh process per build:
 
   RUNET_HIP_LIB=/path/to/other/librunet_hip.so python tools/abi_bits.py > a.txt
@@ -299,6 +301,147 @@ NORM_ACT_CASES = [
 ]
 
 
+# ---- csrc/attention.hip.  (n, h, w, c): more than one chunk per image and partial 16 x 16 tiles | idle threads in a row group (12 channel
+# groups) | one thread row, image smaller than the 7 x 7 window | C < 64 in the 16-lane kernels, Cr = 1 | four thread rows.  All sides even.
+ATT_SHAPES = [(2, 20, 36, 64), (2, 8, 8, 48), (1, 2, 2, 1024), (3, 6, 10, 16), (1, 4, 4, 256)]
+
+
+def ri(hi, *shape, dtype=torch.int32):
+    return torch.randint(0, hi, shape, generator=G, dtype=dtype).to(DEV)
+
+
+def tail_inputs(n, h, w, c):
+    """t2, A, B, sa of the residual-block tail"""
+    return rnd(n, h, w, c), rnd(n, c), rnd(n, c), torch.sigmoid(rnd(n, h, w))
+
+
+def att_rb_out(n, h, w, c, bits, pool, affine, ex=1):
+    t2, A, B, sa = tail_inputs(n, h, w, c)
+    r, rs, rh, o = rnd(n, h, w, c), rnd(c), rnd(c), out(n, h, w, c)
+    rb = torch.zeros((n * h * w, c // 4), dtype=torch.uint8, device=DEV)
+    pooled, pidx = out(n, h // 2, w // 2, c), torch.zeros((n, h // 2, w // 2, c), dtype=torch.uint8, device=DEV)
+    head = (p(t2), c, p(A), p(B), p(sa), p(r), c, p(rs) if affine else None, p(rh) if affine else None, p(o), c)
+    if not ex:
+        check(lib.runet_rb_out(*head, n * h * w, h * w, c, ops.stream()))
+        return [o]
+    check(lib.runet_rb_out_ex(*head, p(rb) if bits else None, p(pooled) if pool else None, c if pool else 0, p(pidx) if pool else None, n, h, w, c,
+                              ops.stream()))
+    return [o] + ([rb] if bits else []) + ([pooled, pidx] if pool else [])
+
+
+def att_rb_bwd1(n, h, w, c, form, pool=0, bits=0):
+    """form: "plain" runet_rb_bwd1 with `out`, "noact" the same with out NULL, "ex" runet_rb_bwd1_ex in its four template cases"""
+    t2, A, B, sa = tail_inputs(n, h, w, c)
+    dout, o, dv, dq = rnd(n, h, w, c), torch.relu(rnd(n, h, w, c)), out(n, h, w, c), out(n, h, w)
+    dpool, pidx, rb = rnd(n, h // 2, w // 2, c), ri(4, n, h // 2, w // 2, c, dtype=torch.uint8), ri(16, n * h * w, c // 4, dtype=torch.uint8)
+    tail = (p(t2), c, p(A), p(B), p(sa), p(dv), c, p(dq))
+    if form == "ex":
+        check(lib.runet_rb_bwd1_ex(p(dout), c, p(dpool) if pool else None, c if pool else 0, p(pidx) if pool else None, p(o), c, p(rb) if bits else None,
+                                   *tail, n, h, w, c, ops.stream()))
+    else:
+        check(lib.runet_rb_bwd1(p(dout), c, p(o) if form == "plain" else None, c, *tail, n * h * w, h * w, c, ops.stream()))
+    return [dv, dq]
+
+
+def att_rb_bwd2(n, h, w, c, bn):
+    dv, t2, sa, dsm, amax = rnd(n, h, w, c), rnd(n, h, w, c), torch.sigmoid(rnd(n, h, w)), rnd(n * h * w, 2), ri(c, n * h * w)
+    sdu, sdut, sums_s, k = out(n, c), out(n, c), out(2 * c), ws(lib.runet_rb_bwd2_bn_workspace_floats(n, h * w, c))
+    head = (p(dv), c, p(t2), c, p(sa), p(dsm), p(amax))
+    if not bn:
+        check(lib.runet_rb_bwd2(*head, n, h * w, c, p(k), p(sdu), p(sdut), ops.stream()))
+        return [sdu, sdut]
+    r, mean_s, invstd_s = rnd(n, h, w, c), rnd(c), pos(c)
+    check(lib.runet_rb_bwd2_bn(*head, p(r), c, p(mean_s), p(invstd_s), n, h * w, c, p(k), k.numel(), p(sdu), p(sdut), p(sums_s), ops.stream()))
+    return [sdu, sdut, sums_s]
+
+
+def att_rb_bwd3(n, h, w, c, sc, m_total):
+    dv, t2, sa, dsm, amax = rnd(n, h, w, c), rnd(n, h, w, c), torch.sigmoid(rnd(n, h, w)), rnd(n * h * w, 2), ri(c, n * h * w)
+    ca, davg, dmx, idx = rnd(n, c), rnd(n, c), rnd(n, c), ri(h * w, n, c)
+    mean2, invstd2, s2, sums2, dt2 = rnd(c), pos(c), rnd(c), rnd(2 * c), out(n, h, w, c)
+    head = (p(dv), c, p(t2), c, p(sa), p(dsm), p(amax), p(ca), p(davg), p(dmx), p(idx), p(mean2), p(invstd2), p(s2), p(sums2), p(dt2), c)
+    if not sc:
+        check(lib.runet_rb_bwd3(*head, n * h * w, h * w, c, m_total, ops.stream()))
+        return [dt2]
+    r, mean_s, invstd_s, scale_s, sums_s = rnd(n, h, w, c), rnd(c), pos(c), rnd(c), rnd(2 * c)
+    check(lib.runet_rb_bwd3_sc(*head, p(r), c, p(mean_s), p(invstd_s), p(scale_s), p(sums_s), m_total, n * h * w, h * w, c, m_total, ops.stream()))
+    return [dt2, dv]
+
+
+def att_sa(n, h, w, c):
+    """runet_sa_reduce, runet_sa_conv7 on its map, runet_sa_conv7_bwd on both"""
+    t2, A, B, _ = tail_inputs(n, h, w, c)
+    P = n * h * w
+    smap, amax, sa, wp = out(P, 2), torch.zeros(P, dtype=torch.int32, device=DEV), out(P), rnd(98)
+    check(lib.runet_sa_reduce(p(t2), c, p(A), p(B), P, h * w, c, p(smap), p(amax), ops.stream()))
+    check(lib.runet_sa_conv7(p(smap), p(wp), p(sa), n, h, w, ops.stream()))
+    dq, dsm, dwp, k = rnd(P), out(P, 2), out(98), ws(lib.runet_sa_conv7_bwd_workspace_floats(n, h, w))
+    check(lib.runet_sa_conv7_bwd(p(smap), p(dq), p(wp), p(dsm), p(dwp), p(k), n, h, w, ops.stream()))
+    return [smap, amax, sa, dsm, dwp]
+
+
+def att_ca(n, c, cr):
+    """runet_ca_coeff, then runet_ca_bwd on what it saved"""
+    mean_nc, max_nc, min_nc, imax, imin = rnd(n, c), rnd(n, c), rnd(n, c), ri(64, n, c), ri(64, n, c)
+    s2, h2, w0p, w2p = rnd(c), rnd(c), rnd(c, cr), rnd(cr, c)
+    A, B, ca, avg, mx, tval = (out(n, c) for _ in range(6))
+    idx = torch.zeros((n, c), dtype=torch.int32, device=DEV)
+    check(lib.runet_ca_coeff(p(mean_nc), p(max_nc), p(min_nc), p(imax), p(imin), p(s2), p(h2), p(w0p), p(w2p), n, c, cr, p(A), p(B), p(ca), p(avg),
+                             p(mx), p(idx), p(tval), ops.stream()))
+    sdu, sdut, mean2, invstd2 = rnd(n, c), rnd(n, c), rnd(c), pos(c)
+    davg, dmx, sums2, dw0p, dw2p, k = out(n, c), out(n, c), out(2 * c), out(c, cr), out(cr, c), ws(lib.runet_ca_bwd_workspace_floats(n, c, cr))
+    check(lib.runet_ca_bwd(p(sdu), p(sdut), p(s2), p(h2), p(ca), p(avg), p(mx), p(w0p), p(w2p), p(mean_nc), p(tval), p(mean2), p(invstd2), n, c, cr,
+                           p(k), p(davg), p(dmx), p(sums2), p(dw0p), p(dw2p), ops.stream()))
+    return [A, B, ca, avg, mx, idx, tval, davg, dmx, sums2, dw0p, dw2p]
+
+
+def att_gate(P, f, ld):
+    """runet_ag_psi, runet_ag_out, runet_ag_bwd1, runet_ag_bwd2 and runet_ag_bwd2_bn over P pixels of f channels with pixel stride ld"""
+    g1, x1, s = rnd(P, ld), rnd(P, ld), out(P)
+    sg, hg, sx, hx, wpsi, bpsi, sp, hp = rnd(f), rnd(f), rnd(f), rnd(f), rnd(f), rnd(1), rnd(1), rnd(1)
+    st = ops.stream()
+    check(lib.runet_ag_psi(p(g1), ld, p(x1), ld, p(sg), p(hg), p(sx), p(hx), p(wpsi), p(bpsi), p(s), P, f, st))
+    att, datt, dxs, dsbn = out(P, ld), rnd(P, ld), out(P, ld), out(P)
+    check(lib.runet_ag_out(p(x1), ld, p(s), p(sp), p(hp), p(att), ld, P, f, st))
+    check(lib.runet_ag_bwd1(p(datt), ld, p(x1), ld, p(s), p(sp), p(hp), p(dxs), ld, p(dsbn), P, f, st))
+    ds, mean_g, invstd_g, mean_x, invstd_x = rnd(P), rnd(f), pos(f), rnd(f), pos(f)
+    res = [s, att, dxs, dsbn]
+    for bn in (0, 1):
+        dpre, dw, sums_g, sums_x, k = out(P, ld), out(f + 1), out(2 * f), out(2 * f), ws(lib.runet_ag_bwd2_bn_workspace_floats(P, f))
+        head = (p(ds), p(g1), ld, p(x1), ld, p(sg), p(hg), p(sx), p(hx), p(wpsi))
+        if bn:
+            check(lib.runet_ag_bwd2_bn(*head, p(mean_g), p(invstd_g), p(mean_x), p(invstd_x), p(dpre), ld, p(k), k.numel(), p(dw), p(sums_g), p(sums_x),
+                                       P, f, st))
+        else:
+            check(lib.runet_ag_bwd2(*head, p(dpre), ld, p(k), p(dw), P, f, st))
+        res += [dpre, dw] + ([sums_g, sums_x] if bn else [])
+    return res
+
+
+def att_outc(P, c, opt):
+    """runet_outc_fwd with the logit wanted or not, runet_outc_bwd on the probability's or (prob NULL) the logit's gradient"""
+    x, wt, b, logit, prob = rnd(P, c), rnd(c), rnd(1), out(P), out(P)
+    check(lib.runet_outc_fwd(p(x), c, p(wt), p(b), p(logit) if opt else None, p(prob), P, c, ops.stream()))
+    dprob, dx, dw_db, k = rnd(P), out(P, c), out(c + 1), ws(lib.runet_reduce_workspace_floats(1, P, c))
+    check(lib.runet_outc_bwd(p(dprob), p(prob) if opt else None, p(x), c, p(wt), p(dx), c, p(k), p(dw_db), P, c, ops.stream()))
+    return [logit, prob, dx, dw_db]
+
+
+ATTENTION_CASES = [
+    *[(att_rb_out, (*s, bits, pool, aff)) for s in ATT_SHAPES for bits in (0, 1) for pool in (0, 1) for aff in (0, 1)],
+    *[(att_rb_out, (*s, 0, 0, 1, 0)) for s in ATT_SHAPES],
+    *[(att_rb_bwd1, (*s, form)) for s in ATT_SHAPES for form in ("plain", "noact")],
+    *[(att_rb_bwd1, (*s, "ex", pool, bits)) for s in ATT_SHAPES for pool in (0, 1) for bits in (0, 1)],
+    *[(att_rb_bwd2, (*s, bn)) for s in ATT_SHAPES for bn in (0, 1)],
+    *[(att_rb_bwd3, (*s, sc, m)) for s in ATT_SHAPES for sc in (0, 1) for m in (0, 3 * s[0] * s[1] * s[2])],
+    *[(att_sa, s) for s in ATT_SHAPES],
+    *[(att_ca, (s[0], s[3], cr)) for s in ATT_SHAPES for cr in (1, 3, 64) if cr <= s[3]],
+    # f = 64 over the 2 x 20 x 36 pixels of strided views (pixel stride 2 f); f = 256 over 8 pixels
+    (att_gate, (128, 8, 8)), (att_gate, (180, 12, 12)), (att_gate, (2 * 20 * 36, 64, 128)), (att_gate, (8, 256, 256)),
+    *[(att_outc, (s[0] * s[1] * s[2], s[3], opt)) for s in ATT_SHAPES for opt in (1, 0)],
+]
+
+
 # (entry point, arguments).  Partial rows each reducing case yields, from its file's chunk rule, against the 16 (hrnet, multiscale,
 # water_index) or 8 (fastscnn, dwsep, dwconv) part-lanes of the final pass:
 CASES = [
@@ -322,6 +465,7 @@ CASES = [
     (bilinear_nhwc_bwd, (2, 5, 7, 11, 13, 8)), (bilinear_nhwc_bwd, (1, 1, 3, 2, 9, 4)), (bilinear_nhwc_bwd, (2, 9, 11, 5, 7, 12)),
     *NORM_ACT_CASES,
     *[(wino_conv_x3, (*s, st)) for s in WINO_X3_SHAPES for st in (0, 1)],
+    *ATTENTION_CASES,
 ]
 
 
@@ -329,6 +473,12 @@ def main():
     for fn, args in CASES:
         outs = fn(*args)
         torch.cuda.synchronize()
+        if fn.__name__.startswith("att_"):      # up to twelve outputs per case: one fingerprint over all of them, in order
+            h = hashlib.sha256()
+            for t in outs:
+                h.update(t.cpu().numpy().tobytes())
+            print(f"{fn.__name__}{args} {len(outs)} outputs {h.hexdigest()}")
+            continue
         for i, t in enumerate(outs):
             print(f"{fn.__name__}{args} out{i} {tuple(t.shape)} {hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()}")
 
