@@ -8,6 +8,7 @@ Reference pipeline, one image at a time (line numbers of predict_coastline.py):
   4. :595-602        MORPH_ELLIPSE k x k, cv2.dilate, dilated - mask                          runet_dilate_diff_u8 (+ the two pixel counts)
   5. :605-616        cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), > 10 points,       runet_contours_count / runet_contours_trace (device
                      approxPolyDP(0.002 * arcLength)                                          masks; host: trace_external_contours), host approx_poly_dp
+                                                                                              (rule "float64") or runet_contours_simplify (rule "exact")
   6. :404-413, :620-652  result dict, two PNG masks (* 255), <base>_coastlines.json           save_extraction_result
 
 A probability model (PROB_MODELS) differs in steps 1-2 only, the two kernels on either side of the network: its tiles are planar NCHW
@@ -16,7 +17,8 @@ comne.py:622, Extended_Baseline_Comparison.py:758, :920), taken by runet_thresho
 water map (predict_scene(return_prob=True)).  Which sizes a model takes is asked of the model (`_check_input`), not tabulated here.
 
 Between the upload of the uint8 image and the single download of (water mask, coastline mask, counts, packed contours) nothing returns to
-the host but the two size words the contour tracing needs to allocate (its state count, then its contour and vertex counts).
+the host but the two size words the contour tracing needs to allocate (its state count, then its contour and vertex counts) and, under
+simplify_rule="exact", the simplifier's head (its kept-vertex count).
 `predict_scene` is the addition for scenes larger than one network input: the scene is cut into overlapping tiles at its own resolution and
 every output pixel is taken from exactly one tile's core (tile_plan), so there is no blending and the result is bit-deterministic.
 
@@ -48,6 +50,12 @@ MAX_DILATION = 31
 # RUNET_NO_DEVICE_CONTOURS=1: masks that live on the device are downloaded and traced by the host loop (trace_external_contours) as before.
 # Consulted at every call; the results are identical either way.
 DEVICE_CONTOURS = os.environ.get("RUNET_NO_DEVICE_CONTOURS", "0") != "1"
+# RUNET_NO_DEVICE_SIMPLIFY=1: under rule "exact" the device-traced contours are downloaded whole and simplified by the host restatement
+# (approx_poly_dp_exact) instead of runet_contours_simplify.  Consulted at every call; the lists are identical either way.
+DEVICE_SIMPLIFY = os.environ.get("RUNET_NO_DEVICE_SIMPLIFY", "0") != "1"
+SIMPLIFY_RULES = ("float64", "exact")
+EXACT_COORD_MAX = 46340                                  # rule "exact": 2 * 46340^2 < 2^32, so every distance numerator stays below 2^64
+_SQRT2 = float.fromhex("0x1.6a09e667f3bcdp+0")
 
 
 # ------------------------------------------------------------------------------------------------ host-side plans
@@ -245,9 +253,10 @@ def trace_external_contours(mask):
 
 
 # ------------------------------------------------------------------------------------------------ contours (device)
-def _trace_packed(mask, min_points=0):
+def _trace_packed(mask, min_points=0, with_sizes=False):
     """mask: device uint8 [h, w] -> device int32 tensor {n, total, offsets [n + 1], points [total][2]} (csrc/contours.hip), or None for a
-    mask without a set pixel.  Two small downloads: the state count, then (n, total) to cut the packed result to its length."""
+    mask without a set pixel.  Two small downloads: the state count, then (n, total) to cut the packed result to its length.
+    with_sizes: -> (packed, (n, total)), so that a caller that goes on working on the device need not read them again."""
     if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.ndim != 2 or not mask.is_cuda:
         raise ValueError("expected a 2-D uint8 device tensor")
     if min_points < 0:
@@ -255,7 +264,7 @@ def _trace_packed(mask, min_points=0):
     mask = mask.contiguous()
     h, w = mask.shape
     if h == 0 or w == 0:
-        return None
+        return (None, (0, 0)) if with_sizes else None
     nbytes = lib.runet_contours_workspace_bytes(h, w)
     if nbytes < 0:
         raise ValueError(f"a {h} x {w} mask is too large for the device tracer (h * w must stay below 2^31)")
@@ -264,14 +273,15 @@ def _trace_packed(mask, min_points=0):
     check(lib.runet_contours_count(mask.data_ptr(), h, w, ws.data_ptr(), nbytes, count.data_ptr(), ops.stream()))
     n_states = int(count.cpu()[0])                                                     # download 1
     if n_states == 0:
-        return None
+        return (None, (0, 0)) if with_sizes else None
     sbytes = lib.runet_contours_state_workspace_bytes(n_states)
     if sbytes < 0:
         raise ValueError(f"{n_states} border states do not fit int32")
     sws = torch.empty(sbytes, device=mask.device, dtype=torch.uint8)
     check(lib.runet_contours_trace(h, w, ws.data_ptr(), nbytes, n_states, int(min_points), sws.data_ptr(), sbytes, ops.stream()))
     n, total = (int(v) for v in sws[:8].view(torch.int32).cpu())                       # download 2
-    return sws[:4 * (3 + n + 2 * total)].view(torch.int32)
+    packed = sws[:4 * (3 + n + 2 * total)].view(torch.int32)
+    return (packed, (n, total)) if with_sizes else packed
 
 
 def _unpack_contours(packed):
@@ -348,15 +358,160 @@ def _simplify(contours, min_points, eps_factor):
     return [approx_poly_dp(c, eps_factor * arc_length(c, True), True).tolist() for c in contours if len(c) > min_points]
 
 
-def coastlines_from_mask(coastline_mask, min_points=10, eps_factor=0.002):
+# ------------------------------------------------------------------------------------------------ the exact rule (include/runet_hip.h)
+def _check_rule(rule):
+    if rule not in SIMPLIFY_RULES:
+        raise ValueError(f"rule must be one of {SIMPLIFY_RULES} (got {rule!r})")
+
+
+def _check_eps_factor(eps_factor):
+    eps_factor = float(eps_factor)
+    if not (0.0 <= eps_factor < float("inf")):
+        raise ValueError("eps_factor must be finite and not negative")
+    return eps_factor
+
+
+def _exact_numerator(a, b, p):
+    """-> (N, den): den * the squared distance of p to the clipped segment a-b, in Python ints; 1 stands in for den == 0"""
+    abx, aby, apx, apy = b[0] - a[0], b[1] - a[1], p[0] - a[0], p[1] - a[1]
+    den, dot, ap2 = abx * abx + aby * aby, apx * abx + apy * aby, apx * apx + apy * apy
+    if den == 0:
+        return ap2, 1
+    if dot <= 0:
+        return ap2 * den, den
+    if dot >= den:
+        return ((p[0] - b[0]) ** 2 + (p[1] - b[1]) ** 2) * den, den
+    return (apx * aby - apy * abx) ** 2, den
+
+
+def approx_poly_dp_exact(points, eps_factor):
+    """Douglas-Peucker on one closed integer contour by the exact rule stated in include/runet_hip.h (the host restatement of
+    runet_contours_simplify: Python ints, and float64 operations that are each rounded once), tolerance eps_factor * arc length.
+    -> int32 [k, 2].  ValueError on a bad input: a coordinate outside [0, 46340] or an edge that is not horizontal, vertical or 45 degrees."""
+    eps_factor = _check_eps_factor(eps_factor)
+    arr = np.asarray(points)
+    if arr.size and not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("the exact rule takes integer vertices")
+    p = [(int(x), int(y)) for x, y in arr.reshape(-1, 2)]
+    n = len(p)
+    if n == 0:
+        return np.zeros((0, 2), dtype=np.int32)
+    axis = diag = 0
+    for i, (x, y) in enumerate(p):
+        if not (0 <= x <= EXACT_COORD_MAX and 0 <= y <= EXACT_COORD_MAX):
+            raise ValueError(f"vertex {i} = ({x}, {y}) is outside [0, {EXACT_COORD_MAX}]")
+    for i, (x, y) in enumerate(p):
+        xn, yn = p[(i + 1) % n]
+        dx, dy = abs(xn - x), abs(yn - y)
+        if dx == 0 or dy == 0:
+            axis += dx + dy
+        elif dx == dy:
+            diag += dx
+        else:
+            raise ValueError(f"edge {i} = ({xn - x}, {yn - y}) is not a horizontal, vertical or 45 degree run")
+    length = np.float64(axis) + np.float64(diag) * np.float64(_SQRT2)
+    eps = np.float64(eps_factor) * length
+    thr = eps * eps
+    d2 = [(x - p[0][0]) ** 2 + (y - p[0][1]) ** 2 for x, y in p]
+    far = d2.index(max(d2))
+    if far == 0:
+        return np.array(p[:1], dtype=np.int32)
+    q = p + p[:1]
+    keep = {0, far}
+    stack = [(0, far), (far, n)]
+    while stack:
+        a, b = stack.pop()
+        if b - a < 2:
+            continue
+        best, k, den = -1, -1, 1
+        for i in range(a + 1, b):
+            num, den = _exact_numerator(q[a], q[b], q[i])
+            if num > best:
+                best, k = num, i
+        if np.float64(float(best)) > thr * np.float64(float(den)):
+            keep.add(k)
+            stack += [(a, k), (k, b)]
+    return np.array([p[i] for i in sorted(keep)], dtype=np.int32)
+
+
+def _simplify_exact(contours, min_points, eps_factor):
+    return [approx_poly_dp_exact(c, eps_factor).tolist() for c in contours if len(c) > min_points]
+
+
+def simplify_packed_device(packed, eps_factor=0.002, lds_max_vertices=None, sizes=None, with_head=False):
+    """packed: the tracer's device int32 tensor {n, total, offsets [n + 1], points [total][2]} -> the same format with every contour
+    simplified by the exact rule on the device (runet_contours_simplify).  sizes = (n, total) where the caller has read them already;
+    otherwise they are one small download.  One more small download follows, the head {n, kept vertices, bad inputs, largest round count},
+    to cut the result to its length.  lds_max_vertices: the contour length up to which the per-vertex state stays in LDS (None: the
+    library's default), same bytes for every value.  ValueError when an input is bad (see approx_poly_dp_exact); with_head: -> (result, head)."""
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.int32 or packed.ndim != 1 or not packed.is_cuda:
+        raise ValueError("expected a 1-D int32 device tensor")
+    eps_factor = _check_eps_factor(eps_factor)
+    packed = packed.contiguous()
+    if sizes is None:
+        if packed.numel() < 3:
+            raise ValueError("a packed contour set has at least three words")
+        sizes = packed[:2].cpu().tolist()
+    n, total = int(sizes[0]), int(sizes[1])
+    nbytes = lib.runet_contours_simplify_workspace_bytes(n, total)
+    if nbytes < 0 or packed.numel() < 3 + n + 2 * total:
+        raise ValueError(f"n = {n}, total = {total} do not describe a packed contour set of {packed.numel()} words")
+    ws = torch.empty(nbytes, device=packed.device, dtype=torch.uint8)
+    lds = -1 if lds_max_vertices is None else max(0, min(int(lds_max_vertices), 2 ** 31 - 1))
+    check(lib.runet_contours_simplify(packed.data_ptr(), n, total, eps_factor, lds, ws.data_ptr(), nbytes, ops.stream()))
+    head = [int(v) for v in ws[:16].view(torch.int32).cpu()]
+    if head[2]:
+        raise ValueError(f"{head[2]} bad inputs: the exact rule takes coordinates in [0, {EXACT_COORD_MAX}] and horizontal, vertical or "
+                         "45 degree edges, in a packed set whose offsets rise from 0 to its vertex count")
+    at = lib.runet_contours_simplify_result_offset()
+    out = ws[at:at + 4 * (3 + n + 2 * head[1])].view(torch.int32)
+    return (out, head) if with_head else out
+
+
+def _check_exact_shape(h, w):
+    if max(h, w) > EXACT_COORD_MAX + 1:
+        raise ValueError(f"rule 'exact' takes masks of at most {EXACT_COORD_MAX + 1} pixels a side (coordinates up to {EXACT_COORD_MAX}); "
+                         f"got {h} x {w}")
+
+
+def _coastlines_packed(coast, min_points, eps_factor, rule):
+    """device mask -> (device packed contours or None, simplified): traced on the device and, under rule "exact" with DEVICE_SIMPLIFY on,
+    simplified there too, so that only the kept vertices are downloaded"""
+    if rule == "exact" and DEVICE_SIMPLIFY:
+        packed, sizes = _trace_packed(coast, min_points, with_sizes=True)
+        return (None if packed is None else simplify_packed_device(packed, eps_factor, sizes=sizes)), True
+    return _trace_packed(coast, min_points), False
+
+
+def _finish_contours(contours, simplified, min_points, eps_factor, rule):
+    """downloaded contours -> coastlines: whatever of the rule has not run on the device"""
+    if simplified:
+        return [c.tolist() for c in contours]
+    return (_simplify_exact if rule == "exact" else _simplify)(contours, min_points, eps_factor)
+
+
+def coastlines_from_mask(coastline_mask, min_points=10, eps_factor=0.002, rule="float64"):
     """predict_coastline.py:605-616 -> list of [[x, y], ...].  A device tensor is traced and length-filtered on the device and its packed
-    vertices downloaded once (DEVICE_CONTOURS off: the mask is downloaded and traced on the host); arc length and Douglas-Peucker stay on
-    the host in float64 either way, so the lists are the same."""
+    vertices downloaded once (DEVICE_CONTOURS off: the mask is downloaded and traced on the host).
+    rule "float64" (the default): arc length and Douglas-Peucker on the host in float64 (approx_poly_dp) either way, so the lists are the same.
+    rule "exact": the project's exact integer rule (include/runet_hip.h), which parts from the float64 rule at ties and near-ties only.  A
+    device mask is traced AND simplified on the device and only the kept vertices are downloaded (DEVICE_SIMPLIFY off: the traced contours
+    are downloaded and simplified by approx_poly_dp_exact); a host mask goes through the host tracer and approx_poly_dp_exact.  The lists
+    are identical whichever way.  Masks of more than 46341 pixels a side are refused under "exact"."""
+    _check_rule(rule)
+    if rule == "exact":
+        if getattr(coastline_mask, "ndim", 2) == 2:
+            _check_exact_shape(*coastline_mask.shape)
+        _check_eps_factor(eps_factor)
     if isinstance(coastline_mask, torch.Tensor):
         if coastline_mask.is_cuda and DEVICE_CONTOURS:
-            return _simplify(trace_external_contours_device(coastline_mask, min_points), min_points, eps_factor)
+            if rule == "float64":
+                return _simplify(trace_external_contours_device(coastline_mask, min_points), min_points, eps_factor)
+            packed, simplified = _coastlines_packed(coastline_mask, min_points, eps_factor, rule)
+            contours = [] if packed is None else _unpack_contours(packed.cpu().numpy())
+            return _finish_contours(contours, simplified, min_points, eps_factor, rule)
         coastline_mask = coastline_mask.cpu().numpy()
-    return _simplify(trace_external_contours(coastline_mask), min_points, eps_factor)
+    return (_simplify_exact if rule == "exact" else _simplify)(trace_external_contours(coastline_mask), min_points, eps_factor)
 
 
 # ------------------------------------------------------------------------------------------------ the extractor
@@ -420,10 +575,15 @@ def _is_prob_model(model):
 
 class CoastlineExtractor:
     """Drop-in for the reference's class (predict_coastline.py:336): same constructor and method names, results as described above.
-    model: a UNet (2-class logits, arg-max) or one of PROB_MODELS (1-channel probabilities, `> threshold`) with its weights loaded."""
+    model: a UNet (2-class logits, arg-max) or one of PROB_MODELS (1-channel probabilities, `> threshold`) with its weights loaded.
+    simplify_rule: "float64" (the default: host Douglas-Peucker in float64, as before) or "exact" (coastlines_from_mask): the contours are
+    then simplified on the device too, the simplified packed contours ride in the one result download in place of the raw ones, and one
+    more small size word (the simplifier's head) is read before it.  The result dict and save_extraction_result are the same."""
 
-    def __init__(self, model_path=None, device="cuda", model=None, input_size=512, threshold=0.5):
+    def __init__(self, model_path=None, device="cuda", model=None, input_size=512, threshold=0.5, simplify_rule="float64"):
         from .unet import UNet
+        _check_rule(simplify_rule)
+        self.simplify_rule = simplify_rule
         self.device = torch.device(device)
         self.input_size = int(input_size)
         self.threshold = float(threshold)
@@ -534,15 +694,18 @@ class CoastlineExtractor:
         """-> (coastlines, coastline_mask) as predict_coastline.py:583-618; water_mask: numpy array or device tensor, uint8."""
         mask = _dev_u8(water_mask, self.device)
         coast, _, _ = dilate_diff(mask, dilation_kernel_size)
+        rule = self.simplify_rule
+        if rule == "exact":
+            _check_exact_shape(*coast.shape)
         if not (coast.is_cuda and DEVICE_CONTOURS):
             coast = coast.cpu().numpy()
-            return coastlines_from_mask(coast), coast
-        # trace before the download; packed contours | coastline mask -> one download
-        packed = _trace_packed(coast, 10)
+            return coastlines_from_mask(coast, rule=rule), coast
+        # trace (rule "exact": and simplify) before the download; packed contours | coastline mask -> one download
+        packed, simplified = _coastlines_packed(coast, 10, 0.002, rule)
         head = 0 if packed is None else 4 * packed.numel()
         host = (coast.view(-1) if packed is None else torch.cat([packed.view(torch.uint8), coast.view(-1)])).cpu().numpy()
         contours = [] if packed is None else _unpack_contours(host[:head].view(np.int32))
-        return _simplify(contours, 10, 0.002), host[head:].reshape(coast.shape).copy()
+        return _finish_contours(contours, simplified, 10, 0.002, rule), host[head:].reshape(coast.shape).copy()
 
     def extract_coastline_from_image(self, image=None, output_dir=None, dilation_size=5, tiled=False, tile=512, halo=64, batch=8, bands=None,
                                      mode="water"):
@@ -550,6 +713,7 @@ class CoastlineExtractor:
         which is enhanced on the device (scene.py, `mode`): tiled, the enhanced scene feeds the tiles directly; resized, it is downloaded
         once for the PIL bilinear resize, the reference's order."""
         ellipse_spans(dilation_size)
+        rule = self.simplify_rule
         if tiled:
             self._check_size(tile, "tile")
         raster = _as_bands(image, bands)
@@ -566,6 +730,8 @@ class CoastlineExtractor:
         else:
             pil, path = _load_rgb(image)
             w, h = pil.size
+        if rule == "exact":
+            _check_exact_shape(h, w)
         # one device buffer for everything that goes back: water mask | coastline mask | the two counts -> one download
         seg = (h * w + 15) // 16 * 16
         buf = torch.empty(2 * seg + 16, device=self.device, dtype=torch.uint8)
@@ -580,7 +746,7 @@ class CoastlineExtractor:
             self._predict_resized(pil, out=water)
         dilate_diff(water, dilation_size, coast=coast, counts=counts)
         on_device = coast.is_cuda and DEVICE_CONTOURS
-        packed = _trace_packed(coast, 10) if on_device else None
+        packed, simplified = _coastlines_packed(coast, 10, 0.002, rule) if on_device else (None, False)
         if packed is not None:                           # the packed contours ride along in the one download
             buf = torch.cat([buf, packed.view(torch.uint8)])
         host = buf.cpu().numpy()
@@ -591,9 +757,9 @@ class CoastlineExtractor:
         n_water, n_coast = (int(v) for v in host[2 * seg:2 * seg + 8].view(np.int32))
         if on_device:
             contours = [] if packed is None else _unpack_contours(host[2 * seg + 16:].view(np.int32))
-            coastlines = _simplify(contours, 10, 0.002)
+            coastlines = _finish_contours(contours, simplified, 10, 0.002, rule)
         else:
-            coastlines = coastlines_from_mask(coast_np)
+            coastlines = coastlines_from_mask(coast_np, rule=rule)
         result = {"image_path": path if path is not None else "image", "image_size": (w, h), "water_mask": water_np,
                   "coastline_mask": coast_np, "coastlines": coastlines, "coastline_count": len(coastlines), "dilation_size": int(dilation_size),
                   "extraction_time": str(datetime.now()), "water_pixels": n_water, "coastline_pixels": n_coast}

@@ -831,6 +831,47 @@ int runet_contours_count(const unsigned char* mask, int h, int w, void* workspac
 int runet_contours_trace(int h, int w, void* workspace, long workspace_bytes, long n_states, int min_points, void* state_workspace,
                          long state_workspace_bytes, void* stream);
 
+/* ---- prediction: the polygons of those contours (predict_coastline.py:605-616; :612-615 is cv2.approxPolyDP(contour, 0.002 * arcLength))
+ *      on the device, by the project's EXACT Douglas-Peucker rule (csrc/simplify.hip).  It is a rule of its own, not the float64 rule of
+ *      predict.approx_poly_dp (whose ties are decided by rounding noise) and not a cv2 equality claim: every decision below is integer
+ *      arithmetic or ONE correctly rounded IEEE-754 double operation, ties go to the first index, so predict.approx_poly_dp_exact (host,
+ *      Python ints) and the kernels return the same lists bit for bit.
+ * Input.  A closed contour of n integer vertices p[0..n), coordinates in [0, 46340]; every cyclic edge is a run: dx == 0, dy == 0 or
+ *   |dx| == |dy|.  A vertex outside the range and an edge between two in-range vertices that is not a run are BAD INPUTS: counted, never
+ *   guessed at.
+ *   1. Arc length.  A = sum of |dx| + |dy| over the axis edges, D = sum of |dx| over the diagonal edges (exact integers, any order).
+ *      L = (double)A + (double)D * 0x1.6a09e667f3bcdp+0, eps = eps_factor * L, thr = eps * eps: four double operations, each rounded on its
+ *      own, NO fused multiply-add.
+ *   2. Far vertex.  far = the first index that maximises |p[i] - p[0]|^2 (below 2^32).  far == 0: the result is [p[0]] (this covers n == 1);
+ *      n == 2 keeps both vertices.
+ *   3. Chain.  Positions 0..n with q[n] = p[0]; positions 0, far and n are kept; plain Douglas-Peucker on every segment (a, b) of
+ *      consecutive kept positions with b - a >= 2.
+ *   4. Distance numerator of interior position i.  ab = q[b] - q[a], ap = q[i] - q[a], den = ab.ab, dot = ap.ab:
+ *        den == 0: N = |ap|^2, and 1 stands in for den below;   dot <= 0: N = |ap|^2 den;   dot >= den: N = |q[i] - q[b]|^2 den;
+ *        otherwise N = (ap x ab)^2.  N = den * (squared distance to the CLIPPED segment) < 2^64: unsigned 64-bit, signed 64-bit cross product.
+ *   5. Split.  k = the first interior position that maximises N; the segment splits at k iff (double)N > thr * (double)den (uint64 -> double
+ *      rounds to nearest-even, the product is one rounded operation, the comparison is strict).
+ *   6. Output.  The kept positions below n, in order.  No contour is dropped after simplification.
+ * packed: the tracer's device result, int32 {n, total, offsets [n + 1], points [total][2]}, 4-byte aligned; n and total are the caller's (it
+ *   has read them to cut the result) and must be the two leading words, offsets must rise from 0 to total - anything else counts as bad input.
+ * workspace: >= runet_contours_simplify_workspace_bytes(n, total) bytes (-1 unless 0 <= n <= total < 2^30), 16-byte aligned.  At its start
+ *   stands the HEAD, int32 {n, kept vertices, bad inputs, largest round count of any contour}; at byte
+ *   runet_contours_simplify_result_offset() the packed result in the input's format, {n, kept, offsets [n + 1], points [kept][2]}.  The
+ *   caller reads the head as its one size word.  bad inputs != 0: kept reads 0 and NOTHING is written past the head.
+ * Formulation.  One workgroup per contour; level-synchronous rounds inside the kernel with workgroup barriers only (no grid barrier, no
+ *   cooperative launch, no waiting on other workgroups).  In a round every interior position of a still-open segment computes its N, the
+ *   segment takes (max N, first index) by integer atomicMax / atomicMin, decides, and its positions narrow their bounds or close.  Every
+ *   round splits or closes every open segment: at most n rounds, the contour's recursion depth.  Contours of at most lds_max_vertices
+ *   vertices (negative: the default; capped at the 2048 that fit LDS) keep their state in LDS, longer ones in the workspace; the results are
+ *   the same bytes.  One prefix sum over the keep flags of all vertices gives slots and offsets, an emit pass writes the result.
+ * All validation on the host before any device work: sizes, a finite eps_factor >= 0, workspace size and alignment.  n == 0 launches
+ * nothing and writes an empty head and result.  No float atomics, nothing depends on arrival order: two runs give the same bytes.
+ * runet_contours_simplify_workspace_bytes / runet_contours_simplify_result_offset: HOST ONLY. */
+long runet_contours_simplify_workspace_bytes(long n, long total);
+long runet_contours_simplify_result_offset(void);
+int runet_contours_simplify(const int* packed, long n, long total, double eps_factor, int lds_max_vertices, void* workspace,
+                            long workspace_bytes, void* stream);
+
 /* ---- ENet baseline (comne.py:482-608; csrc/enet.hip, the rectangular launchers in csrc/conv_igemm.hip).  Its 1x1 and 3x3 (dilation 1..16)
  *      convolutions, BatchNorm + ReLU, the 2x2 max-pool and the k3-s2 transposed convolutions' gradients and A/B forward (the data gradient of a stride-2 convolution,
  *      runet_conv2d_general) are shared; these are the pieces nothing else expresses.  NHWC fp32, pixel strides multiples of 4 floats that cover

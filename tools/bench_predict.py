@@ -14,10 +14,15 @@
   * contour tracing (csrc/contours.hip) against the host tracer on the same coastline band, on this box, in interleaved rounds: the band
     of the 512^2 scene above, and the bands of a seeded smooth random field at 2048^2 and 10980^2; device time by device events and by the
     wall clock including its three downloads, the workspace bytes at each size.  Where the host tracer would exceed --host-budget seconds
-    it is timed on the top-left 2048^2 crop instead, and the report says so.
+    it is timed on the top-left 2048^2 crop instead, and the report says so;
+  * polygon simplification by the exact rule (csrc/simplify.hip) on the traced contours of those bands, interleaved the same way: the
+    device kernels by events, device trace + simplify + downloads by the wall clock, the default path (trace, download, host float64
+    Douglas-Peucker) by the wall clock, and the two host rules alone on the same contours (on the first contours only where all of them
+    would exceed --host-budget, and the report says so); vertices in and out, the largest round count, download and workspace bytes
+    (figures kept in profiles/contours_simplify.txt).
 
 Not a bench line of the contract (bench.py measures the Robust U-Net training metric); the figures are kept in profiles/predict_postprocess.txt.
-  python tools/bench_predict.py [--what all|path|kernels|contours] [--model unet] [--window 0.5] [--host-budget 20] [--out FILE]
+  python tools/bench_predict.py [--what all|path|kernels|contours|simplify] [--model unet] [--window 0.5] [--host-budget 20] [--out FILE]
 """
 import argparse
 import importlib
@@ -313,9 +318,90 @@ def contour_rows(sizes, host_budget):
     return rows
 
 
+def simplify_rows(sizes, host_budget):
+    """polygon simplification by the exact rule on the device (csrc/simplify.hip) against the host: the float64 rule (predict._simplify,
+    what the default path runs after the trace) and the exact rule's host restatement, on the traced contours of the bands of
+    contour_rows; the host side on the first contours only where all of them would exceed the budget"""
+    lib = importlib.import_module("eusipco-2026-robust-unet_amd._lib").lib
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    rows = []
+    host_v_per_s = {}
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    for size in sizes:
+        water = torch.from_numpy(scene_u8(512, 512, 1)[1]).to(DEV) if size == 512 else field_water(size, size)
+        band = P.dilate_diff(water, 5)[0]
+        del water
+        packed, (n, total) = P._trace_packed(band, 10, with_sizes=True)
+        contours = P._unpack_contours(packed.cpu().numpy())
+        # the host side: all contours, or the first ones whose vertices fit the budget at the speed measured on the size before
+        n_host = n
+        slowest = min(host_v_per_s.values()) if host_v_per_s else None
+        if slowest is not None and total / slowest > host_budget:
+            lens = np.cumsum([len(c) for c in contours])
+            n_host = max(1, int(np.searchsorted(lens, slowest * host_budget)))
+        host_contours = contours[:n_host]
+        host_vertices = int(sum(len(c) for c in host_contours))
+        ws_bytes = lib.runet_contours_simplify_workspace_bytes(n, total)
+        ws = torch.empty(ws_bytes, device=DEV, dtype=torch.uint8)
+
+        def kernels():
+            assert lib.runet_contours_simplify(packed.data_ptr(), n, total, 0.002, -1, ws.data_ptr(), ws_bytes, None) == 0
+
+        rounds = 5 if size <= 512 else 3
+        t_dev, t_wall_exact, t_wall_default, t_f64, t_exact = [], [], [], [], []
+        kernels()
+        got = P.coastlines_from_mask(band, rule="exact")     # warm-up: code objects, allocator
+        for _ in range(rounds):                              # interleaved: device, host, device, host, ...
+            torch.cuda.synchronize()
+            ev[0].record()
+            kernels()
+            ev[1].record()
+            ev[1].synchronize()
+            t_dev.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+            t, got = wall(lambda: P.coastlines_from_mask(band, rule="exact"))
+            t_wall_exact.append(t)
+            t, lines_f64 = wall(lambda: P._simplify(host_contours, 10, 0.002))
+            t_f64.append(t)
+            t, lines_exact = wall(lambda: P._simplify_exact(host_contours, 10, 0.002))
+            t_exact.append(t)
+            if n_host == n:
+                t, default = wall(lambda: P.coastlines_from_mask(band))
+                t_wall_default.append(t)
+        assert got[:n_host] == lines_exact, "device and host lists of the exact rule differ"
+        head = ws[:16].view(torch.int32).cpu().tolist()
+        assert head[0] == n and head[2] == 0 and head[1] == sum(len(c) for c in got)
+        host_v_per_s = {"f64": host_vertices / float(np.median(t_f64)), "exact": host_vertices / float(np.median(t_exact))}
+        differ = sum(a != b for a, b in zip(lines_f64, lines_exact))
+        med = lambda v: round(float(np.median(v)) * 1e3, 3) if v else None
+        row = {"size": size, "contours": n, "vertices_in": total, "vertices_out": head[1], "largest_round_count": head[3],
+               "device_simplify_ms_events": med(t_dev), "device_trace_simplify_downloads_ms_wall": med(t_wall_exact),
+               "default_trace_download_host_float64_ms_wall": med(t_wall_default), "host_float64_ms": med(t_f64), "host_exact_ms": med(t_exact),
+               "host_on_contours": n_host, "host_on_vertices": host_vertices, "float64_and_exact_lists_differ_on": differ,
+               "download_bytes_before": 4 * (3 + n + 2 * total), "download_bytes_after": 4 * (3 + n + 2 * head[1]), "workspace_bytes": ws_bytes,
+               "rounds": rounds}
+        rows.append(row)
+        scale = total / max(1, host_vertices)
+        say(f"  {size:5d}^2 band: {n} contours, {total} -> {head[1]} vertices, largest round count {head[3]} | device simplify "
+            f"{row['device_simplify_ms_events']:.3f} ms (events) | device trace + simplify + downloads {row['device_trace_simplify_downloads_ms_wall']:.3f} ms (wall)"
+            + (f" | default path (trace, download, host float64) {row['default_trace_download_host_float64_ms_wall']:.3f} ms (wall)" if t_wall_default else "")
+            + f" | host float64 _simplify {row['host_float64_ms']:.1f} ms, host exact rule {row['host_exact_ms']:.1f} ms on "
+            + (f"all contours" if n_host == n else f"the first {n_host} contours ({host_vertices} vertices, x {scale:.1f} for all)")
+            + f"; the two rules differ on {differ} of them | download {row['download_bytes_before']} -> {row['download_bytes_after']} bytes | "
+            f"workspace {ws_bytes / 2**20:.1f} MiB | medians of {rounds} interleaved rounds")
+        del band, ws, packed
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", default="all", choices=("all", "path", "kernels", "contours"))
+    ap.add_argument("--what", default="all", choices=("all", "path", "kernels", "contours", "simplify"))
     ap.add_argument("--model", default="unet", choices=sorted(MODELS), help="the model of the whole-prediction lines; any but unet also "
                     "times the two kernels of the probability route")
     ap.add_argument("--host-budget", type=float, default=20.0, help="seconds one host tracing run may take before it moves to a 2048^2 crop")
@@ -336,6 +422,10 @@ def main():
     if a.what in ("all", "contours"):
         say("contour tracing (csrc/contours.hip against predict.trace_external_contours on the same band, results checked equal):")
         res["contours"] = contour_rows((512, 2048, 10980), a.host_budget)
+    if a.what in ("all", "simplify"):
+        say("polygon simplification (csrc/simplify.hip, the exact rule, against the host float64 rule and the exact rule's host restatement on "
+            "the same traced contours; eps factor 0.002, contours of more than 10 vertices; device and host lists of the exact rule checked equal):")
+        res["simplify"] = simplify_rows((512, 2048, 10980), a.host_budget)
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(LINES) + "\n")
