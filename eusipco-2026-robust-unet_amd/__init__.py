@@ -16,6 +16,9 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   trace_external_contours_device (its cv2.findContours step as parallel border following on the device)
   enhance_scene, convert_scene, band_percentiles, select_bands, percentile_ranks (scene.py: the multi-band raster -> uint8 RGB step of
   tif_to_image.py / predict_coastline.py on the device: exact 2-98 % percentiles and the float64 stretch)
+  combined_overlay, ndwi_histograms, rgb_histograms, coastline_lengths, analysis_report, create_coastsat_style_visualization,
+  error_overlays, generate_error_maps (report.py: the arrays of the reference's analysis report and error-map figures on the device, bit
+  for bit numpy's; matplotlib only draws them)
   DeviceCoastalDataset, DeviceLoader, Augment, prepare_device_dataset, resize_pil_device, resample_tables, nearest_table, rotation_words
   (device_data.py: the dataset built once and kept on the device as bytes, PIL-exact resampling there, batches assembled on the device with
   the augmentation of train_water_segmentation.py:313-321)
@@ -52,6 +55,8 @@ _LAZY = {
     "PSPNet": "pspnet", "PyramidPooling": "pspnet",
     "enhance_scene": "scene", "convert_scene": "scene", "band_percentiles": "scene", "select_bands": "scene", "percentile_ranks": "scene",
     "trace_external_contours_device": "predict",
+    "combined_overlay": "report", "ndwi_histograms": "report", "rgb_histograms": "report", "coastline_lengths": "report",
+    "analysis_report": "report", "create_coastsat_style_visualization": "report", "error_overlays": "report", "generate_error_maps": "report",
     "DeviceCoastalDataset": "device_data", "DeviceLoader": "device_data", "Augment": "device_data", "prepare_device_dataset": "device_data",
     "resize_pil_device": "device_data", "resample_tables": "device_data", "nearest_table": "device_data", "rotation_words": "device_data",
 }

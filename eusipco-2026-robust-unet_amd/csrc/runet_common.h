@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "../../include/runet_hip.h"
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -59,6 +61,20 @@ static inline int ew_grid(long total, int cap) {
     RUNET_REQUIRE((ld) >= (c) && (ld) % 4 == 0 && ((uintptr_t)(p) % 16) == 0,         \
                   "pixel strides must be multiples of 4 floats that cover the channels, tensors 16-byte aligned")
 
+static inline int runet_band_elem_size(int dtype) { return dtype == RUNET_BAND_U8 ? 1 : dtype == RUNET_BAND_F32 ? 4 : 2; }
+// The raster checks of the entry points that read band planes (scene_bands.hip, report.hip): a planar [n_bands][h][w] raster read through
+// strides (in elements) that cover its extent.  runet_band_elem_size: bytes per element of a RUNET_BAND_* dtype.
+#define RUNET_REQ_BANDS()                                                                                                            \
+    do {                                                                                                                             \
+        RUNET_REQUIRE(dtype >= RUNET_BAND_U8 && dtype <= RUNET_BAND_F32, "dtype must be RUNET_BAND_U8 / U16 / I16 / F32");           \
+        RUNET_REQUIRE(n_bands >= 1 && h > 0 && w > 0, "bad shape");                                                                  \
+        RUNET_REQUIRE((long)h * w < 2147483648L, "h * w must be below 2^31");                                                        \
+        RUNET_REQUIRE(elem_stride >= 1 && row_stride >= (long)(w - 1) * elem_stride + 1, "strides smaller than a row's extent");     \
+        RUNET_REQUIRE(n_bands == 1 || band_stride >= (long)(h - 1) * row_stride + (long)(w - 1) * elem_stride + 1,                   \
+                      "band stride smaller than a band's extent");                                                                   \
+        RUNET_REQUIRE(((uintptr_t)bands % runet_band_elem_size(dtype)) == 0, "bands must be aligned to their element size");                    \
+    } while (0)
+
 // gemm.hip (internal launchers behind runet_gemm_batched / runet_gemm_tn_batched)
 int runet_gemm_nn_launch(const float* a, int lda, long sa, const float* b, long sb, float* c, int ldc, long sc, int batch, int rows, int k, int n,
                          hipStream_t st);
@@ -84,6 +100,19 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// LDS histograms private to a wave: one count for `bin` (or none: bin < 0) from every lane of a converged wave.  The lanes that hold the
+// first active lane's bin are added by that lane in one atomic: a run of equal keys costs one LDS atomic per wave, not 64 serialised ones on
+// one address.
+__device__ __forceinline__ void wave_add(unsigned* h, int bin, int lane) {
+    const unsigned long long act = __ballot(bin >= 0);
+    if (act == 0) return;
+    const int leader = __ffsll((long long)act) - 1;
+    const int lb = __shfl(bin, leader, 64);
+    const unsigned long long same = __ballot(bin == lb);
+    if (lane == leader) atomicAdd(&h[lb], (unsigned)__popcll(same));
+    else if (bin >= 0 && bin != lb) atomicAdd(&h[bin], 1u);
+}
+
 // 16-byte access to four consecutive floats (p 16-byte aligned)
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, const f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }

@@ -51,18 +51,6 @@ template <> struct KeyOf<float> {
 };
 __device__ __forceinline__ float key_to_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
-// One count for `bin` (or none: bin < 0) from every lane of a converged wave.  The lanes that hold the first active lane's bin are added by
-// that lane in one atomic: a run of equal keys costs one LDS atomic per wave, not 64 serialised ones on one address.
-__device__ __forceinline__ void wave_add(unsigned* h, int bin, int lane) {
-    const unsigned long long act = __ballot(bin >= 0);
-    if (act == 0) return;
-    const int leader = __ffsll((long long)act) - 1;
-    const int lb = __shfl(bin, leader, 64);
-    const unsigned long long same = __ballot(bin == lb);
-    if (lane == leader) atomicAdd(&h[lb], (unsigned)__popcll(same));
-    else if (bin >= 0 && bin != lb) atomicAdd(&h[bin], 1u);
-}
-
 // A block walks the rows blockIdx.x, blockIdx.x + gridDim.x, ...; a lane owns one 16-byte group of a row, cut on addresses when the elements
 // are contiguous (one 16-byte load), element by element at a row's ends and for strided elements.
 template <typename T>
@@ -280,8 +268,6 @@ __global__ __launch_bounds__(TPB) void band_stretch_kernel(const T* __restrict__
     }
 }
 
-int elem_size(int dtype) { return dtype == RUNET_BAND_U8 ? 1 : dtype == RUNET_BAND_F32 ? 4 : 2; }
-
 template <typename T>
 void launch_pass(const void* bands, int h, int w, long bs, long rs, long es, Sel3 sel, int n_sel, int pass, int shift, unsigned* hist,
                  const SelState* st, int* nonfinite, hipStream_t s) {
@@ -296,18 +282,6 @@ void launch_stretch(const void* bands, int h, int w, long bs, long rs, long es, 
                        rs, es, sel, pct, mode, out, ors);
 }
 }  // namespace
-
-// The checks both entry points share: a planar [n_bands][h][w] raster read through strides (in elements) that cover its extent.
-#define RUNET_REQ_BANDS()                                                                                                            \
-    do {                                                                                                                             \
-        RUNET_REQUIRE(dtype >= RUNET_BAND_U8 && dtype <= RUNET_BAND_F32, "dtype must be RUNET_BAND_U8 / U16 / I16 / F32");           \
-        RUNET_REQUIRE(n_bands >= 1 && h > 0 && w > 0, "bad shape");                                                                  \
-        RUNET_REQUIRE((long)h * w < 2147483648L, "h * w must be below 2^31");                                                        \
-        RUNET_REQUIRE(elem_stride >= 1 && row_stride >= (long)(w - 1) * elem_stride + 1, "strides smaller than a row's extent");     \
-        RUNET_REQUIRE(n_bands == 1 || band_stride >= (long)(h - 1) * row_stride + (long)(w - 1) * elem_stride + 1,                   \
-                      "band stride smaller than a band's extent");                                                                   \
-        RUNET_REQUIRE(((uintptr_t)bands % elem_size(dtype)) == 0, "bands must be aligned to their element size");                    \
-    } while (0)
 
 extern "C" long runet_band_percentiles_workspace(int n_sel) {
     if (n_sel < 1 || n_sel > MAXSEL) return -1;
@@ -338,7 +312,7 @@ static int band_percentiles_impl(const void* bands, int dtype, int n_bands, int 
         runet_set_error("runet_band_percentiles: clearing the workspace failed");
         return RUNET_ELAUNCH;
     }
-    const int passes = elem_size(dtype) == 1 ? 1 : elem_size(dtype) == 2 ? 2 : 4;
+    const int passes = runet_band_elem_size(dtype) == 1 ? 1 : runet_band_elem_size(dtype) == 2 ? 2 : 4;
     if (ev) (void)hipEventRecord(ev[0], s);
     for (int p = 0; p < passes; ++p) {
         const int shift = 8 * (passes - 1 - p);

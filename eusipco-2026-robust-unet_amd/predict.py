@@ -23,7 +23,8 @@ simplify_rule="exact", the simplifier's head (its kept-vertex count).
 every output pixel is taken from exactly one tile's core (tile_plan), so there is no blending and the result is bit-deterministic.
 
 OpenCV is not a dependency.  Steps 3-5 restate OpenCV's rules (index rule, ellipse spans, Suzuki-Abe border following); vertex-for-vertex
-equality of the contours with cv2 is not claimed.  The matplotlib report, the GUI and the CLI are out of scope.
+equality of the contours with cv2 is not claimed.  The analysis report (:659-846) is report.py: its arrays come from the device, matplotlib
+only draws them (`report=True` below).  The GUI and the CLI are out of scope.
 
 Multi-band rasters (load_tif_image, :425-581) come in through scene.py: `extract_coastline_from_image` and `predict_scene` take the raw
 bands - a [B, H, W] array or device tensor with B <= 6, a .npy path, or anything through `bands=` (a .tif path there is read with GDAL where
@@ -544,9 +545,10 @@ def _as_bands(image, bands):
     return None
 
 
-def save_extraction_result(result, output_dir):
-    """predict_coastline.py:620-652 without the matplotlib report: <base>_water_mask.png, <base>_coastline_mask.png (* 255) and
-    <base>_coastlines.json with the reference's keys."""
+def save_extraction_result(result, output_dir, report=False):
+    """predict_coastline.py:620-652: <base>_water_mask.png, <base>_coastline_mask.png (* 255) and <base>_coastlines.json with the
+    reference's keys.  report=True: also the reference's fourth product, <base>_coastsat_analysis.png (report.py), drawn from
+    result["report"] (computed from the result where it is missing, and stored there); that alone needs matplotlib."""
     os.makedirs(output_dir, exist_ok=True)
     base = os.path.splitext(os.path.basename(str(result["image_path"])))[0]
     Image.fromarray(result["water_mask"] * 255).save(os.path.join(output_dir, f"{base}_water_mask.png"))
@@ -556,6 +558,11 @@ def save_extraction_result(result, output_dir):
            "extraction_time": result["extraction_time"]}
     with open(os.path.join(output_dir, f"{base}_coastlines.json"), "w", encoding="utf-8") as fh:
         json.dump(doc, fh, indent=2, ensure_ascii=False)
+    if report:
+        from . import report as _report
+        if "report" not in result:
+            result["report"] = _report.analysis_report(result)
+        _report.create_coastsat_style_visualization(result, output_dir, report=result["report"])
 
 
 def _raise_nonfinite(count):
@@ -708,10 +715,13 @@ class CoastlineExtractor:
         return _finish_contours(contours, simplified, 10, 0.002, rule), host[head:].reshape(coast.shape).copy()
 
     def extract_coastline_from_image(self, image=None, output_dir=None, dilation_size=5, tiled=False, tile=512, halo=64, batch=8, bands=None,
-                                     mode="water"):
+                                     mode="water", report=False):
         """predict_coastline.py:366-423.  `image`: a path, a PIL image or a uint8 [H, W, 3] array as before, or a band raster (_as_bands),
         which is enhanced on the device (scene.py, `mode`): tiled, the enhanced scene feeds the tiles directly; resized, it is downloaded
-        once for the PIL bilinear resize, the reference's order."""
+        once for the PIL bilinear resize, the reference's order.
+        report=True: the result gains "report" (report.analysis_report's arrays), computed from the masks and the scene while they are on
+        the device, before the download; a raster's background is its "display"-mode image, its histograms are NDWI from four bands on.
+        With output_dir the analysis PNG is written too (matplotlib)."""
         ellipse_spans(dilation_size)
         rule = self.simplify_rule
         if tiled:
@@ -747,6 +757,15 @@ class CoastlineExtractor:
         dilate_diff(water, dilation_size, coast=coast, counts=counts)
         on_device = coast.is_cuda and DEVICE_CONTOURS
         packed, simplified = _coastlines_packed(coast, 10, 0.002, rule) if on_device else (None, False)
+        arrays = None
+        if report:
+            from . import report as _report
+            if raster is not None:
+                display, bad = _scene._enhance(r, "display")
+                _raise_nonfinite(int(bad.item()))
+            else:
+                display = _dev_u8(np.array(pil, dtype=np.uint8), self.device)
+            arrays = _report._device_arrays(display, water, coast, r if raster is not None else None, 50)
         if packed is not None:                           # the packed contours ride along in the one download
             buf = torch.cat([buf, packed.view(torch.uint8)])
         host = buf.cpu().numpy()
@@ -763,8 +782,10 @@ class CoastlineExtractor:
         result = {"image_path": path if path is not None else "image", "image_size": (w, h), "water_mask": water_np,
                   "coastline_mask": coast_np, "coastlines": coastlines, "coastline_count": len(coastlines), "dilation_size": int(dilation_size),
                   "extraction_time": str(datetime.now()), "water_pixels": n_water, "coastline_pixels": n_coast}
+        if arrays is not None:
+            result["report"] = _report._with_statistics(arrays, h * w, n_water, n_coast, coastlines)
         if output_dir:
-            save_extraction_result(result, output_dir)
+            save_extraction_result(result, output_dir, report=report)
         return result
 
     save_extraction_result = staticmethod(save_extraction_result)

@@ -1057,6 +1057,61 @@ int runet_batch_assemble(const unsigned char* images, const unsigned char* masks
                          float mean1, float mean2, float std0, float std1, float std2, const int* geom, const float* factors, const long* sums,
                          int mask_mode, float* out_images, float* out_masks, void* stream);
 
+/* ---- report arrays: what the reference's two figures show, computed on the device (csrc/report.hip, report.py).  The analysis report of one
+ *      extraction (predict_coastline.py:708-835) and the error maps of the model comparison (Extended_Baseline_Comparison.py:882-959) are
+ *      numpy on the host there.  Every result below equals numpy's bit for bit (tests/report_ref.py restates the rules).  h * w < 2^31.  No
+ *      floating-point atomics; integer atomics only, so the bits do not depend on arrival order.  All validation happens on the host before
+ *      any device work; no call synchronises the host.
+ * runet_report_overlay_u8 (:708-730, the "combined" panel): image and out dense interleaved uint8 [h][w][3], water and coast dense uint8
+ *   [h][w], all 4-byte aligned; table uint8 [3][256] on the device.  Per pixel: coast == 1 -> (255, 255, 255); else water == 1 -> channel c
+ *   becomes table[c][v]; else unchanged (mask bytes other than 1 leave the pixel alone; coast wins over water).  The HOST fills the table
+ *   from the reference's own expression, the C cast to uint8 (truncation) of float64(v) * 0.6 + (0, 100, 200)[c] * 0.4.  5 bytes read and
+ *   3 written per pixel.
+ * runet_ndwi_stats / runet_ndwi_hist (:789-813, the NDWI histograms of the water and the non-water pixels): bands as in the scene ingestion
+ *   (planar, strided, RUNET_BAND_*), n_bands >= 4, green = plane 1, NIR = plane 3 (GetRasterBand(2) and (4)); mask dense uint8 [h][w].
+ *   Per pixel in float64, each operation rounded once, true division, no contraction:  x = (g - n) / ((g + n) + 1e-8).
+ *   Class 0 "water" is mask == 1, class 1 "rest" is mask == 0; other mask bytes count nowhere.
+ *   stats, device 8 x 64-bit words, written whole by the call: {count water, count rest, non-finite x over both classes, min key water, max
+ *     key water, min key rest, max key rest, 0}.  A non-finite x is counted in word 2 only.  key(x) = the bits of x with -0.0 taken as +0.0,
+ *     then ~bits for a negative x and bits | 2^63 otherwise: unsigned order = numeric order; an empty class keeps min key 2^64 - 1 and max
+ *     key 0.  Integer atomics (add, min, max).
+ *   hist: edges, device float64 [2][bins + 1] (class-major, rising: np.linspace(min, max, bins + 1) built by the host, as np.histogram
+ *     builds them), 2 <= bins <= 256; counts, device 64-bit [2][bins], cleared by the call.  Bin i holds edges[i] <= x < edges[i + 1], the
+ *     last bin also x == edges[bins]; computed numpy's way (the equal-bin path of np.histogram): i = trunc(((x - first) / (last - first)) *
+ *     bins), i == bins -> bins - 1, then i - 1 if x < edges[i], then i + 1 if x >= edges[i + 1] and i != bins - 1.  x outside [first, last]
+ *     or NaN counts nowhere.  Histograms private to a wave in LDS, merged with integer atomics.
+ *   stats reads 2 elements + 1 byte per pixel and writes nothing but the eight words; hist the same plus 2 * bins counts.
+ * runet_rgb_hist_u8 (:821-829, the fallback below four bands): image dense interleaved uint8 [h][w][3], 4-byte aligned -> hist, device
+ *   64-bit [3][256], cleared by the call: the exact count of every byte value per channel.  3 bytes read per pixel.  The host folds it into
+ *   np.histogram's bins (report.py: fold_byte_histogram).
+ * runet_error_overlays (Extended_Baseline_Comparison.py:882-959): images fp32 [n][3][h][w] (normalised), prob and masks fp32 [n][1][h][w],
+ *   1 <= n <= 65535.  One pass, per pixel and channel c, fp32 operations each rounded once, no contraction:
+ *     vis  fp32 [n][h][w][3] = clamp(fl32(fl32(x * std[c]) + mean[c]), 0, 1) with v < 0 -> 0, v > 1 -> 1 (NaN stays NaN)          (:885)
+ *     p = prob > threshold (ordered: NaN is not);  class TP: p and g == 1, FP: p and g == 0, FN: not p and g == 1, TN: not p and g == 0;
+ *       a mask value that is neither 0 nor 1 (NaN included) puts the pixel in a fifth class "none"                                  (:920-927)
+ *     overlay fp64 [n][h][w][3] = float64(fl32(fl32(0.4) * vis)) + colours[class][c], colours device float64 [5][3] = 0.6 * the class
+ *       colour as the HOST computes it in float64 (TP .2 .8 .2, FP .9 .2 .2, FN .2 .2 .9, TN .9 .9 .9, none 0 0 0)                 (:929-935)
+ *     err fp32 [n][h][w] = |prob - masks| in fp32                                                                                  (:954)
+ *     counts, device 64-bit [n][5] (cleared by the call) = the pixels of each class (TP, FP, FN, TN, none); integer atomics         (:940-941)
+ *     sums, device float64 [n] = S, the sum of err in float64 in this fixed order (the host's mae = S / (h * w); np.mean at :957 adds the
+ *       fp32 values pairwise in fp32 and differs by that rounding only): pixels are cut into chunks of 1024, chunk b = [1024 b, 1024 (b + 1)),
+ *       err beyond h * w counting as 0.  In a chunk, t = 0..255: d[t] = ((e[t] + e[t + 256]) + e[t + 512]) + e[t + 768]; the 256 d fall into
+ *       four groups of 64 consecutive t, each folded by a[t] += a[t + o] for o = 32, 16, 8, 4, 2, 1 to a[0]; chunk sum = ((a0 + a1) + a2) +
+ *       a3.  Then lane l = 0..63 adds the chunk sums l, l + 64, l + 128, ... in that order from 0.0, and the 64 lanes fold the same way.
+ *   workspace: at least runet_error_overlays_workspace_bytes(n, h, w) BYTES (host only; -1: bad shape), 8-byte aligned: the chunk sums.
+ *   20 bytes read and 40 written per pixel (12 vis + 24 overlay + 4 err). */
+int runet_report_overlay_u8(const unsigned char* image, const unsigned char* water, const unsigned char* coast, int h, int w,
+                            const unsigned char* table, unsigned char* out, void* stream);
+int runet_ndwi_stats(const void* bands, int dtype, int n_bands, int h, int w, long band_stride, long row_stride, long elem_stride,
+                     const unsigned char* mask, long* stats, void* stream);
+int runet_ndwi_hist(const void* bands, int dtype, int n_bands, int h, int w, long band_stride, long row_stride, long elem_stride,
+                    const unsigned char* mask, const double* edges, int bins, long* counts, void* stream);
+int runet_rgb_hist_u8(const unsigned char* image, int h, int w, long* hist, void* stream);
+long runet_error_overlays_workspace_bytes(int n, int h, int w);
+int runet_error_overlays(const float* images, const float* prob, const float* masks, int n, int h, int w, float threshold, float mean0,
+                         float mean1, float mean2, float std0, float std1, float std2, const double* colours, float* vis, double* overlay,
+                         float* err, long* counts, double* sums, void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

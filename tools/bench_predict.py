@@ -21,8 +21,13 @@
     would exceed --host-budget, and the report says so); vertices in and out, the largest round count, download and workspace bytes
     (figures kept in profiles/contours_simplify.txt).
 
+  * --what report: the kernels behind the report figures (csrc/report.hip: combined overlay, NDWI pass 1 and pass 2, RGB histogram,
+    error overlays) at 512^2, 2048^2 and 10980^2: device-event time and GB/s over the bytes each must move, beside numpy on this host
+    running the restatement tests/report_ref.py on the same data (results checked equal first); and the public functions end to end by
+    the wall clock, upload, synchronisation and download included, against the same numpy (figures kept in profiles/report.txt).
+
 Not a bench line of the contract (bench.py measures the Robust U-Net training metric); the figures are kept in profiles/predict_postprocess.txt.
-  python tools/bench_predict.py [--what all|path|kernels|contours|simplify] [--model unet] [--window 0.5] [--host-budget 20] [--out FILE]
+  python tools/bench_predict.py [--what all|path|kernels|contours|simplify|report] [--model unet] [--window 0.5] [--host-budget 20] [--out FILE]
 """
 import argparse
 import importlib
@@ -399,9 +404,116 @@ def simplify_rows(sizes, host_budget):
     return rows
 
 
+def report_rows(sizes, window_s, end_to_end_sizes=(128, 256, 512, 2048, 10980)):
+    """the report kernels against numpy running tests/report_ref.py on this host"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import report_ref as R
+    M = importlib.import_module("eusipco-2026-robust-unet_amd.report")
+    S = importlib.import_module("eusipco-2026-robust-unet_amd.scene")
+    lib = importlib.import_module("eusipco-2026-robust-unet_amd._lib").lib
+
+    def host(fn):
+        t0 = time.perf_counter()
+        r = fn()
+        return time.perf_counter() - t0, r
+
+    def wall(fn):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts))
+
+    def inputs(size):
+        rng = np.random.default_rng(size)
+        img, water = scene_u8(size, size, size)
+        coast = P.dilate_diff(torch.from_numpy(water).to(DEV), 5)[0].cpu().numpy()
+        bands = rng.integers(1, 4096, (4, size, size)).astype(np.uint16)
+        bands[3][water == 1] //= 4                       # water is dark in the near infrared: two separated NDWI populations
+        x = (rng.standard_normal((1, 3, size, size)) * 1.5).astype(np.float32)
+        prob = rng.random((1, 1, size, size)).astype(np.float32)
+        gt = water.astype(np.float32)[None, None]
+        return img, water, coast, bands, x, prob, gt
+
+    rows, e2e = [], []
+    for size in sorted(set(sizes) | set(end_to_end_sizes)):
+        n = size * size
+        img, water, coast, bands, x, prob, gt = inputs(size)
+        t_np = {}
+        t_np["combined_overlay"], want_overlay = host(lambda: R.combined_overlay(img, water, coast))
+        t_np["ndwi pass 1 (index, min, max)"], sel = host(lambda: [(v, v.min(), v.max()) for x_ in (R.ndwi(bands),) for v in (x_[water == 1], x_[water == 0])])
+        t_np["ndwi pass 2 (binning)"], want_hist = host(lambda: [np.histogram(v[0], bins=50) for v in sel])
+        t_np["rgb histogram"], want_rgb = host(lambda: [np.histogram(img[:, :, c].flatten(), bins=50, density=True) for c in range(3)])   # :828, once per channel
+        t_np["error_overlays"], want_err = host(lambda: R.error_overlays(x, prob, gt))
+        del sel
+        # end to end: numpy in, numpy out, by the wall clock
+        t_dev = {"combined_overlay": wall(lambda: M.combined_overlay(img, water, coast)),
+                 "ndwi_histograms": wall(lambda: M.ndwi_histograms(bands, water)),
+                 "rgb_histograms": wall(lambda: M.rgb_histograms(img)),
+                 "error_overlays": wall(lambda: M.error_overlays(x, prob, gt))}
+        t_host = {"combined_overlay": t_np["combined_overlay"], "ndwi_histograms": t_np["ndwi pass 1 (index, min, max)"] + t_np["ndwi pass 2 (binning)"],
+                  "rgb_histograms": t_np["rgb histogram"], "error_overlays": t_np["error_overlays"]}
+        e2e.append({"size": size, **{k: {"device_ms_wall": round(t_dev[k] * 1e3, 3), "numpy_ms": round(t_host[k] * 1e3, 3)} for k in t_dev}})
+        say(f"  {size:5d}^2  end to end (upload, kernels, syncs, download | numpy): " + "; ".join(
+            f"{k} {t_dev[k] * 1e3:.2f} | {t_host[k] * 1e3:.2f} ms" for k in t_dev))
+        if size not in sizes:
+            continue
+        # the kernels alone, inputs and outputs on the device
+        d_img, d_water, d_coast = (torch.from_numpy(a).to(DEV) for a in (img, water, coast))
+        r = S.load_raster(bands, DEV)
+        got = M.ndwi_histograms(r, d_water)
+        assert np.array_equal(M.combined_overlay(d_img, d_water, d_coast), want_overlay)
+        assert all(np.array_equal(got[k]["counts"], w[0]) and np.array_equal(got[k]["edges"], w[1]) for k, w in zip(("water", "other"), want_hist))
+        got = M.rgb_histograms(d_img)
+        assert all(np.array_equal(got[k]["density"], w[0]) and np.array_equal(got[k]["edges"], w[1]) for k, w in zip(("red", "green", "blue"), want_rgb))
+        got = M.error_overlays(x, prob, gt)
+        assert all(np.array_equal(got[k], want_err[k], equal_nan=True) for k in want_err)
+        del got, want_err, want_overlay
+        table = torch.from_numpy(M.overlay_table()).to(DEV)
+        out = torch.empty_like(d_img)
+        stats = torch.empty(8, device=DEV, dtype=torch.int64)
+        edges = torch.from_numpy(np.stack([w[1] for w in want_hist])).to(DEV)
+        counts = torch.empty((2, 50), device=DEV, dtype=torch.int64)
+        hist = torch.empty((3, 256), device=DEV, dtype=torch.int64)
+        d_x, d_prob, d_gt = (torch.from_numpy(a).to(DEV) for a in (x, prob, gt))
+        colours = torch.from_numpy(M.class_colour_terms()).to(DEV)
+        vis, ov = torch.empty((1, size, size, 3), device=DEV), torch.empty((1, size, size, 3), device=DEV, dtype=torch.float64)
+        err, cls, sums = torch.empty((1, size, size), device=DEV), torch.empty((1, 5), device=DEV, dtype=torch.int64), torch.empty(1, device=DEV, dtype=torch.float64)
+        nws = lib.runet_error_overlays_workspace_bytes(1, size, size)
+        ws = torch.empty(nws // 8, device=DEV, dtype=torch.float64)
+        m, sd = data.IMAGENET_MEAN, data.IMAGENET_STD
+        st = None
+        kernels = [
+            ("combined_overlay", "combined_overlay", 8 * n,
+             lambda: lib.runet_report_overlay_u8(d_img.data_ptr(), d_water.data_ptr(), d_coast.data_ptr(), size, size, table.data_ptr(), out.data_ptr(), st)),
+            ("ndwi pass 1 (index, min, max)", "ndwi pass 1 (index, min, max)", 5 * n,
+             lambda: lib.runet_ndwi_stats(*r.args, d_water.data_ptr(), stats.data_ptr(), st)),
+            ("ndwi pass 2 (binning)", "ndwi pass 2 (binning)", 5 * n,
+             lambda: lib.runet_ndwi_hist(*r.args, d_water.data_ptr(), edges.data_ptr(), 50, counts.data_ptr(), st)),
+            ("rgb histogram", "rgb histogram", 3 * n, lambda: lib.runet_rgb_hist_u8(d_img.data_ptr(), size, size, hist.data_ptr(), st)),
+            ("error_overlays", "error_overlays", 60 * n,
+             lambda: lib.runet_error_overlays(d_x.data_ptr(), d_prob.data_ptr(), d_gt.data_ptr(), 1, size, size, 0.5, m[0], m[1], m[2], sd[0], sd[1], sd[2],
+                                              colours.data_ptr(), vis.data_ptr(), ov.data_ptr(), err.data_ptr(), cls.data_ptr(), sums.data_ptr(),
+                                              ws.data_ptr(), nws, st)),
+        ]
+        for name, key, nbytes, fn in kernels:
+            (t,), (calls,) = windows((fn,), window_s)
+            rows.append({"size": size, "kernel": name, "hip_us": round(t * 1e6, 2), "bytes_min": nbytes, "hip_GBps": round(nbytes / t * 1e-9, 1),
+                         "numpy_ms": round(t_np[key] * 1e3, 3), "numpy_over_hip": round(t_np[key] / t, 1), "calls": calls})
+            say(f"  {size:5d}^2  {name:32s} HIP {t * 1e6:10.2f} us  {nbytes / t * 1e-9:8.1f} GB/s ({nbytes / n} B/pixel)   numpy {t_np[key] * 1e3:10.2f} ms"
+                f"   numpy / HIP = {t_np[key] / t:8.1f}   ({calls} calls)")
+        del d_x, d_prob, d_gt, vis, ov, err, ws
+    return {"kernels": rows, "end_to_end": e2e}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", default="all", choices=("all", "path", "kernels", "contours", "simplify"))
+    ap.add_argument("--what", default="all", choices=("all", "path", "kernels", "contours", "simplify", "report"),
+                    help="report is not part of all: its numpy side takes minutes at 10980^2")
     ap.add_argument("--model", default="unet", choices=sorted(MODELS), help="the model of the whole-prediction lines; any but unet also "
                     "times the two kernels of the probability route")
     ap.add_argument("--host-budget", type=float, default=20.0, help="seconds one host tracing run may take before it moves to a 2048^2 crop")
@@ -426,6 +538,9 @@ def main():
         say("polygon simplification (csrc/simplify.hip, the exact rule, against the host float64 rule and the exact rule's host restatement on "
             "the same traced contours; eps factor 0.002, contours of more than 10 vertices; device and host lists of the exact rule checked equal):")
         res["simplify"] = simplify_rows((512, 2048, 10980), a.host_budget)
+    if a.what == "report":
+        say("report arrays (HIP = csrc/report.hip, device events; numpy = the operations of tests/report_ref.py on this host, np.histogram once per selection or channel, one run; results checked equal first):")
+        res["report"] = report_rows((512, 2048, 10980), a.window)
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(LINES) + "\n")
