@@ -6,20 +6,21 @@
 //
 // * `wino_weight_kernel` transforms the HWIO weight once per use into U[16][K/4][N][4] (forward: K = cin, N = cout; data
 //   gradient: the 180-degree rotated filter with K = cout, N = cin).
-// * `wino_conv_kernel`: one block = 32 tiles (one 32-row MFMA tile) x 64 output channels.  Per 16-channel chunk every thread
-//   loads the 4x4 patch of one (tile, channel pair) straight from NHWC global memory (8 lanes cover the 64 contiguous bytes
-//   of a pixel), applies B^T d B in registers and writes the 16 transformed values to LDS as V[xi][tile][k]; after a barrier
-//   wave w multiplies positions xi = 4w..4w+3 : [32 tiles x 16 k] x [16 k x 64 n] with v_mfma_f32_32x32x2_f32, the U
-//   fragments coming straight from global/L2 (each wave needs different positions, so LDS staging would buy no reuse).
-//   Default multiply stage (M16): v_mfma_f32_16x16x4_f32, wave w owns 16 of the 64 output channels for all 16 positions, so
-//   the 16 position-products of a (tile, channel) sit in one lane and A^T m A runs in registers.  The earlier form (M16 = false,
-//   RUNET_WINO_ABL=32) splits the positions over the waves and exchanges them through LDS in four 16-channel passes.
+// * `wino_conv_kernel`: one block = 32 tiles (a 4 x 8 patch of 2x2 tiles) x 64 output channels.  Per 16-channel chunk the block loads the
+//   10 x 18 input halo of its patch from NHWC global memory into LDS; every thread applies B^T d B to the 4x4 patch of one (tile, channel
+//   pair) in registers and writes the 16 transformed values to LDS as V[xi][tile][k]; after a barrier the multiply stage runs
+//   [32 tiles x 16 k] x [16 k x 64 n] per position with v_mfma_f32_16x16x4_f32, the U fragments coming straight from global/L2.  Wave w
+//   owns 16 of the 64 output channels for all 16 positions, so the 16 position-products of a (tile, channel) sit in one lane and
+//   A^T m A runs in registers.  Block order, tile constants, patch decode and B^T d B are shared with the split-operand kernel of
+//   conv_winograd_x3.hip (wino2_common.h).
 // Algorithmic FLOPs are counted as the direct convolution's (2*9*Cin*Cout per pixel); the MFMA work is 16/36 of that.
-#include "runet_common.h"
+#include "wino2_common.h"
 #include "../../include/runet_hip.h"
 #include <stdlib.h>
 
 namespace {
+
+using namespace wino2;
 
 struct WinoArgs {
     const float* x; int ldx;      // [Nimg, H, W, ldx], K channels
@@ -33,44 +34,22 @@ struct WinoArgs {
     int npatches, nchunks;        // grid = npatches * nchunks blocks (4x8-tile patches x 64-channel output chunks)
 };
 
-constexpr int WT = 32;            // tiles per block
-constexpr int WBN = 64;           // output channels per block
 constexpr int VLD = 20;           // padded k-stride of a V row (conflict-free ds_read_b128)
-constexpr int RH = 10, RW = 18;   // input halo of a 4x8 patch of 2x2 tiles
-constexpr int RPS = 24;           // floats per halo pixel in LDS (16 channels + pad: conflict-free ds_read_b64 in the transform)
 
-// M16 = true: the multiply stage uses v_mfma_f32_16x16x4_f32 and wave w owns output channels [16w, 16w+16) of the block for ALL 16
-// positions (32 accumulator tiles of 4 registers).  A lane then holds the 16 position-products of its (tile, channel) items, so the
-// output transform runs in registers - no exchange through LDS, no barriers in the epilogue - at the price of every wave reading the
-// whole V tile (4x the LDS fragment reads of the 32x32x2 form, where a wave reads only its 4 positions).
-template <int ABL, bool M16>
+// The multiply stage uses v_mfma_f32_16x16x4_f32 and wave w owns output channels [16w, 16w+16) of the block for ALL 16 positions (32
+// accumulator tiles of 4 registers).  A lane then holds the 16 position-products of its (tile, channel) items, so the output transform
+// runs in registers - no exchange through LDS, no barriers in the epilogue - at the price of every wave reading the whole V tile.
 __global__ __launch_bounds__(256, 2) void wino_conv_kernel(WinoArgs g) {
-    __shared__ __attribute__((aligned(16))) float V[16 * WT * VLD];       // 40 KB; reused as M[16][32][16] in the epilogue
+    __shared__ __attribute__((aligned(16))) float V[16 * WT * VLD];       // 40 KB
     __shared__ __attribute__((aligned(16))) float R[RH * RW * RPS];       // 17 KB raw input halo of the current 16-channel chunk
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: U offsets stay in SGPRs
-    const int li = lane & 31, lh = lane >> 5;
-    // 1-D grid.  Blocks that share an input patch (same patch, different output-channel chunk) get ids 8 apart: consecutive ids are
-    // dealt to the 8 XCDs round-robin, so they run at the same time on the SAME XCD and the halo is fetched into one L2 once.
-    int bpatch, bchunk;
-    {
-        const int L = blockIdx.x, nch = g.nchunks, span = 8 * nch;
-        const int grp = L / span, r = L - grp * span;
-        bpatch = grp * 8 + (r & 7);
-        bchunk = r >> 3;
-        if (grp * 8 + 8 > g.npatches) {      // tail group (npatches not a multiple of 8): plain order over what is left
-            const int done = grp * 8, rem = g.npatches - done;
-            bpatch = done + r % rem;
-            bchunk = r / rem;
-        }
-    }
+    int bpatch, bchunk;           // blocks that share an input patch get ids 8 apart: same XCD, the halo is fetched into one L2 once
+    xcd_order(blockIdx.x, g.npatches, g.nchunks, bpatch, bchunk);
     const int n0 = bchunk * WBN;
 
-    // block -> (image, 4x8 patch of tiles): 8x16 output pixels, 10x18 input halo shared by the 32 tiles through LDS
-    const int bxs = (g.TX + 7) >> 3, bys = (g.TY + 3) >> 2;
-    const int bimg = bpatch / (bxs * bys);
-    const int brem = bpatch - bimg * (bxs * bys);
-    const int by = brem / bxs, bx = brem - by * bxs;
+    const Patch pt = patch_of(bpatch, g.TY, g.TX);
+    const int bimg = pt.img, by = pt.by, bx = pt.bx;
     const int h00 = 8 * by - 1, w00 = 16 * bx - 1;                // image coordinates of halo pixel (0,0)
 
     // Every global read is UNCONDITIONAL (a masked lane reads element 0 and the value is then zeroed): no branches around
@@ -94,10 +73,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(WinoArgs g) {
     auto load_halo = [&](int c0) {
         const float* xc = g.x + c0;            // wave-uniform
 #pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            if constexpr (ABL & 1) hreg[v] = f32x4{(float)c0, 1.f, 2.f, 3.f};
-            else hreg[v] = *reinterpret_cast<const f32x4*>(xc + hoff[v]);
-        }
+        for (int v = 0; v < 3; ++v) hreg[v] = *reinterpret_cast<const f32x4*>(xc + hoff[v]);
     };
     auto store_halo = [&]() {
 #pragma unroll
@@ -108,38 +84,8 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(WinoArgs g) {
     // ---- transform role: (tile lt, channel pair k2); the wave's 8 tiles are one row of the 4x8 patch ----
     const int lt = tid >> 3, k2 = tid & 7;
     const int rbase = ((2 * (lt >> 3)) * RW + 2 * (lt & 7)) * RPS + 2 * k2;      // halo pixel (0,0) of this tile's 4x4 patch
-    auto transform_store = [&]() {
-        // B^T d B on both channels; V[xi][lt][2*k2 .. 2*k2+1]
-        float2 raw[16], tmp[16];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) raw[a * 4 + b] = *reinterpret_cast<const float2*>(&R[rbase + (a * RW + b) * RPS]);
-        if constexpr (ABL & 2) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) *reinterpret_cast<float2*>(&V[(i * WT + lt) * VLD + 2 * k2]) = raw[i];
-            return;
-        }
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const float2 d0 = raw[b], d1 = raw[4 + b], d2 = raw[8 + b], d3 = raw[12 + b];
-            tmp[b] = make_float2(d0.x - d2.x, d0.y - d2.y);
-            tmp[4 + b] = make_float2(d1.x + d2.x, d1.y + d2.y);
-            tmp[8 + b] = make_float2(d2.x - d1.x, d2.y - d1.y);
-            tmp[12 + b] = make_float2(d1.x - d3.x, d1.y - d3.y);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const float2 v0 = tmp[a * 4], v1 = tmp[a * 4 + 1], v2 = tmp[a * 4 + 2], v3 = tmp[a * 4 + 3];
-            float2 o[4];
-            o[0] = make_float2(v0.x - v2.x, v0.y - v2.y);
-            o[1] = make_float2(v1.x + v2.x, v1.y + v2.y);
-            o[2] = make_float2(v2.x - v1.x, v2.y - v1.y);
-            o[3] = make_float2(v1.x - v3.x, v1.y - v3.y);
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                *reinterpret_cast<float2*>(&V[((a * 4 + b) * WT + lt) * VLD + 2 * k2]) = o[b];
-        }
+    auto transform_store = [&]() {      // B^T d B on both channels; V[xi][lt][2*k2 .. 2*k2+1]
+        input_transform(R, rbase, [&](int xi, const float2 v) { *reinterpret_cast<float2*>(&V[(xi * WT + lt) * VLD + 2 * k2]) = v; });
     };
 
     // U is stored [16][K/4][N][4]: lane (j, h) reads ONE float4 = the 4 consecutive k it feeds to 4 MFMAs
@@ -147,204 +93,77 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(WinoArgs g) {
     const f32x4* U4 = reinterpret_cast<const f32x4*>(g.U);
     const int nchunks = g.K >> 4;
 
-    if constexpr (M16) {
-        const int l16 = lane & 15, kq = lane >> 4;
-        const int ncol = n0 + wid * 16 + l16;
-        const int uo = (ncol < g.N) ? kq * g.N + wid * 16 + l16 : 0;      // column >= N: reads element 0, result never stored
-        f32x4 acc16[16][2];
+    const int l16 = lane & 15, kq = lane >> 4;
+    const int ncol = n0 + wid * 16 + l16;
+    const int uo = (ncol < g.N) ? kq * g.N + wid * 16 + l16 : 0;      // column >= N: reads element 0, result never stored
+    f32x4 acc16[16][2];
 #pragma unroll
-        for (int xi = 0; xi < 16; ++xi)
+    for (int xi = 0; xi < 16; ++xi)
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) acc16[xi][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 ring16[8];          // filter fragment of step t (= position t of the chunk) lives in slot t & 7, loaded 6 steps ahead
-        auto load16 = [&](int xi, int c0, f32x4& slot) { slot = U4[((long)(xi * K4 + (c0 >> 2)) * g.N + n0) + uo]; };
-        auto read_a16 = [&](int xi, f32x4 (&a)[2]) {
+        for (int mb = 0; mb < 2; ++mb) acc16[xi][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 ring16[8];          // filter fragment of step t (= position t of the chunk) lives in slot t & 7, loaded 6 steps ahead
+    auto load16 = [&](int xi, int c0, f32x4& slot) { slot = U4[((long)(xi * K4 + (c0 >> 2)) * g.N + n0) + uo]; };
+    auto read_a16 = [&](int xi, f32x4 (&a)[2]) {
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) a[mb] = *reinterpret_cast<const f32x4*>(&V[(xi * WT + mb * 16 + l16) * VLD + 4 * kq]);
-        };
-        load_halo(0);
-#pragma unroll
-        for (int t = 0; t < 6; ++t) load16(t, 0, ring16[t]);
-        for (int ch = 0; ch < nchunks; ++ch) {
-            const int c0 = ch * 16;
-            const int cn = (ch + 1 < nchunks) ? c0 + 16 : c0;
-            store_halo();
-            __syncthreads();
-            transform_store();
-            __syncthreads();
-            f32x4 af[2][2];
-            read_a16(0, af[0]);
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                if (t + 6 < 16) load16(t + 6, c0, ring16[(t + 6) & 7]);
-                else load16(t + 6 - 16, cn, ring16[(t + 6) & 7]);
-                if (t == 1) load_halo(cn);
-                if (t + 1 < 16) read_a16(t + 1, af[(t + 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb)
-                        acc16[t][mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[t & 1][mb][j], ring16[t & 7][j], acc16[t][mb], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // epilogue in registers: lane = (channel ncol, tiles mb*16 + 4*kq + r)
-        float bv = 0.f;
-        if (g.bias && ncol < g.N) bv = g.bias[ncol];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int tile = mb * 16 + 4 * kq + r;
-                const int e_ty = 4 * by + (tile >> 3), e_tx = 8 * bx + (tile & 7);
-                if (e_ty < g.TY && e_tx < g.TX && ncol < g.N) {
-                    float m[16];
-#pragma unroll
-                    for (int xi = 0; xi < 16; ++xi) m[xi] = acc16[xi][mb][r];
-                    float sA[2][4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        sA[0][j] = m[j] + m[4 + j] + m[8 + j];
-                        sA[1][j] = m[4 + j] - m[8 + j] - m[12 + j];
-                    }
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        float o0 = sA[i][0] + sA[i][1] + sA[i][2] + bv;
-                        float o1 = sA[i][1] - sA[i][2] - sA[i][3] + bv;
-                        float* d0 = g.y + (((long)bimg * g.H + 2 * e_ty + i) * g.W + 2 * e_tx) * g.ldy + ncol;
-                        if (g.accumulate) { o0 += d0[0]; o1 += d0[g.ldy]; }
-                        d0[0] = o0;
-                        d0[g.ldy] = o1;
-                    }
-                }
-            }
-        return;
-    }
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][b][r] = 0.f;
-
-    int uoff[2];              // columns n >= N read element 0 instead: their products land in output columns that are never stored
-#pragma unroll
-    for (int b = 0; b < 2; ++b) uoff[b] = (n0 + b * 32 + li < g.N) ? lh * g.N + b * 32 + li : 0;
-    // U fragments travel through a ring of four half-position slots (one slot = the two float4 of one (position, k-half)):
-    // the load for step t+3 is issued in front of step t's 8 MFMAs, i.e. every fragment has ~1500 MFMA cycles to arrive,
-    // with the same 32 registers a plain double buffer of whole positions would use.
-    f32x4 ring[4][2];
-    auto load_step = [&](int t, int c0, f32x4 (&slot)[2]) {
-        const int xl = t >> 1, kh = t & 1;
-        const f32x4* up = U4 + ((long)((wid * 4 + xl) * K4 + (c0 >> 2) + kh * 2) * g.N + n0);      // wave-uniform
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            if constexpr (ABL & 4) slot[b] = f32x4{1.f, 2.f, 3.f, (float)c0};
-            else slot[b] = up[uoff[b]];
-        }
+        for (int mb = 0; mb < 2; ++mb) a[mb] = *reinterpret_cast<const f32x4*>(&V[(xi * WT + mb * 16 + l16) * VLD + 4 * kq]);
     };
-    // the A fragment (one ds_read_b128) of step t+1 is read in front of step t's MFMAs: only the first read after the barrier is exposed
-    auto read_a = [&](int t) {
-        const int xl = t >> 1, kh = t & 1;
-        return *reinterpret_cast<const f32x4*>(&V[((wid * 4 + xl) * WT + li) * VLD + kh * 8 + 4 * lh]);
-    };
-    auto mma_step = [&](int t, const f32x4 a, const f32x4 (&slot)[2]) {
-        const int xl = t >> 1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc[xl][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], slot[b][q], acc[xl][b], 0, 0, 0);
-    };
-
     load_halo(0);
-    load_step(0, 0, ring[0]);
-    load_step(1, 0, ring[1]);
-    load_step(2, 0, ring[2]);
+#pragma unroll
+    for (int t = 0; t < 6; ++t) load16(t, 0, ring16[t]);
     for (int ch = 0; ch < nchunks; ++ch) {
         const int c0 = ch * 16;
-        const int cn = (ch + 1 < nchunks) ? c0 + 16 : c0;      // last chunk: harmless re-read, keeps the code branch-free
-        store_halo();                          // R was last read before the previous chunk's second barrier
-        __syncthreads();                       // R complete; previous chunk's MFMA reads of V are done
+        const int cn = (ch + 1 < nchunks) ? c0 + 16 : c0;
+        store_halo();
+        __syncthreads();
         transform_store();
         __syncthreads();
-        // the sched_barriers pin each load group in FRONT of the MFMAs it overlaps (the scheduler otherwise sinks loads to the
-        // end of the region, right in front of their first use)
-        f32x4 afrag[2];
-        afrag[0] = read_a(0);
+        f32x4 af[2][2];
+        read_a16(0, af[0]);
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (t + 3 < 8) load_step(t + 3, c0, ring[(t + 3) & 3]);
-            else load_step(t + 3 - 8, cn, ring[(t + 3) & 3]);          // first steps of the NEXT chunk, in flight across the barriers
-            if (t == 1) load_halo(cn);                                 // next chunk's halo: in flight during the rest of the MFMAs
-            if (t + 1 < 8) afrag[(t + 1) & 1] = read_a(t + 1);
+        for (int t = 0; t < 16; ++t) {
+            if (t + 6 < 16) load16(t + 6, c0, ring16[(t + 6) & 7]);
+            else load16(t + 6 - 16, cn, ring16[(t + 6) & 7]);
+            if (t == 1) load_halo(cn);
+            if (t + 1 < 16) read_a16(t + 1, af[(t + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
-            mma_step(t, afrag[t & 1], ring[t & 3]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+                    acc16[t][mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[t & 1][mb][j], ring16[t & 7][j], acc16[t][mb], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-
-    // ---- epilogue: exchange the 16 positions through LDS (16 output channels per pass), A^T m A, store ----
-    if constexpr (ABL & 8) {
+    // epilogue in registers: lane = (channel ncol, tiles mb*16 + 4*kq + r)
+    float bv = 0.f;
+    if (g.bias && ncol < g.N) bv = g.bias[ncol];
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+    for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) asm volatile("" :: "v"(acc[i][b]));
-        return;
-    }
-    float* M = V;                               // M[xi][t][16]
-    const int et = tid >> 3;                    // tile of the two (tile, channel) items this thread finishes
-    const int en = (tid & 7) * 2;               // channels en, en+1 of the pass
-    const int e_ty = 4 * by + (et >> 3), e_tx = 8 * bx + (et & 7);
-    const bool e_ok = e_ty < g.TY && e_tx < g.TX;
-    const int e_n = bimg, e_h = 2 * e_ty, e_w = 2 * e_tx;
+        for (int r = 0; r < 4; ++r) {
+            const int tile = mb * 16 + 4 * kq + r;
+            const int e_ty = 4 * by + (tile >> 3), e_tx = 8 * bx + (tile & 7);
+            if (e_ty < g.TY && e_tx < g.TX && ncol < g.N) {
+                float m[16];
 #pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        __syncthreads();
-        const int b = pass >> 1;                // which 32-wide N tile
-        if ((li >> 4) == (pass & 1)) {          // lanes whose column falls into this 16-channel pass
+                for (int xi = 0; xi < 16; ++xi) m[xi] = acc16[xi][mb][r];
+                float sA[2][4];
 #pragma unroll
-            for (int xl = 0; xl < 4; ++xl)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int t = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    M[((wid * 4 + xl) * WT + t) * 16 + (li & 15)] = acc[xl][b][r];
+                for (int j = 0; j < 4; ++j) {
+                    sA[0][j] = m[j] + m[4 + j] + m[8 + j];
+                    sA[1][j] = m[4 + j] - m[8 + j] - m[12 + j];
                 }
-        }
-        __syncthreads();
-        if (e_ok) {
-            float2 m[16];
-#pragma unroll
-            for (int xi = 0; xi < 16; ++xi) m[xi] = *reinterpret_cast<const float2*>(&M[(xi * WT + et) * 16 + en]);
-            // A^T m A : rows [1,1,1,0],[0,1,-1,-1]
-            float2 s[2][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s[0][j] = make_float2(m[j].x + m[4 + j].x + m[8 + j].x, m[j].y + m[4 + j].y + m[8 + j].y);
-                s[1][j] = make_float2(m[4 + j].x - m[8 + j].x - m[12 + j].x, m[4 + j].y - m[8 + j].y - m[12 + j].y);
-            }
-            const int nch = n0 + pass * 16 + en;
-            if (nch < g.N) {
-                float2 bv = make_float2(0.f, 0.f);
-                if (g.bias) bv = *reinterpret_cast<const float2*>(g.bias + nch);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    float2 o0 = make_float2(s[i][0].x + s[i][1].x + s[i][2].x + bv.x, s[i][0].y + s[i][1].y + s[i][2].y + bv.y);
-                    float2 o1 = make_float2(s[i][1].x - s[i][2].x - s[i][3].x + bv.x, s[i][1].y - s[i][2].y - s[i][3].y + bv.y);
-                    float* d0 = g.y + (((long)e_n * g.H + e_h + i) * g.W + e_w) * g.ldy + nch;
-                    float* d1 = d0 + g.ldy;
-                    if (g.accumulate) {
-                        const float2 p0 = *reinterpret_cast<const float2*>(d0), p1 = *reinterpret_cast<const float2*>(d1);
-                        o0.x += p0.x; o0.y += p0.y; o1.x += p1.x; o1.y += p1.y;
-                    }
-                    *reinterpret_cast<float2*>(d0) = o0;
-                    *reinterpret_cast<float2*>(d1) = o1;
+                    float o0 = sA[i][0] + sA[i][1] + sA[i][2] + bv;
+                    float o1 = sA[i][1] - sA[i][2] - sA[i][3] + bv;
+                    float* d0 = g.y + (((long)bimg * g.H + 2 * e_ty + i) * g.W + 2 * e_tx) * g.ldy + ncol;
+                    if (g.accumulate) { o0 += d0[0]; o1 += d0[g.ldy]; }
+                    d0[0] = o0;
+                    d0[g.ldy] = o1;
                 }
             }
         }
-    }
 }
 
 // U[xi][k][n] = (G g G^T)[xi] ;  forward: g[r][s] = w[r][s][k][n] ;  dgrad: g[r][s] = w[2-r][2-s][n][k]  (w is [3][3][cin][cout])
@@ -407,17 +226,7 @@ __global__ __launch_bounds__(256, 2) void wino_wgrad_kernel(WinoWgradArgs g) {
     // 1-D grid, XCD-aware: the (cin-chunk, cout-chunk) blocks of one tile range get ids 8 apart -> same XCD, same time: x and dy of the
     // range go through one L2 (PMC: 1.2 GB of HBM traffic per launch against 0.54-0.8 GB algorithmic with the plain order)
     int bsplit, bchunk;
-    {
-        const int L = blockIdx.x, nch = g.nchunks, span = 8 * nch;
-        const int grp = L / span, r = L - grp * span;
-        bsplit = grp * 8 + (r & 7);
-        bchunk = r >> 3;
-        if (grp * 8 + 8 > g.nsplits) {
-            const int done = grp * 8, rem = g.nsplits - done;
-            bsplit = done + r % rem;
-            bchunk = r / rem;
-        }
-    }
+    xcd_order(blockIdx.x, g.nsplits, g.nchunks, bsplit, bchunk);
     const int ci0 = (bchunk / g.co_chunks) * GCI, co0 = (bchunk % g.co_chunks) * GCO;
     const long t_begin = (long)bsplit * g.tiles_per_split;
     const long t_end = t_begin + g.tiles_per_split < g.tiles ? t_begin + g.tiles_per_split : g.tiles;
@@ -576,11 +385,11 @@ struct WinoWgradDirectArgs {
     int ci_chunks, co_chunks, nchunks, nsplits;
     long tiles, tiles_per_split;  // tiles_per_split even
     long x_bytes, dy_bytes;       // extents for the bounds-checked buffer loads (< 2^31)
-    int abl;                      // timing ablations (wrong results): 1 = x loads dropped by the range check, 2 = dy loads, 3 = both
 };
 
-// PH: position half (rows 2*PH, 2*PH + 1 of the position grid).  CABL: compile-time timing ablations (4: no loads, 8: no MFMA).
-template <int PH, int CABL, bool ZIG = (CABL & 16) != 0>
+// PH: position half (rows 2*PH, 2*PH + 1 of the position grid).  ZIG: zig-zag tile order (needs an even number of tile rows AND of tile
+// columns), else row-major.
+template <int PH, bool ZIG>
 __device__ __forceinline__ void wino_wgrad_direct_body(const WinoWgradDirectArgs& g, int bsplit, int bchunk, int sub, int lane) {
     const int li = lane & 31, lh = lane >> 5;
     const int wco = 4 / g.wci;
@@ -635,7 +444,7 @@ __device__ __forceinline__ void wino_wgrad_direct_body(const WinoWgradDirectArgs
     // SIMD cycles (a step costs matrix time PLUS 4 cycles per VALU instruction, measured), so every v_add removed here is matrix time.
     auto load = [&](float (&rx)[12], float (&ry)[4], const int par) {
         const bool tv = tg < t_end_i;
-        const unsigned ox = (tv && ca_ok && !(g.abl & 1)) ? offx : BIG, oy = (tv && cb_ok && !(g.abl & 2)) ? offy : BIG;
+        const unsigned ox = (tv && ca_ok) ? offx : BIG, oy = (tv && cb_ok) ? offy : BIG;
         // Patch rows PH, PH+1, PH+2 (patch row 1 = pixel row 2ty): the first (PH = 0) or the last (PH = 1) of them may lie outside the
         // image, as may patch columns 0 and 3.  Vector offsets never go below zero (the range check sees voffset alone): rows / columns in
         // front of the origin subtract in the VALU and are only formed where they exist.
@@ -644,27 +453,20 @@ __device__ __forceinline__ void wino_wgrad_direct_body(const WinoWgradDirectArgs
         const unsigned oe = edge_ok ? (PH == 0 ? ox - rowx4 : ox) : BIG;            // origin of the edge row (PH = 0: row 0, scalar part 0; PH = 1: row 3)
         const unsigned ox_l = left ? ox - ldx4 : BIG, ox_r = right ? ox : BIG;
         const unsigned oe_l = (left && edge_ok) ? oe - ldx4 : BIG, oe_r = right ? oe : BIG;
-        if constexpr (CABL & 4) {                       // timing ablation: no load instructions at all
 #pragma unroll
-            for (int i = 0; i < 12; ++i) rx[i] = __builtin_bit_cast(float, (i & 1 ? ox_l : oe_r) + (i & 2 ? oe_l : ox_r) + (unsigned)i);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ry[i] = __builtin_bit_cast(float, oy + i);
-        } else {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const bool e = (PH == 0 && a == 0) || (PH == 1 && a == 2);
-                // scalar part of patch row PH + a relative to its vector origin: PH = 0: rows 0,1,2 -> 0 (own origin), 0, rowx4; PH = 1: rows 1,2,3 -> 0, rowx4, 2 rowx4
-                const unsigned so = PH == 0 ? (a == 2 ? rowx4 : 0u) : (unsigned)a * rowx4;
-                rx[a * 4 + 0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe_l : ox_l, so, 0));
-                rx[a * 4 + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe : ox, so, 0));
-                rx[a * 4 + 2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe : ox, so + ldx4, 0));
-                rx[a * 4 + 3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe_r : ox_r, so + 2 * ldx4, 0));
-            }
-            ry[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, 0, 0));
-            ry[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, ldy4, 0));
-            ry[2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, rowy4, 0));
-            ry[3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, rowy4 + ldy4, 0));
+        for (int a = 0; a < 3; ++a) {
+            const bool e = (PH == 0 && a == 0) || (PH == 1 && a == 2);
+            // scalar part of patch row PH + a relative to its vector origin: PH = 0: rows 0,1,2 -> 0 (own origin), 0, rowx4; PH = 1: rows 1,2,3 -> 0, rowx4, 2 rowx4
+            const unsigned so = PH == 0 ? (a == 2 ? rowx4 : 0u) : (unsigned)a * rowx4;
+            rx[a * 4 + 0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe_l : ox_l, so, 0));
+            rx[a * 4 + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe : ox, so, 0));
+            rx[a * 4 + 2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe : ox, so + ldx4, 0));
+            rx[a * 4 + 3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx_, e ? oe_r : ox_r, so + 2 * ldx4, 0));
         }
+        ry[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, 0, 0));
+        ry[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, ldy4, 0));
+        ry[2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, rowy4, 0));
+        ry[3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry_, oy, rowy4 + ldy4, 0));
         // advance by two tiles (TX >= 2: at most one wrap); branch-free, the loop body stays one basic block
         tg += 2;
         if constexpr (ZIG) {
@@ -724,10 +526,8 @@ __device__ __forceinline__ void wino_wgrad_direct_body(const WinoWgradDirectArgs
         transform(raw_x[(cur + 1) % 3], raw_y[(cur + 1) % 3], op_v[(cur + 1) & 1], op_z[(cur + 1) & 1]);
         load(raw_x[cur % 3], raw_y[cur % 3], (cur + 1) & 1);
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            if constexpr (CABL & 8) acc[p][0] += op_v[cur & 1][p] * op_z[cur & 1][p];      // timing ablation: no MFMA
-            else acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(op_v[cur & 1][p], op_z[cur & 1][p], acc[p], 0, 0, 0);
-        }
+        for (int p = 0; p < 8; ++p)
+            acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(op_v[cur & 1][p], op_z[cur & 1][p], acc[p], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     };
 
@@ -758,25 +558,15 @@ __device__ __forceinline__ void wino_wgrad_direct_body(const WinoWgradDirectArgs
     }
 }
 
-template <int CABL>
+template <bool ZIG>
 __global__ __launch_bounds__(512) void wino_wgrad_direct_kernel(WinoWgradDirectArgs g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bsplit, bchunk;
-    {   // XCD-aware order (see wino_wgrad_kernel): the chunks of one tile range sit on one XCD
-        const int L = blockIdx.x, nch = g.nchunks, span = 8 * nch;
-        const int grp = L / span, r = L - grp * span;
-        bsplit = grp * 8 + (r & 7);
-        bchunk = r >> 3;
-        if (grp * 8 + 8 > g.nsplits) {
-            const int done = grp * 8, rem = g.nsplits - done;
-            bsplit = done + r % rem;
-            bchunk = r / rem;
-        }
-    }
+    int bsplit, bchunk;           // XCD-aware order (see wino_wgrad_kernel): the chunks of one tile range sit on one XCD
+    xcd_order(blockIdx.x, g.nsplits, g.nchunks, bsplit, bchunk);
     // waves 2k, 2k+1 (position halves of channel block k) sit on different SIMDs; wave w and w + 4 share a SIMD: another channel block
-    if (wid & 1) wino_wgrad_direct_body<1, CABL>(g, bsplit, bchunk, wid >> 1, lane);
-    else wino_wgrad_direct_body<0, CABL>(g, bsplit, bchunk, wid >> 1, lane);
+    if (wid & 1) wino_wgrad_direct_body<1, ZIG>(g, bsplit, bchunk, wid >> 1, lane);
+    else wino_wgrad_direct_body<0, ZIG>(g, bsplit, bchunk, wid >> 1, lane);
 }
 
 // dw[r][s][ci][co] = (G^T (sum_splits slab) G)[r][s];  block = 32 (ci,co) columns x 8 split-lanes
@@ -826,7 +616,7 @@ static bool wino_wgrad_direct(int n_img, int h, int w, long ldx, long ldy) {
     const long px = (long)n_img * h * w;
     return !lds_form && w >= 4 && px * ldx * 4 < (1L << 31) && px * ldy * 4 < (1L << 31) && px / 4 + 64 < (1L << 31);
 }
-static bool wino_wgrad_rowmajor() {      // measurement knob: RUNET_WINO_WGRAD_ROWMAJOR=1 -> the row-major tile order of round 2
+static bool wino_wgrad_rowmajor() {      // RUNET_WINO_WGRAD_ROWMAJOR=1: the row-major instance (the path of odd tile counts) for every shape
     static const bool v = getenv("RUNET_WINO_WGRAD_ROWMAJOR") && atoi(getenv("RUNET_WINO_WGRAD_ROWMAJOR")) != 0;
     return v;
 }
@@ -887,18 +677,7 @@ extern "C" int runet_wino_conv(const float* x, int ldx, const float* U, const fl
     a.Nimg = n_img; a.H = h; a.W = w; a.TY = h / 2; a.TX = w / 2; a.tiles = (long)n_img * a.TY * a.TX; a.accumulate = accumulate;
     a.npatches = n_img * cdiv(a.TY, 4) * cdiv(a.TX, 8);
     a.nchunks = cdiv(n, WBN);
-    dim3 grid(a.npatches * a.nchunks);
-    static const int abl = getenv("RUNET_WINO_ABL") ? atoi(getenv("RUNET_WINO_ABL")) : 0;      // timing ablations only (wrong results)
-    switch (abl) {
-    case 1: hipLaunchKernelGGL((wino_conv_kernel<1, false>), grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 2: hipLaunchKernelGGL((wino_conv_kernel<2, false>), grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 4: hipLaunchKernelGGL((wino_conv_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 8: hipLaunchKernelGGL((wino_conv_kernel<8, false>), grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 7: hipLaunchKernelGGL((wino_conv_kernel<7, false>), grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 15: hipLaunchKernelGGL((wino_conv_kernel<15, false>), grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 32: hipLaunchKernelGGL((wino_conv_kernel<0, false>), grid, dim3(256), 0, (hipStream_t)stream, a); break;     // 32x32x2 form with the LDS exchange
-    default: hipLaunchKernelGGL((wino_conv_kernel<0, true>), grid, dim3(256), 0, (hipStream_t)stream, a);             // 16x16x4 form: 6-10 % faster on the 64/128-channel layers
-    }
+    hipLaunchKernelGGL(wino_conv_kernel, dim3(a.npatches * a.nchunks), dim3(256), 0, (hipStream_t)stream, a);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -916,23 +695,21 @@ extern "C" int runet_wino_wgrad(const float* x, int ldx, const float* dy, int ld
     const WinoWgradPlan p = wino_wgrad_plan(n_img, h, w, cin, cout, direct);
     RUNET_REQUIRE(workspace_floats >= (long)p.splits * 16 * cin * cout, "workspace too small (runet_wino_wgrad_workspace_floats)");
     hipStream_t st = (hipStream_t)stream;
-    WinoWgradArgs a{};
-    a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy; a.slabs = workspace; a.cin = cin; a.cout = cout; a.Nimg = n_img; a.H = h; a.W = w;
-    a.TY = h / 2; a.TX = w / 2; a.co_chunks = p.co_chunks; a.tiles = p.tiles; a.tiles_per_split = p.tps;
-    a.nchunks = p.ci_chunks * p.co_chunks; a.nsplits = p.splits;
     if (direct) {
         WinoWgradDirectArgs d{};
         d.x_bytes = (long)n_img * h * w * ldx * 4; d.dy_bytes = (long)n_img * h * w * ldy * 4;
-        static const int abl = getenv("RUNET_WINO_WGRAD_ABL") ? atoi(getenv("RUNET_WINO_WGRAD_ABL")) : 0;
-        d.abl = abl;
         d.x = x; d.ldx = ldx; d.dy = dy; d.ldy = ldy; d.slabs = workspace; d.cin = cin; d.cout = cout; d.Nimg = n_img; d.H = h; d.W = w;
         d.TY = h / 2; d.TX = w / 2; d.wci = p.wci; d.ci_chunks = p.ci_chunks; d.co_chunks = p.co_chunks; d.nchunks = p.ci_chunks * p.co_chunks;
         d.nsplits = p.splits; d.tiles = p.tiles; d.tiles_per_split = p.tps;
-        if (abl & 4) hipLaunchKernelGGL(wino_wgrad_direct_kernel<4>, dim3(d.nchunks * p.splits), dim3(512), 0, st, d);
-        else if (abl & 8) hipLaunchKernelGGL(wino_wgrad_direct_kernel<8>, dim3(d.nchunks * p.splits), dim3(512), 0, st, d);
-        else if ((h / 2) % 2 == 0 && !wino_wgrad_rowmajor()) hipLaunchKernelGGL(wino_wgrad_direct_kernel<16>, dim3(d.nchunks * p.splits), dim3(512), 0, st, d);   // zig-zag tile order
-        else hipLaunchKernelGGL(wino_wgrad_direct_kernel<0>, dim3(d.nchunks * p.splits), dim3(512), 0, st, d);
+        const dim3 grid(d.nchunks * p.splits);
+        // the zig-zag order walks 2 x 2 groups of tiles: even counts of tile rows and of tile columns; everything else goes row-major
+        if (d.TY % 2 == 0 && d.TX % 2 == 0 && !wino_wgrad_rowmajor()) hipLaunchKernelGGL(wino_wgrad_direct_kernel<true>, grid, dim3(512), 0, st, d);
+        else hipLaunchKernelGGL(wino_wgrad_direct_kernel<false>, grid, dim3(512), 0, st, d);
     } else {
+        WinoWgradArgs a{};
+        a.x = x; a.ldx = ldx; a.dy = dy; a.ldy = ldy; a.slabs = workspace; a.cin = cin; a.cout = cout; a.Nimg = n_img; a.H = h; a.W = w;
+        a.TY = h / 2; a.TX = w / 2; a.co_chunks = p.co_chunks; a.tiles = p.tiles; a.tiles_per_split = p.tps;
+        a.nchunks = p.ci_chunks * p.co_chunks; a.nsplits = p.splits;
         hipLaunchKernelGGL(wino_wgrad_kernel, dim3(a.nchunks * p.splits), dim3(256), 0, st, a);
     }
     const long kn = (long)cin * cout;

@@ -6,7 +6,8 @@
 //   Y = A^T [ (G g G^T) .* (B^T d B) ] A      per 2x2 output tile, 4x4 input patch d, 3x3 filter g
 //
 // Same block (32 tiles = a 4 x 8 patch of 2x2 tiles, 64 output channels), same halo loader and same input transform in registers as
-// wino_conv_kernel<0, false>.  What changes:
+// wino_conv_kernel: block order, tile constants, patch decode and B^T d B are the one copy of wino2_common.h; the halo loader and the
+// patch-base expression stand here in full, because this kernel's instructions change when they come from the header.  What differs:
 //   * transform_store splits every transformed value on its way into LDS: V lives as three bf16 planes [plane][xi 16][tile 32][16 k]
 //     (32-byte rows with the two 16-byte k-octets swapped on tiles with bit 3 set - the conflict-free ds_read_b128 image of gemm_split.hip);
 //   * the filter comes PRE-SPLIT: runet_wino_weights_x3 writes U straight into Up[xi 16][plane 3][K/8][N][8] bf16, so a lane's B fragment
@@ -16,6 +17,7 @@
 //   * the output transform's stage over i is therefore lane-local: a wave adds its four accumulators in registers and half as much data
 //     goes through the LDS exchange, with every lane storing (see the epilogue).
 #include "x3_common.h"
+#include "wino2_common.h"
 #include "../../include/runet_hip.h"
 #include "derive_weights.h"
 #include <stdlib.h>
@@ -28,6 +30,7 @@
 namespace {
 
 using namespace x3;
+using namespace wino2;
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
@@ -43,10 +46,6 @@ struct WinoX3Args {
     float* stats;                 // nullptr, or [npatches][N][3]: (count, mean, M2) per output channel over the block's pixels (BatchNorm statistics)
 };
 
-constexpr int WT = 32;            // tiles per block
-constexpr int WBN = 64;           // output channels per block
-constexpr int RH = 10, RW = 18;   // input halo of a 4x8 patch of 2x2 tiles
-constexpr int RPS = 24;           // floats per halo pixel in LDS (16 channels + pad: conflict-free ds_read_b64 in the transform)
 constexpr int VPLANE = 16 * WT * 32;      // bytes of one bf16 plane of V: 16 positions x 32 tiles x 16 k
 
 __global__ __launch_bounds__(256, 2) void wino_conv_x3_kernel(WinoX3Args g) {
@@ -56,24 +55,11 @@ __global__ __launch_bounds__(256, 2) void wino_conv_x3_kernel(WinoX3Args g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
-    // blocks that share an input patch (same patch, different output-channel chunk) get ids 8 apart: same XCD, the halo is fetched into one L2
-    int bpatch, bchunk;
-    {
-        const int L = blockIdx.x, nch = g.nchunks, span = 8 * nch;
-        const int grp = L / span, r = L - grp * span;
-        bpatch = grp * 8 + (r & 7);
-        bchunk = r >> 3;
-        if (grp * 8 + 8 > g.npatches) {
-            const int done = grp * 8, rem = g.npatches - done;
-            bpatch = done + r % rem;
-            bchunk = r / rem;
-        }
-    }
+    int bpatch, bchunk;           // blocks that share an input patch get ids 8 apart: same XCD, the halo is fetched into one L2
+    xcd_order(blockIdx.x, g.npatches, g.nchunks, bpatch, bchunk);
     const int n0 = bchunk * WBN;
-    const int bxs = (g.TX + 7) >> 3, bys = (g.TY + 3) >> 2;
-    const int bimg = bpatch / (bxs * bys);
-    const int brem = bpatch - bimg * (bxs * bys);
-    const int by = brem / bxs, bx = brem - by * bxs;
+    const Patch pt = patch_of(bpatch, g.TY, g.TX);
+    const int bimg = pt.img, by = pt.by, bx = pt.bx;
     const int h00 = 8 * by - 1, w00 = 16 * bx - 1;                // image coordinates of halo pixel (0,0)
 
     // ---- halo loader: item = (halo pixel, 4-channel group); 180 x 4 = 720 items, 3 per thread; every read unconditional ----
@@ -127,29 +113,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv_x3_kernel(WinoX3Args g) {
         *reinterpret_cast<bf16x2*>(d + VPLANE) = m;
         *reinterpret_cast<bf16x2*>(d + 2 * VPLANE) = l;
     };
-    auto transform_store = [&]() {
-        float2 raw[16], tmp[16];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) raw[a * 4 + b] = *reinterpret_cast<const float2*>(&R[rbase + (a * RW + b) * RPS]);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const float2 d0 = raw[b], d1 = raw[4 + b], d2 = raw[8 + b], d3 = raw[12 + b];
-            tmp[b] = make_float2(d0.x - d2.x, d0.y - d2.y);
-            tmp[4 + b] = make_float2(d1.x + d2.x, d1.y + d2.y);
-            tmp[8 + b] = make_float2(d2.x - d1.x, d2.y - d1.y);
-            tmp[12 + b] = make_float2(d1.x - d3.x, d1.y - d3.y);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const float2 v0 = tmp[a * 4], v1 = tmp[a * 4 + 1], v2 = tmp[a * 4 + 2], v3 = tmp[a * 4 + 3];
-            put(a * 4 + 0, make_float2(v0.x - v2.x, v0.y - v2.y));
-            put(a * 4 + 1, make_float2(v1.x + v2.x, v1.y + v2.y));
-            put(a * 4 + 2, make_float2(v2.x - v1.x, v2.y - v1.y));
-            put(a * 4 + 3, make_float2(v1.x - v3.x, v1.y - v3.y));
-        }
-    };
+    auto transform_store = [&]() { input_transform(R, rbase, put); };
 
     f32x16 acc[4][2];
 #pragma unroll

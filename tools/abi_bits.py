@@ -2,7 +2,7 @@
 ordered final pass sum_parts of csrc/runet_common.h), the gather adjoints of the bilinear resizes, every entry point of csrc/norm_act.hip
 (BatchNorm statistics, apply and backward: Chan combines in chunk order, first-occurrence max / min, explicit FMAs) and every entry point of
 csrc/attention.hip (the residual-block tail and the attention gate: chunk plans, 16-lane pixel sums, the ordered final passes; ATT_SHAPES
-below).  Every case fills seeded inputs, calls
+below) and of csrc/conv_winograd.hip (the fp32 F(2x2) filter transform, convolution and weight gradient; WINO2_CASES).  Every case fills seeded inputs, calls
 the entry point once through the package's binding and prints one SHA-256 per output tensor (per case for attention.hip).  Two builds of the library compute the same
 bits exactly when their printouts are equal line for line; RUNET_HIP_LIB selects the build (see _lib.py), one fresh process per build:
 
@@ -442,6 +442,46 @@ ATTENTION_CASES = [
 ]
 
 
+def wino2_weights(cin, cout, dgrad):
+    """runet_wino_weights (csrc/conv_winograd.hip): U[16][K/4][N][4] of the forward or the rotated data-gradient filter"""
+    wt, k, nn = rnd(3, 3, cin, cout), (cout if dgrad else cin), (cin if dgrad else cout)
+    U = out(16, k, nn)
+    check(lib.runet_wino_weights(p(wt), p(U), cin, cout, dgrad, ops.stream()))
+    return [U]
+
+
+def wino2_conv(n, h, w, cin, cout, dgrad):
+    """runet_wino_weights, then runet_wino_conv: the forward with bias, or the data gradient accumulated into a channel slice"""
+    k, nn = (cout, cin) if dgrad else (cin, cout)
+    x, wt, b, U = rnd(n, h, w, k), rnd(3, 3, cin, cout), rnd(nn), out(16, k, nn)
+    y = rnd(n, h, w, nn + 8) if dgrad else out(n, h, w, nn)
+    check(lib.runet_wino_weights(p(wt), p(U), cin, cout, dgrad, ops.stream()))
+    check(lib.runet_wino_conv(p(x), k, p(U), None if dgrad else p(b), p(y[..., 8:] if dgrad else y), nn + 8 if dgrad else nn, n, h, w, k, nn, dgrad,
+                              ops.stream()))
+    return [y]
+
+
+def wino2_wgrad(n, h, w, cin, cout, ldx, ldy):
+    """runet_wino_wgrad on channel slices (the last cin / cout channels of pixel strides ldx / ldy): slabs per tile range, summed in order"""
+    x, dy, dw = rnd(n, h, w, ldx), rnd(n, h, w, ldy), out(3, 3, cin, cout)
+    k = ws(lib.runet_wino_wgrad_workspace_floats(n, h, w, cin, cout))
+    check(lib.runet_wino_wgrad(p(x[..., ldx - cin:]), ldx, p(dy[..., ldy - cout:]), ldy, p(dw), p(k), k.numel(), n, h, w, cin, cout, ops.stream()))
+    return [dw]
+
+
+# ---- csrc/conv_winograd.hip: the shapes of tests/test_gpu_wino2_f32.py.  (n, h, w, cin, cout); the data gradient contracts over cout (a multiple of 16)
+WINO2_FWD = [(2, 8, 8, 16, 32), (1, 12, 20, 64, 128), (3, 4, 4, 128, 256), (2, 16, 16, 32, 48), (2, 64, 64, 64, 64), (1, 32, 32, 256, 64),
+             (5, 6, 10, 48, 32), (1, 4, 36, 16, 6), (1, 20, 36, 16, 6)]
+# (n, h, w, cin, cout, ldx, ldy): zig-zag with one / two tile ranges | odd tile columns, two ranges (x2) | odd tile rows | w < 4: the LDS form | slices
+WINO2_WGRAD = [(1, 8, 8, 16, 16, 16, 16), (2, 16, 12, 48, 80, 48, 80), (4, 16, 6, 16, 16, 16, 16), (2, 16, 10, 32, 48, 32, 48),
+               (5, 6, 10, 48, 32, 48, 32), (3, 8, 2, 16, 32, 16, 32), (2, 16, 12, 48, 80, 56, 96)]
+WINO2_CASES = [
+    *[(wino2_weights, (s[3], s[4], dg)) for s in WINO2_FWD[:4] + WINO2_FWD[7:8] for dg in (0, 1) if s[3 + dg] % 16 == 0],
+    *[(wino2_conv, (*s, dg)) for s in WINO2_FWD for dg in (0, 1) if s[3 + dg] % 16 == 0],
+    *[(wino2_wgrad, s) for s in WINO2_WGRAD],
+]
+
+
 # (entry point, arguments).  Partial rows each reducing case yields, from its file's chunk rule, against the 16 (hrnet, multiscale,
 # water_index) or 8 (fastscnn, dwsep, dwconv) part-lanes of the final pass:
 CASES = [
@@ -466,6 +506,7 @@ CASES = [
     *NORM_ACT_CASES,
     *[(wino_conv_x3, (*s, st)) for s in WINO_X3_SHAPES for st in (0, 1)],
     *ATTENTION_CASES,
+    *WINO2_CASES,
 ]
 
 
