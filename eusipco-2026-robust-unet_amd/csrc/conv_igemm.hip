@@ -24,6 +24,7 @@
 //   partial slabs that a second kernel sums in a fixed order (bitwise reproducible, no atomics).
 #include "runet_common.h"
 #include "../../include/runet_hip.h"
+#include <algorithm>
 
 namespace {
 
@@ -1167,15 +1168,12 @@ extern "C" int runet_conv_igemm(const float* x, int ldx, const float* w, const f
     RUNET_CHECK_LAUNCH();
 }
 
-// ------------------------------------------------------------------------------------------ its weight gradient: five routes
-static bool use_tile_kernel(int kh, int kw, int dil, int transposed) {
-    if (transposed) return kh == 2 && kw == 2;
-    return (kh == 1 && kw == 1) || (kh == 3 && kw == 3 && dil == 1);
-}
-
-// 1x1 weight gradient = one TN GEMM over the pixels (dW[cin][cout] = x^T dy): rows per split so that ~512 blocks exist, 16-aligned
+// ------------------------------------------------------------------------------------------ its weight gradient: one route of five
+// 1x1 weight gradient = one TN GEMM over the pixels (dW[cin][cout] = x^T dy): rows per split, 16-aligned.  The split count aims at ~2048
+// 64 x 64 wave tiles on the chip; wm, wn count them per block side as a removed kernel with one-, two- and four-wave blocks did (both
+// GEMM kernels here use 128 x 128 blocks of four).  The formula stays: it fixes the split count, therefore the summation order of the wide
+// GEMMs, and the workspace size every caller is told.
 static int wgrad1x1_rows_per_split(long P, int cin, int cout) {
-    // gemm.hip picks one-, two- or four-wave blocks by the output's size: aim at ~2048 waves on the chip
     const int wm = cin > 64 ? 2 : 1, wn = cout > 64 ? 2 : 1;
     const long tiles = (long)cdiv(cin, 64 * wm) * cdiv(cout, 64 * wn);
     long splits = cdiv(2048, tiles * wm * wn);
@@ -1183,36 +1181,8 @@ static int wgrad1x1_rows_per_split(long P, int cin, int cout) {
     if (splits > maxs) splits = maxs;
     return (int)((cdiv(P, splits) + 15) / 16 * 16);
 }
-// The 1x1 weight gradient as one TN GEMM over the pixels (gemm.hip: 128 x 128 LDS-ring tiles, lean loader) where both channel counts
-// fill such a tile; narrower layers stay on wgrad_tile_kernel<1,..>, whose per-tile integer address arithmetic costs it 30-77 TFLOP/s
-// on the wide ones.  Measured (tools/conv_launches.py, 16 x 256^2 step): 256->128 @ 128^2 231 -> 159 us, 512->256 @ 64^2 223 -> 155,
-// 1024->512 @ 32^2 220 -> 153, the ten wide launches 1.13 -> 0.83 ms; 128->64 / 64->128 @ 128^2 would go 89 -> 131 us (half-empty tiles).
-// The step time does not move (weight gradients run on the side stream); the GPU does 0.3 ms less work.  RUNET_WGRAD1X1_TILE=1: tile kernel
-// everywhere.  (With RUNET_GEMM_TN_DIRECT=1 the GEMM is the register-direct one, which also serves narrow outputs.)
-static bool wgrad1x1_direct(long P, int cin, int cout) {
-    static const bool off = env_flag("RUNET_WGRAD1X1_TILE");
-    static const bool direct = env_flag("RUNET_GEMM_TN_DIRECT");
-    if (off || P * 4 >= (1L << 31)) return false;
-    if (direct) return !((long)cin * cout <= 8192 && P >= (1L << 19));
-    // RUNET_WGRAD1X1_MIN_NARROW (measurement knob, default 128): channels the NARROWER side needs (the wider one always >= 128)
-    static const int narrow = env_int("RUNET_WGRAD1X1_MIN_NARROW", 128);
-    const int lo = cin < cout ? cin : cout, hi = cin < cout ? cout : cin;
-    return hi >= 128 && lo >= narrow;
-}
-// ... and of those the ones the split-operand TN GEMM (gemm_split.hip, BF16 matrix cores, fp32-accurate) takes: pixel count a multiple of 16
-static bool wgrad1x1_x3(long P, int cin, int cout) {
-    static const bool off = env_flag("RUNET_NO_X3") || env_flag("RUNET_GEMM_TN_DIRECT");
-    return !off && P % 16 == 0;
-}
-
-// the transposed convolution's weight gradient on the split-operand TN GEMM: image width a multiple of 16 (a k-step's rows share an image row),
-// both channel counts >= RUNET_CONVT_WGRAD_X3_MIN [64]
-static bool convt_wgrad_x3(long P, int w_, int cin, int cout) {
-    static const bool off = env_flag("RUNET_NO_X3") || env_flag("RUNET_NO_CONVT_WGRAD_X3");
-    static const int lo = env_int("RUNET_CONVT_WGRAD_X3_MIN", 64);
-    return !off && w_ % 16 == 0 && P % 16 == 0 && P < (1L << 31) && cin >= lo && cout >= lo;
-}
-// ... its plan: 4 taps = 4 GEMMs over the low-resolution pixels, up to 512 / tiles splits of at least 256 rows; -> rows per split (16-aligned)
+// the transposed convolution's weight gradient on the split-operand TN GEMM: 4 taps = 4 GEMMs over the low-resolution pixels, up to
+// 512 / tiles splits of at least 256 rows; -> rows per split (16-aligned)
 static int convt_wgrad_x3_rows_per_split(long P, int cin, int cout) {
     const long tiles = (long)cdiv(cin, 128) * cdiv(cout, 128) * 4;
     long splits = cdiv(512, tiles);
@@ -1221,27 +1191,75 @@ static int convt_wgrad_x3_rows_per_split(long P, int cin, int cout) {
     return (int)((cdiv(P, splits) + 15) / 16 * 16);
 }
 
-// the largest workspace any route of runet_conv_wgrad may use for the shape (dilation and the knobs are unknown here)
-extern "C" long runet_conv_wgrad_workspace_floats(int n_img, int h, int w_, int cin_w, int cout, int kh, int kw) {
+enum WGradKind { WG_STEM, WG_GEMM_TN, WG_CONVT_X3, WG_TILE, WG_SPLITK };
+struct WGradRoute {
+    WGradKind kind;
+    bool x3;            // WG_GEMM_TN: gemm_split.hip's split-operand kernel, else gemm.hip's f32 one
+    int rps;            // WG_GEMM_TN, WG_CONVT_X3: rows (pixels) per split
+    int splits;         // partial sums as planned; WG_TILE and WG_SPLITK shrink them to the workspace they are given
+    long slab;          // floats of one partial sum = of dw
+    TilePlan tile;      // WG_TILE
+    // Floats of workspace to announce for the route.  The stem's 64 slabs on top and the GEMMs' slab for a single split are not used by
+    // the launches below; they are the sizes callers have always been told and stay.
+    long workspace() const {
+        if (kind == WG_STEM) return (long)splits * slab + 64 * slab;
+        if (kind == WG_GEMM_TN || kind == WG_CONVT_X3) return splits * slab;
+        return splits > 1 ? splits * slab : 0;
+    }
+};
+// rows per split, splits and slab of one kind for a shape (cin_w input channels take part)
+static WGradRoute wgrad_plan_as(WGradKind kind, int n_img, int h, int w_, int cin_w, int cout, int kh, int kw, int transposed) {
     const long P = (long)n_img * h * w_;
-    const long generic = wgrad_workspace(P, cin_w, cout, kh * kw);
-    if (kh == 1 && kw == 1) {
-        const long direct = (long)cdiv(P, wgrad1x1_rows_per_split(P, cin_w, cout)) * cin_w * cout;
-        const long tile = slab_floats(wgrad_tile_plan(n_img, h, w_, cin_w, cout, 1).splits, 1, cin_w, cout);
-        return direct > tile ? direct : tile;
+    WGradRoute r{};
+    r.kind = kind;
+    r.slab = (long)kh * kw * cin_w * cout;
+    switch (kind) {
+    case WG_STEM: r.splits = cdiv(h, STEM_ROWS) * n_img; break;
+    case WG_GEMM_TN: r.rps = wgrad1x1_rows_per_split(P, cin_w, cout); r.splits = cdiv(P, r.rps); break;
+    case WG_CONVT_X3: r.rps = convt_wgrad_x3_rows_per_split(P, cin_w, cout); r.splits = cdiv(P, r.rps); break;
+    case WG_TILE: r.tile = wgrad_tile_plan(n_img, h, w_, cin_w, cout, transposed ? 1 : kh, transposed ? 4 : 1); r.splits = r.tile.splits; break;
+    default: r.splits = wgrad_plan(P, cin_w, cout, kh * kw).splits; break;
     }
-    if (kh == 3 && kw == 3 && cin_w <= 4) return (long)cdiv(h, 4) * n_img * 9 * cin_w * cout + 64L * 9 * cin_w * cout;   // stem kernel slabs
-    if (kh == 2 && kw == 2) {                                // transposed: the split-operand TN plan, the tile plan or the generic one
-        const long x3 = (long)cdiv(P, convt_wgrad_x3_rows_per_split(P, cin_w, cout)) * 4 * cin_w * cout;
-        const long tile = slab_floats(wgrad_tile_plan(n_img, h, w_, cin_w, cout, 1, 4).splits, 4, cin_w, cout);
-        const long m = tile > generic ? tile : generic;
-        return x3 > m ? x3 : m;
-    }
-    if (kh == 3 && kw == 3) {                                // the tile plan (dilation 1) or the generic one
-        const long tile = slab_floats(wgrad_tile_plan(n_img, h, w_, cin_w, cout, 3).splits, 9, cin_w, cout);
-        return tile > generic ? tile : generic;
-    }
-    return generic;
+    return r;
+}
+// Which kernel family takes the shape, and with which plan.
+//   stem: the RGB stem's 3x3 (conv_igemm.hip's stem_wgrad_kernel).
+//   TN GEMM: the 1x1 weight gradient as one TN GEMM over the pixels where both channel counts fill a 128 x 128 tile; narrower layers stay
+//     on wgrad_tile_kernel<1,..>, whose per-tile integer address arithmetic costs it 30-77 TFLOP/s on the wide ones.  Measured
+//     (tools/conv_launches.py, 16 x 256^2 step): 256->128 @ 128^2 231 -> 159 us, 512->256 @ 64^2 223 -> 155, 1024->512 @ 32^2 220 -> 153,
+//     the ten wide launches 1.13 -> 0.83 ms; 128->64 / 64->128 @ 128^2 would go 89 -> 131 us (half-empty tiles).  The step time does not
+//     move (weight gradients run on the side stream); the GPU does 0.3 ms less work.  RUNET_WGRAD1X1_TILE=1: tile kernel everywhere.
+//     The split-operand kernel (gemm_split.hip, BF16 matrix cores, fp32-accurate) where the pixel count is a multiple of 16, else gemm.hip's.
+//   transposed x3: ConvTranspose2d(k2, s2) on the split-operand TN GEMM: image width a multiple of 16 (a k-step's rows share an image row).
+//   tile kernel: the other 1x1, 3x3 at dilation 1 and transposed 2x2 shapes.   split-K: what is left, 3x3 with dilation > 1.
+constexpr int WGRAD1X1_GEMM_MIN_CH = 128;      // channels the NARROWER side of a 1x1 needs for the TN GEMM (half-empty 128 x 128 tiles below)
+constexpr int CONVT_X3_WGRAD_MIN_CH = 64;      // channels both sides of a transposed convolution need for the split-operand TN GEMM
+static WGradRoute wgrad_route(int n_img, int h, int w_, int cin, int cin_w, int cout, int kh, int kw, int dil, int transposed) {
+    static const bool no_x3 = env_flag("RUNET_NO_X3"), tile_1x1 = env_flag("RUNET_WGRAD1X1_TILE"), no_convt_x3 = env_flag("RUNET_NO_CONVT_WGRAD_X3");
+    const long P = (long)n_img * h * w_;
+    const bool k1 = kh == 1 && kw == 1, k2 = kh == 2 && kw == 2, k3 = kh == 3 && kw == 3;
+    const int lo = cin < cout ? cin : cout;
+    WGradKind kind = WG_SPLITK;
+    if (!transposed && k3 && dil == 1 && cin == 4 && cout <= 1024 && 256 % (cout / 4) == 0) kind = WG_STEM;
+    else if (!transposed && k1 && cin_w == cin && !tile_1x1 && P * 4 < (1L << 31) && lo >= WGRAD1X1_GEMM_MIN_CH) kind = WG_GEMM_TN;
+    else if (transposed && k2 && cin_w == cin && !no_x3 && !no_convt_x3 && w_ % 16 == 0 && P % 16 == 0 && P < (1L << 31) && lo >= CONVT_X3_WGRAD_MIN_CH)
+        kind = WG_CONVT_X3;
+    else if (transposed ? k2 : (k1 || (k3 && dil == 1))) kind = WG_TILE;
+    WGradRoute r = wgrad_plan_as(kind, n_img, h, w_, cin_w, cout, kh, kw, transposed);
+    r.x3 = kind == WG_GEMM_TN && !no_x3 && P % 16 == 0;
+    return r;
+}
+
+// The largest workspace any route of runet_conv_wgrad may use for the shape.  cin, the dilation and the knobs are unknown here, so every
+// kind the kernel size admits counts, whether wgrad_route would pick it or not.
+extern "C" long runet_conv_wgrad_workspace_floats(int n_img, int h, int w_, int cin_w, int cout, int kh, int kw) {
+    const bool k1 = kh == 1 && kw == 1, k2 = kh == 2 && kw == 2, k3 = kh == 3 && kw == 3;
+    auto ws = [&](WGradKind kind) { return wgrad_plan_as(kind, n_img, h, w_, cin_w, cout, kh, kw, k2).workspace(); };
+    if (k1) return std::max(ws(WG_GEMM_TN), ws(WG_TILE));
+    if (k3 && cin_w <= 4) return ws(WG_STEM);
+    if (k2) return std::max({ws(WG_CONVT_X3), ws(WG_TILE), ws(WG_SPLITK)});
+    if (k3) return std::max(ws(WG_TILE), ws(WG_SPLITK));
+    return ws(WG_SPLITK);
 }
 
 extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ldy, float* dw, float* workspace,
@@ -1255,48 +1273,46 @@ extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ld
     RUNET_REQUIRE((kh == 1 && kw == 1) || (kh == 3 && kw == 3) || (kh == 2 && kw == 2 && transposed), "unsupported kernel size");
     hipStream_t st = (hipStream_t)stream;
     const long P = (long)n_img * h * w_;
-    if (!transposed && kh == 3 && kw == 3 && dil == 1 && cin == 4 && cout <= 1024 && 256 % (cout / 4) == 0) {      // RGB stem
-        const int nblk = cdiv(h, STEM_ROWS) * n_img;
-        const long wsize = 9L * cin_w * cout;
+    WGradRoute r = wgrad_route(n_img, h, w_, cin, cin_w, cout, kh, kw, dil, transposed);
+    if (r.kind == WG_SPLITK) {      // plans, shrinks to the workspace and reduces on its own, as for the general and rectangular entry points
+        WGradArgs a = wgrad_operands(x, ldx, dy, ldy, n_img, cin, cin_w, cout);
+        wgrad_geom_conv(a, same_conv(h, w_, kh, kw, dil));
+        launch_wgrad_splitk(a, P, cin_w, cout, kh * kw, dw, workspace, workspace_floats, st);
+        RUNET_CHECK_LAUNCH();
+    }
+    const long wsize = r.slab;
+    // a workspace too small for the transposed GEMM's splits: the tile kernel, which shrinks its splits to what it is given
+    if (r.kind == WG_CONVT_X3 && r.splits > 1 && !(workspace && workspace_floats >= r.splits * wsize))
+        r = wgrad_plan_as(WG_TILE, n_img, h, w_, cin_w, cout, kh, kw, transposed);
+    int splits = r.splits;
+    switch (r.kind) {
+    case WG_STEM: {
+        const int nblk = splits;
         RUNET_REQUIRE(workspace && workspace_floats >= nblk * wsize, "workspace too small for the stem weight gradient");
         hipLaunchKernelGGL(stem_wgrad_kernel, dim3(cdiv(h, STEM_ROWS), n_img), dim3(256), 0, st, x, ldx, dy, ldy, workspace, h, w_, cin_w, cout);
-        reduce_slabs(workspace, dw, wsize, nblk, st);
-        RUNET_CHECK_LAUNCH();
+        break;
     }
-    if (!transposed && kh == 1 && kw == 1 && cin_w == cin && wgrad1x1_direct(P, cin, cout)) {
-        // register-direct TN GEMM (gemm.hip): both operands are read from HBM in MFMA operand order, no LDS, no VALU
-        const int rps = wgrad1x1_rows_per_split(P, cin, cout);
-        const int splits = cdiv(P, rps);
-        const long wsize = (long)cin * cout;
+    case WG_GEMM_TN: {
         RUNET_REQUIRE(splits == 1 || (workspace && workspace_floats >= splits * wsize), "workspace too small (runet_conv_wgrad_workspace_floats)");
-        const int rc = wgrad1x1_x3(P, cin, cout)
-                           ? runet_gemm_x3_tn_batched(x, ldx, 0, dy, ldy, 0, splits > 1 ? workspace : dw, 1, (int)P, cin, cout, rps, stream)
-                           : runet_gemm_tn_launch(x, ldx, 0, dy, ldy, 0, splits > 1 ? workspace : dw, 1, (int)P, cin, cout, rps, st);
+        const int rc = r.x3 ? runet_gemm_x3_tn_batched(x, ldx, 0, dy, ldy, 0, splits > 1 ? workspace : dw, 1, (int)P, cin, cout, r.rps, stream)
+                            : runet_gemm_tn_launch(x, ldx, 0, dy, ldy, 0, splits > 1 ? workspace : dw, 1, (int)P, cin, cout, r.rps, st);
         if (rc) return rc;
-        if (splits > 1) reduce_slabs(workspace, dw, wsize, splits, st);
-        RUNET_CHECK_LAUNCH();
+        break;
     }
-    if (transposed && cin_w == cin && convt_wgrad_x3(P, w_, cin, cout)) {
-        // ConvTranspose2d weight gradient on the split-operand TN GEMM (gemm_split.hip): 4 taps = 4 GEMMs over the low-resolution pixels
-        const int rps = convt_wgrad_x3_rows_per_split(P, cin, cout);
-        const int ns = cdiv(P, rps);
-        const long wsize = 4L * cin * cout;
-        if (ns == 1 || (workspace && workspace_floats >= ns * wsize)) {
-            const int rc = runet_gemm_x3_tn_convt(x, ldx, dy, ldy, ns > 1 ? workspace : dw, n_img, h, w_, cin, cout, rps, stream);
-            if (rc) return rc;
-            if (ns > 1) reduce_slabs(workspace, dw, wsize, ns, st);
-            RUNET_CHECK_LAUNCH();
-        }
+    case WG_CONVT_X3: {
+        const int rc = runet_gemm_x3_tn_convt(x, ldx, dy, ldy, splits > 1 ? workspace : dw, n_img, h, w_, cin, cout, r.rps, stream);
+        if (rc) return rc;
+        break;
     }
-    if (use_tile_kernel(kh, kw, dil, transposed)) {
-        TilePlan p = wgrad_tile_plan(n_img, h, w_, cin_w, cout, transposed ? 1 : kh, transposed ? 4 : 1);
-        const long wsize = (long)kh * kw * cin_w * cout;
+    default: {      // WG_TILE (WG_SPLITK has returned above)
+        TilePlan& p = r.tile;
         if (p.splits > 1 && (workspace == nullptr || workspace_floats < p.splits * wsize)) {
             int s2 = workspace ? (int)(workspace_floats / wsize) : 1;
             if (s2 < 1) s2 = 1;
             p.tps = cdiv(p.total_tiles, s2);
             p.splits = cdiv(p.total_tiles, p.tps);
         }
+        splits = p.splits;
         WGradTileArgs t{};
         t.x = x; t.ldx = ldx; t.dy = dy; t.ldy = ldy; t.out = (p.splits > 1) ? workspace : dw;
         t.Kci = cin; t.Kvalid = cin_w; t.Nco = cout; t.Nimg = n_img; t.H = h; t.W = w_;
@@ -1307,12 +1323,9 @@ extern "C" int runet_conv_wgrad(const float* x, int ldx, const float* dy, int ld
         else if (p.tm == 2) launch_wgrad_tile<1, 2, 1>(t, p, st);
         else if (p.tn == 2) launch_wgrad_tile<1, 1, 2>(t, p, st);
         else launch_wgrad_tile<1, 1, 1>(t, p, st);
-        if (p.splits > 1) reduce_slabs(workspace, dw, wsize, p.splits, st);
-        RUNET_CHECK_LAUNCH();
     }
-    WGradArgs a = wgrad_operands(x, ldx, dy, ldy, n_img, cin, cin_w, cout);      // what is left: 3x3 with dilation > 1
-    wgrad_geom_conv(a, same_conv(h, w_, kh, kw, dil));
-    launch_wgrad_splitk(a, P, cin_w, cout, kh * kw, dw, workspace, workspace_floats, st);
+    }
+    if (r.kind == WG_STEM || splits > 1) reduce_slabs(workspace, dw, wsize, splits, st);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1498,19 +1511,14 @@ extern "C" int runet_conv_wgrad_rect(const float* x, int ldx, const float* dy, i
 // Batched plain GEMMs on the same kernels (the 36 position-GEMMs of the unfused Winograd F(4x4,3x3) path, conv_winograd4.hip).
 //   runet_gemm_batched   : C[z][rows][n] = A[z][rows][k] . B[z][k][n]                (blockIdx.z = z)
 //   runet_gemm_tn_batched: C[split][z][k][n] = sum over the split's rows of A[z][row][k] * B[z][row][n];  splits = ceil(rows / rows_per_split)
-// RUNET_GEMM_OLD: A/B switch for tools/bench_gemm.py, set at all, whatever the value
-static bool gemm_old_path() { static const bool old_path = getenv("RUNET_GEMM_OLD") != nullptr; return old_path; }
 // what runet_gemm_batched launches for a shape: an igemm tile variant, or GEMM_NN = gemm.hip's gemm_nn_kernel
 constexpr int GEMM_NN = 5;
 static int gemm_batched_route(int batch, int rows, int n) {
     const long b128 = (long)cdiv(rows, 128) * cdiv(n, 128) * batch;
-    if (!gemm_old_path()) {
-        // 128x64 tiles where 128x128 tiles would fill the 256 CUs unevenly (e.g. 576 blocks = 2.25 per CU -> 3 rounds for 2.25 of work)
-        const double per_cu = b128 / 256.0, bal = per_cu / (double)((b128 + 255) / 256);
-        if (bal < 0.8 && n % 64 == 0) return V_128x64;
-        if (n >= 96) return GEMM_NN;
-    }
-    if (n % 128 == 0 && b128 >= 256) return V_128x128;      // n % 128 == 0 is n >= 96: reachable only with RUNET_GEMM_OLD set
+    // 128x64 tiles where 128x128 tiles would fill the 256 CUs unevenly (e.g. 576 blocks = 2.25 per CU -> 3 rounds for 2.25 of work)
+    const double per_cu = b128 / 256.0, bal = per_cu / (double)((b128 + 255) / 256);
+    if (bal < 0.8 && n % 64 == 0) return V_128x64;
+    if (n >= 96) return GEMM_NN;
     if (n > 32 && (long)cdiv(rows, 128) * cdiv(n, 64) * batch >= 256) return V_128x64;
     if (n > 32) return V_64x64;
     return V_128x32;
@@ -1554,8 +1562,7 @@ extern "C" int runet_gemm_tn_batched(const float* a, int lda, long stride_a, con
     RUNET_REQUIRE(k > 0 && k % 4 == 0 && n > 0 && n % 4 == 0 && lda >= k && lda % 4 == 0 && ldb >= n && ldb % 4 == 0, "k, n and the row strides must be multiples of 4");
     RUNET_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0 && ((uintptr_t)c % 16) == 0 && stride_a % 4 == 0 && stride_b % 4 == 0, "alignment");
     hipStream_t st = (hipStream_t)stream;
-    const bool big = k > 64 && n > 64;
-    if (!gemm_old_path() && big) {
+    if (k > 64 && n > 64) {                  // gemm.hip's 128 x 128 LDS-ring kernel where both sides fill more than half a tile
         runet_gemm_tn_launch(a, lda, stride_a, b, ldb, stride_b, c, batch, rows, k, n, rows_per_split, st);
         RUNET_CHECK_LAUNCH();
     }
@@ -1565,7 +1572,7 @@ extern "C" int runet_gemm_tn_batched(const float* a, int lda, long stride_a, con
     g.H = 1; g.W = rows; g.Hin = 1; g.Win = rows; g.a_scale = 1; g.KH = batch; g.KW = 1; g.Hout = 1; g.Wout = rows; g.o_scale = 1;
     g.tap_bs_x = stride_a; g.tap_bs_dy = stride_b;
     g.pix_per_split = rows_per_split;
-    launch_wgrad_tiles(g, big, k, n, batch, splits, st);
+    launch_wgrad_tiles(g, false, k, n, batch, splits, st);
     RUNET_CHECK_LAUNCH();
 }
 

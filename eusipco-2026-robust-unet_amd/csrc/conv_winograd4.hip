@@ -16,7 +16,6 @@
 #include "runet_common.h"
 #include "../../include/runet_hip.h"
 #include "derive_weights.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -429,10 +428,10 @@ W4Geom geom(int n_img, int h, int w, int dil) {
 bool dil_ok(int h, int w, int dil) { return dil >= 1 && dil <= 8 && h % dil == 0 && w % dil == 0; }
 
 // rows (tiles) per split of the weight-gradient GEMMs: enough splits for ~512 blocks, at least 64 tiles each, 16-aligned
+// (a target of 256 blocks measured 582.1 img/s, 512: 580.9, 1024: 576.1, 2048: 572.1 - within the run-to-run spread up to 512)
 int wgrad_rows_per_split(long T, int cin, int cout) {
-    static const int target = getenv("RUNET_W4_WGRAD_BLOCKS") ? atoi(getenv("RUNET_W4_WGRAD_BLOCKS")) : 512;      // measurement knob (256: 582.1, 512: 580.9, 1024: 576.1, 2048: 572.1 img/s)
     const long blocks = (long)cdiv(cin, 128) * cdiv(cout, 128) * 36;
-    long s = cdiv(target, blocks);
+    long s = cdiv(512, blocks);
     const long maxs = T / 64 > 0 ? T / 64 : 1;
     if (s > maxs) s = maxs;
     if (s < 1) s = 1;

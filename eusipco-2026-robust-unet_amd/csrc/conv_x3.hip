@@ -17,7 +17,6 @@
 #include "x3_common.h"
 #include "../../include/runet_hip.h"
 #include "derive_weights.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -307,9 +306,6 @@ bool mode_ok(int mode) { return mode == RUNET_CONV_FWD || mode == RUNET_CONV_DGR
 
 // 128 x 64 tiles where 128 x 128 would leave the 256 CUs (two resident blocks each) unevenly filled, or the output is narrow
 bool narrow_tile(long rows, int n, int gz) {
-    static const int force = getenv("RUNET_CONV_X3_BN") ? atoi(getenv("RUNET_CONV_X3_BN")) : 0;      // measurement knob: 64 / 128
-    if (force == 64) return true;
-    if (force == 128) return false;
     if (n <= 64) return true;
     const long b128 = (long)cdiv(rows, 128) * cdiv(n, 128) * gz;
     const double rounds = b128 / 512.0;
@@ -362,6 +358,12 @@ extern "C" int runet_conv_x3_stats(const float* x, int ldx, const void* wpacked,
     return conv_x3_launch(x, ldx, wpacked, bias, y, ldy, n_img, h, w_, cin, cout, mode, accumulate, stats, stream);
 }
 
+template <int BN>
+static void launch_conv_x3(X3ConvArgs g, hipStream_t st) {
+    g.gn = cdiv(g.n, BN);
+    hipLaunchKernelGGL(conv_nn_x3_kernel<BN>, dim3((unsigned)((long)g.gm * g.gn * g.gz)), dim3(256), 3 * NNX3<BN>::STAGE + 1024, st, g);
+}
+
 static int conv_x3_launch(const float* x, int ldx, const void* wpacked, const float* bias, float* y, int ldy, int n_img, int h, int w_, int cin,
                           int cout, int mode, int accumulate, float* stats, void* stream) {
     RUNET_REQUIRE(x && wpacked && y, "null pointer");
@@ -376,13 +378,7 @@ static int conv_x3_launch(const float* x, int ldx, const void* wpacked, const fl
     if (mode == RUNET_CONVT_FWD) { g.c_scale = 2; g.gz = 4; }
     if (mode == RUNET_CONVT_DGRAD) { g.a_scale = 2; g.ntaps = 4; }
     g.gm = cdiv(g.rows, 128);
-    hipStream_t st = (hipStream_t)stream;
-    if (narrow_tile(g.rows, cout, g.gz)) {
-        g.gn = cdiv(cout, 64);
-        hipLaunchKernelGGL(conv_nn_x3_kernel<64>, dim3((unsigned)((long)g.gm * g.gn * g.gz)), dim3(256), 3 * NNX3<64>::STAGE + 1024, st, g);
-    } else {
-        g.gn = cdiv(cout, 128);
-        hipLaunchKernelGGL(conv_nn_x3_kernel<128>, dim3((unsigned)((long)g.gm * g.gn * g.gz)), dim3(256), 3 * NNX3<128>::STAGE + 1024, st, g);
-    }
+    if (narrow_tile(g.rows, cout, g.gz)) launch_conv_x3<64>(g, (hipStream_t)stream);
+    else launch_conv_x3<128>(g, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }

@@ -25,7 +25,6 @@
 // and the row tiles that share a B matrix meet in one L2 (gemm.hip's order re-fetched A across XCDs: 1.49x its algorithmic bytes).
 #include "x3_common.h"
 #include "../../include/runet_hip.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -420,20 +419,16 @@ extern "C" int runet_gemm_x3_pack(const float* b, long stride_b, void* packed, i
 
 // which tile the NN kernel uses for a shape: 128 x 64 where 128 x 128 tiles would fill the 256 CUs (two resident blocks each) unevenly
 static bool nn_x3_narrow(int batch, int rows, int n) {
-    static const int force = getenv("RUNET_GEMM_X3_BN") ? atoi(getenv("RUNET_GEMM_X3_BN")) : 0;      // measurement knob: 64 / 128
-    if (force == 64) return true;
-    if (force == 128) return false;
     if (n <= 64) return true;
-    // narrower tiles only where 128 x 128 tiles cannot fill the chip once (512 resident blocks): small-batch shards.  The earlier rule also chose
-    // them for unevenly filled last waves (balance < 0.8); with the loop's prefetch fixed the two rules measure the same at 16 x 256^2 (586.3 vs 586.4
-    // img/s) and the simpler one is 0.3 % ahead on the 2-image shard
-    static const int mode = getenv("RUNET_GEMM_X3_BALANCE") ? atoi(getenv("RUNET_GEMM_X3_BALANCE")) : 0;      // measurement knob: 1 = the earlier rule
-    const long b128 = (long)cdiv(rows, 128) * cdiv(n, 128) * batch;
-    if (mode == 1) {
-        const double rounds = b128 / 512.0;
-        return rounds / (double)((b128 + 511) / 512) < 0.8;
-    }
-    return b128 < 512;
+    // narrower tiles only where 128 x 128 tiles cannot fill the chip once (512 resident blocks): small-batch shards.  An earlier rule also chose
+    // them for unevenly filled last waves (balance < 0.8, conv_x3.hip's rule); with the loop's prefetch fixed the two rules measured the same at
+    // 16 x 256^2 (586.3 vs 586.4 img/s) and this simpler one was 0.3 % ahead on the 2-image shard
+    return (long)cdiv(rows, 128) * cdiv(n, 128) * batch < 512;
+}
+
+template <int BN>
+static void launch_nn_x3(const X3Args& g, long total, hipStream_t st) {
+    hipLaunchKernelGGL(gemm_nn_x3_kernel<BN>, dim3((unsigned)total), dim3(256), 3 * NNX3<BN>::STAGE, st, g);
 }
 
 extern "C" const char* runet_gemm_x3_kernel_name(int batch, int rows, int k, int n) {
@@ -446,19 +441,12 @@ extern "C" int runet_gemm_x3_batched(const float* a, int lda, long stride_a, con
     RUNET_REQUIRE(lda >= k && lda % 4 == 0 && ldc >= n && ((uintptr_t)a % 16) == 0 && ((uintptr_t)packed_b % 16) == 0 && stride_a % 4 == 0, "alignment");
     X3Args g{};
     g.a = a; g.lda = lda; g.sa = stride_a; g.b = packed_b; g.sb = 3L * k * n; g.c = c; g.ldc = ldc; g.sc = stride_c; g.rows = rows; g.k = k; g.n = n;
-    g.gm = cdiv(rows, 128); g.gz = batch;
-    hipStream_t st = (hipStream_t)stream;
-    if (nn_x3_narrow(batch, rows, n)) {
-        g.gn = cdiv(n, 64);
-        const long total = (long)g.gm * g.gn * g.gz;
-        RUNET_REQUIRE(total < (1L << 31), "grid too large");
-        hipLaunchKernelGGL(gemm_nn_x3_kernel<64>, dim3((unsigned)total), dim3(256), 3 * NNX3<64>::STAGE, st, g);
-    } else {
-        g.gn = cdiv(n, 128);
-        const long total = (long)g.gm * g.gn * g.gz;
-        RUNET_REQUIRE(total < (1L << 31), "grid too large");
-        hipLaunchKernelGGL(gemm_nn_x3_kernel<128>, dim3((unsigned)total), dim3(256), 3 * NNX3<128>::STAGE, st, g);
-    }
+    const bool narrow = nn_x3_narrow(batch, rows, n);
+    g.gm = cdiv(rows, 128); g.gn = cdiv(n, narrow ? 64 : 128); g.gz = batch;
+    const long total = (long)g.gm * g.gn * g.gz;
+    RUNET_REQUIRE(total < (1L << 31), "grid too large");
+    if (narrow) launch_nn_x3<64>(g, total, (hipStream_t)stream);
+    else launch_nn_x3<128>(g, total, (hipStream_t)stream);
     RUNET_CHECK_LAUNCH();
 }
 

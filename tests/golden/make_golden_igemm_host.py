@@ -3,7 +3,7 @@ refusal messages) as one build of the library makes them.  Nothing here launches
 
     RUNET_HIP_LIB=<librunet_hip.so of the commit to record> python tests/golden/make_golden_igemm_host.py
 
-tests/test_igemm_host.py imports the grids and the collectors below, so the golden and the test cannot drift apart.  The three environment
+tests/test_igemm_host.py imports the grids and the collectors below, so the golden and the test cannot drift apart.  The two environment
 knobs are read once per process by the library: every knob setting is collected in a child process of its own (`--child`)."""
 import base64
 import ctypes
@@ -20,7 +20,7 @@ GOLDEN = os.path.join(HERE, "igemm_host.json")
 PKG = "eusipco-2026-robust-unet_amd"
 
 FWD, DGRAD, CONVT_FWD, CONVT_DGRAD, DGRAD_T, CONVT_DGRAD_T = range(6)
-KNOBS = ("RUNET_IGEMM_GENERAL", "RUNET_IGEMM_OLD_TILES", "RUNET_GEMM_OLD")      # each collected alone, set to "1"
+KNOBS = ("RUNET_IGEMM_GENERAL", "RUNET_IGEMM_OLD_TILES")      # each collected alone, set to "1"
 SHAPES = ((1, 4, 4), (3, 9, 11), (2, 32, 32), (16, 64, 64), (16, 128, 128), (16, 256, 256))
 MODE_KH = ((FWD, 1), (FWD, 3), (DGRAD, 1), (DGRAD, 3), (DGRAD_T, 1), (DGRAD_T, 3), (CONVT_FWD, 2), (CONVT_DGRAD, 2), (CONVT_DGRAD_T, 2))
 NAME_CIN = (4, 8, 16, 20, 32, 48, 64, 128, 256, 512)
@@ -110,7 +110,7 @@ def collect(lib):
 
 
 def collect_child(knob):
-    """collect() in a fresh process with one knob set to 1 (None: with all three unset)"""
+    """collect() in a fresh process with one knob set to 1 (None: with both unset)"""
     env = {k: v for k, v in os.environ.items() if k not in KNOBS}
     if knob:
         env[knob] = "1"

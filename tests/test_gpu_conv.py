@@ -266,20 +266,6 @@ def test_data_gradient_on_pre_transposed_weights_equals_the_default_path(k, dil)
     assert torch.equal(got, ref) and torch.equal(gott, reft)
 
 
-def test_opt_in_direct_gemm_paths_in_a_child_process():
-    """RUNET_GEMM_TN_DIRECT (register-direct TN GEMM for the F(4x4) and all 1x1 weight gradients; off by default because it slows the step
-    down from the side stream, see csrc/gemm.hip) is read once per process: the F(4x4) and generic convolution tests run again in a
-    child with it set."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, RUNET_GEMM_TN_DIRECT="1")
-    here = os.path.abspath(__file__)
-    r = subprocess.run([sys.executable, "-m", "pytest", here, "-q", "-x", "-k", "winograd_f4 or fwd_dgrad_wgrad", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600, cwd=os.path.dirname(os.path.dirname(here)))
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-
-
 @pytest.mark.parametrize("rows,k,n,scale", [(256, 64, 64, 1.0), (200, 48, 36, 1.0), (1024, 512, 256, 1e-9), (130, 1024, 132, 1.0), (4096, 16, 128, 1e4)])
 def test_split_operand_gemms_against_float64(rows, k, n, scale):
     """csrc/gemm_split.hip: the fp32 position GEMMs on the BF16 matrix cores (x = h + m + l, six bf16 products) are fp32-accurate - error

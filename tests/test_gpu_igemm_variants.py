@@ -1,7 +1,7 @@
 """GPU: every tile variant, loader and route of csrc/conv_igemm.hip and csrc/gemm.hip against tests/igemm_ref.py in float64.
 
 Both files choose their kernel by problem size and the rest of the suite uses small problems, so the large-problem instantiations are forced
-here (runet_igemm_force_variant, runet_igemm_lowp_force_variant, RUNET_GEMM_TN_DIRECT, RUNET_C3_PH) at shapes that are ragged against every
+here (runet_igemm_force_variant, runet_igemm_lowp_force_variant, RUNET_C3_PH) at shapes that are ragged against every
 tile: P = 297 pixels, cin = 20 (K pads to 32), cout = 36 / 68 / 132 / 8 / 4.  tests/test_igemm_ref_cpu.py shows on the CPU that the references
 are torch's float64 operations and that the bound used here notices a dropped tap, channel chunk, a shifted source or a misplaced row at
 each of these shapes.
@@ -296,7 +296,7 @@ def test_gemm_batched_every_branch_against_float64(c):
 @pytest.mark.parametrize("k", R.TN_KN)
 def test_gemm_tn_batched_against_float64(k, rows):
     """split-K slabs of A^T B: three splits, the last one short; rows = 80 takes the loaders without predicates, 77 the general ones.  k and n
-    both > 64: gemm_tn_kernel (with RUNET_GEMM_TN_DIRECT=1: gemm_tn_direct_kernel<2, 2, 2, 2>), otherwise wgrad_kernel<64, 64, 32, 32>."""
+    both > 64: gemm_tn_kernel, otherwise wgrad_kernel<64, 64, 32, 32>."""
     lib, check = L()
     batch, rps = R.TN_BATCH, R.TN_RPS
     splits = -(-rows // rps)
@@ -343,30 +343,16 @@ NINE = [R.NS(route="nine", slabs=5, n=3, h=9, w=11, cin=ci, cin_w=ci, cout=co, k
 
 
 @pytest.mark.parametrize("c", NINE, ids=lambda c: c.id)
-def test_one_by_one_wgrad_direct_shapes_against_float64(c):
-    """1 x 1 weight gradients with cin, cout each <= 32, <= 64, > 64: with RUNET_GEMM_TN_DIRECT=1 (the child run below) these are the nine
-    launch_tn_direct shapes of csrc/gemm.hip, which only runet_conv_wgrad reaches (runet_gemm_tn_batched sends k, n > 64 there and nothing
-    else); without it, wgrad_tile_kernel<1, ..>"""
+def test_one_by_one_wgrad_nine_channel_classes_against_float64(c):
+    """1 x 1 weight gradients with cin, cout each <= 32, <= 64, > 64 (all below the 128 channels of the TN GEMM route): the four
+    wgrad_tile_kernel<1, TM, TN> instances, one or two 64-channel chunks per side, ragged against every one of them"""
     lib, _ = L()
     p = R.wgrad_problem(c)
     ref, mag = p.ref()
     ws = lib.runet_conv_wgrad_workspace_floats(c.n, c.h, c.w, c.cin_w, c.cout, 1, 1)
     assert ws >= c.slabs * c.cin * c.cout
     got = wgrad_run(c, p, ws)
-    within("runet_conv_wgrad", got, ref.to(DEV), R.bound(p.pixels + c.slabs, mag).to(DEV), c.id)      # 5 tiles of 64 pixels (the direct GEMM: 1 slab)
-
-
-def test_register_direct_gemm_kernels_in_a_child_process():
-    """RUNET_GEMM_TN_DIRECT is read once per process: the TN and 1 x 1 weight-gradient cases run again in ONE fresh child with it set"""
-    env = dict(os.environ, RUNET_GEMM_TN_DIRECT="1")
-    here = os.path.abspath(__file__)
-    r = subprocess.run([sys.executable, "-m", "pytest", here, "-q", "-x", "-s", "-m", "gpu", "-k",
-                        "gemm_tn_batched_against or one_by_one_wgrad_direct or wgrad_every_route", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600, cwd=os.path.dirname(os.path.dirname(here)))
-    print("\n".join(ln for ln in r.stdout.splitlines() if "worst" in ln).replace("worst", "worst (RUNET_GEMM_TN_DIRECT=1)"))
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    ran = len(R.TN_KN) * len(R.TN_ROWS) + len(NINE) + len(R.wgrad_cases())
-    assert f"{ran} passed" in r.stdout, r.stdout[-500:]
+    within("runet_conv_wgrad", got, ref.to(DEV), R.bound(p.pixels + c.slabs, mag).to(DEV), c.id)      # 5 tiles of 64 pixels
 
 
 # ------------------------------------------------------------------------------------------------ e. runet_conv_wgrad

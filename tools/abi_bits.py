@@ -2,7 +2,8 @@
 ordered final pass sum_parts of csrc/runet_common.h), the gather adjoints of the bilinear resizes, every entry point of csrc/norm_act.hip
 (BatchNorm statistics, apply and backward: Chan combines in chunk order, first-occurrence max / min, explicit FMAs) and every entry point of
 csrc/attention.hip (the residual-block tail and the attention gate: chunk plans, 16-lane pixel sums, the ordered final passes; ATT_SHAPES
-below) and of csrc/conv_winograd.hip (the fp32 F(2x2) filter transform, convolution and weight gradient; WINO2_CASES).  Every case fills seeded inputs, calls
+below), of csrc/conv_winograd.hip (the fp32 F(2x2) filter transform, convolution and weight gradient; WINO2_CASES) and of the GEMM layer
+(the plain and split-operand GEMMs, the 1x1 / transposed split-operand convolutions, runet_conv_wgrad; GEMM_LAYER_CASES).  Every case fills seeded inputs, calls
 the entry point once through the package's binding and prints one SHA-256 per output tensor (per case for attention.hip).  Two builds of the library compute the same
 bits exactly when their printouts are equal line for line; RUNET_HIP_LIB selects the build (see _lib.py), one fresh process per build:
 
@@ -21,7 +22,8 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import igemm_ref      # noqa: E402  (tests/: the GEMM-layer shapes are the ones its tests use)
 importlib.import_module("eusipco-2026-robust-unet_amd")
 ops = importlib.import_module("eusipco-2026-robust-unet_amd.ops")
 L = importlib.import_module("eusipco-2026-robust-unet_amd._lib")
@@ -482,6 +484,91 @@ WINO2_CASES = [
 ]
 
 
+# ---- the GEMM layer (csrc/gemm.hip, gemm_split.hip, conv_x3.hip and the weight-gradient and GEMM entry points of conv_igemm.hip): which
+# kernel, tile and split count a shape takes is a host decision, and the split count fixes the order of the sums
+def gemm_batched(batch, rows, k, n):
+    a, b, c = rnd(batch, rows, k), rnd(batch, k, n), out(batch, rows, n)
+    check(lib.runet_gemm_batched(p(a), k, rows * k, p(b), k * n, p(c), n, rows * n, batch, rows, k, n, ops.stream()))
+    return [c]
+
+
+def gemm_tn_batched(batch, rows, k, n, rps):
+    a, b, c = rnd(batch, rows, k), rnd(batch, rows, n), out(-(-rows // rps), batch, k, n)
+    check(lib.runet_gemm_tn_batched(p(a), k, rows * k, p(b), n, rows * n, p(c), batch, rows, k, n, rps, ops.stream()))
+    return [c]
+
+
+def conv_wgrad(n, h, w, cin, cin_w, cout, k, dil, tr):
+    """runet_conv_wgrad with the workspace runet_conv_wgrad_workspace_floats asks for; the size is part of the fingerprint"""
+    up = 2 if tr else 1
+    x, dy, dw = rnd(n, h, w, cin), rnd(n, up * h, up * w, cout), out(k, k, cin_w, cout)
+    floats = lib.runet_conv_wgrad_workspace_floats(n, h, w, cin_w, cout, k, k)
+    buf = ws(max(floats, 4))
+    check(lib.runet_conv_wgrad(p(x), cin, p(dy), cout, p(dw), p(buf), floats, n, h, w, cin, cin_w, cout, k, k, dil, tr, ops.stream()))
+    return [dw, torch.tensor([floats])]
+
+
+def gemm_x3_batched(batch, rows, k, n):
+    a, b, c = rnd(batch, rows, k), rnd(batch, k, n), out(batch, rows, n)
+    bp = torch.empty(lib.runet_gemm_x3_pack_elems(batch, k, n), device=DEV, dtype=torch.bfloat16)
+    check(lib.runet_gemm_x3_pack(p(b), k * n, p(bp), batch, k, n, ops.stream()))
+    check(lib.runet_gemm_x3_batched(p(a), k, rows * k, p(bp), p(c), n, rows * n, batch, rows, k, n, ops.stream()))
+    return [c]
+
+
+def gemm_x3_tn_batched(batch, rows, k, n, rps):
+    a, b, c = rnd(batch, rows, k), rnd(batch, rows, n), out(-(-rows // rps), batch, k, n)
+    check(lib.runet_gemm_x3_tn_batched(p(a), k, rows * k, p(b), n, rows * n, p(c), batch, rows, k, n, rps, ops.stream()))
+    return [c]
+
+
+def gemm_x3_tn_convt(n, h, w, cin, cout, rps):
+    x, dy, c = rnd(n, h, w, cin), rnd(n, 2 * h, 2 * w, cout), out(-(-n * h * w // rps), 2, 2, cin, cout)
+    check(lib.runet_gemm_x3_tn_convt(p(x), cin, p(dy), cout, p(c), n, h, w, cin, cout, rps, ops.stream()))
+    return [c]
+
+
+def conv_x3(n, h, w, cin, cout, mode, stats):
+    """runet_conv_x3_pack, then runet_conv_x3 or runet_conv_x3_stats with a bias, accumulating onto old content.  cin: the channels the
+    mode reads; h, w: the low-resolution side of the transposed modes"""
+    taps = 2 if mode in (ops.CONVT_FWD, ops.CONVT_DGRAD) else 1
+    wt = rnd(taps, taps, *((cout, cin) if mode in (ops.CONV_DGRAD, ops.CONVT_DGRAD) else (cin, cout)))
+    sx, sy = (2 if mode == ops.CONVT_DGRAD else 1), (2 if mode == ops.CONVT_FWD else 1)
+    x, b, y = rnd(n, sx * h, sx * w, cin), rnd(cout), rnd(n, sy * h, sy * w, cout)
+    wp = torch.empty(lib.runet_conv_x3_pack_elems(cin, cout, mode), device=DEV, dtype=torch.bfloat16)
+    check(lib.runet_conv_x3_pack(p(wt), p(wp), cin, cout, mode, ops.stream()))
+    head = (p(x), cin, p(wp), p(b), p(y), cout, n, h, w, cin, cout, mode, 1)
+    if not stats:
+        check(lib.runet_conv_x3(*head, ops.stream()))
+        return [y]
+    part = out(lib.runet_conv_x3_stats_parts(n, h, w), cout, 3)
+    check(lib.runet_conv_x3_stats(*head, p(part), ops.stream()))
+    return [y, part]
+
+
+# (n, h, w, cin, cin_w, cout, k, dil, transposed): the nine narrow 1x1 channel classes and the one-case-per-route list of
+# tests/test_gpu_igemm_variants.py, then the routes that list leaves out: the stem, the transposed split-operand GEMM, a TN GEMM of two splits
+WGRAD_SHAPES = [
+    *[(3, 9, 11, ci, ci, co, 1, 1, 0) for ci in (20, 36, 68) for co in (20, 36, 68)],
+    *[(c.n, c.h, c.w, c.cin, c.cin_w, c.cout, c.k, c.dil, c.tr) for c in igemm_ref.wgrad_cases()],
+    (2, 9, 11, 4, 3, 16, 3, 1, 0), (1, 4, 16, 64, 64, 64, 2, 1, 1), (2, 16, 16, 128, 128, 128, 1, 1, 0),
+]
+GEMM_LAYER_CASES = [
+    *[(gemm_batched, (c.batch, c.rows, c.k, c.n)) for c in igemm_ref.gemm_cases()],
+    *[(gemm_tn_batched, (igemm_ref.TN_BATCH, rows, k, n, igemm_ref.TN_RPS)) for rows in igemm_ref.TN_ROWS for k in igemm_ref.TN_KN for n in igemm_ref.TN_KN],
+    *[(conv_wgrad, s) for s in WGRAD_SHAPES],
+    # gemm_nn_x3_kernel<64> (n <= 64) | <128>: 15 x 2 x 36 = 1080 tiles of 128 x 128
+    (gemm_x3_batched, (2, 130, 48, 36)), (gemm_x3_batched, (36, 1800, 16, 132)),
+    # the shapes of tests/test_gpu_x3_edges.py: three splits of 48 rows | the 1x1 weight gradient's two splits of 256 | the transposed one's single slab
+    (gemm_x3_tn_batched, (2, 144, 48, 36, 48)), (gemm_x3_tn_batched, (1, 512, 128, 128, 256)), (gemm_x3_tn_convt, (1, 4, 16, 64, 64, 64)),
+    # 1 x 6 x 10, 48 -> 36 (48 -> 48 for the data gradients) in the four modes, the 1x1 modes with statistics; conv_nn_x3_kernel<128>:
+    # 205 x 2 tiles of 128 x 128 fill 0.8 of a round of 512
+    *[(conv_x3, (1, 6, 10, 48, 36 if mode in (0, 2) else 48, mode, 0)) for mode in (0, 1, 2, 3)],
+    *[(conv_x3, (1, 6, 10, 48, 36 if mode == 0 else 48, mode, 1)) for mode in (0, 1)],
+    (conv_x3, (1, 164, 160, 16, 132, 0, 0)),
+]
+
+
 # (entry point, arguments).  Partial rows each reducing case yields, from its file's chunk rule, against the 16 (hrnet, multiscale,
 # water_index) or 8 (fastscnn, dwsep, dwconv) part-lanes of the final pass:
 CASES = [
@@ -507,6 +594,7 @@ CASES = [
     *[(wino_conv_x3, (*s, st)) for s in WINO_X3_SHAPES for st in (0, 1)],
     *ATTENTION_CASES,
     *WINO2_CASES,
+    *GEMM_LAYER_CASES,
 ]
 
 
