@@ -1,4 +1,5 @@
-"""What the single-node baseline models share (UNet, SegNet, YOLOSeg, SegFormerLite, HRNetWater, WaterNet, MSWNet).
+"""What the single-node baseline models share (DeepLabV3Plus, UNet, SegNet, YOLOSeg, SegFormerLite, HRNetWater, WaterNet, MSWNet, ENet,
+FastSCNN, PSPNet).
 
 Each of them is ONE autograd node with an explicit backward, NHWC inside.  A model file holds the attribute tree (= the reference's state_dict),
 its input check, `<model>_forward(net, x, save)` -> (output, context) and `<model>_backward(net, context, doutput)` -> {parameter name:
@@ -12,8 +13,7 @@ import torch.nn as nn
 
 from . import blocks as B
 from . import ops
-from .deeplab import ConvTranspose2dK4
-from .model import ConvTranspose2d, _Act, _Holder, _logical, _require_cuda
+from .model import _Act, _Holder, _logical, _require_cuda
 
 
 # ------------------------------------------------------------------------------------------------------------ stand-ins (no parameters)
@@ -73,12 +73,10 @@ class FusedNet(nn.Module):
 
     def logical_grad(self, name, g):
         """One entry of <model>_backward's dictionary -> the gradient shaped like the parameter.  The type of the module that owns the
-        parameter decides (model._logical): the weight of a transposed convolution [kh, kw, cin, cout] -> [cin, cout, kh, kw], any other
-        4-D gradient HWIO -> OIHW, the rest as it is.  Views; ops.deliver_grads copies."""
+        parameter decides (model._logical): the weight of a transposed convolution (a holder class with TRANSPOSED_WEIGHT) [kh, kw, cin, cout]
+        -> [cin, cout, kh, kw], any other 4-D gradient HWIO -> OIHW, the rest as it is.  Views; ops.deliver_grads copies."""
         if self._transposed is None:
-            from .enet import ConvTranspose2dK3      # enet.py builds on this module
-            self._transposed = frozenset(f"{k}.weight" for k, m in self.named_modules()
-                                         if isinstance(m, (ConvTranspose2d, ConvTranspose2dK4, ConvTranspose2dK3)))
+            self._transposed = frozenset(f"{k}.weight" for k, m in self.named_modules() if getattr(m, "TRANSPOSED_WEIGHT", False))
         return _logical(g, name in self._transposed)
 
 

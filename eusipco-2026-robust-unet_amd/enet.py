@@ -66,6 +66,8 @@ class ConvTranspose2dK3(_Holder):
     """nn.ConvTranspose2d(cin, cout, 3, stride=2, padding=1, output_padding=1) parameter holder; weight logical [cin, cout, 3, 3], memory
     [3][3][cin][cout]."""
 
+    TRANSPOSED_WEIGHT = True
+
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=2, padding=1, output_padding=1):
         super().__init__()
         assert (kernel_size, stride, padding, output_padding) == (3, 2, 1, 1)

@@ -56,6 +56,8 @@ class Conv2d(_Holder):
 
 
 class ConvTranspose2d(_Holder):
+    TRANSPOSED_WEIGHT = True     # baseline.FusedNet.logical_grad: the weight's memory is [kh, kw, cin, cout], logical [cin, cout, kh, kw]
+
     def __init__(self, in_channels, out_channels, kernel_size=2, stride=2):
         super().__init__()
         assert kernel_size == 2 and stride == 2, "the hot path only has the k2-s2 transposed convolution"

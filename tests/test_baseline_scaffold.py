@@ -1,4 +1,4 @@
-"""CPU: the shell the seven single-node baselines share (baseline.FusedNet): the SyncBatchNorm guard, set_precision, the device check and the
+"""CPU: the shell the eight single-node baselines share (baseline.FusedNet): the SyncBatchNorm guard, set_precision, the device check and the
 physical -> logical layout rule for every 4-D parameter of every model."""
 import importlib
 
@@ -7,7 +7,7 @@ import torch
 
 from conftest import PKG_NAME
 
-MODELS = ("UNet", "SegNet", "YOLOSeg", "SegFormerLite", "HRNetWater", "WaterNet", "MSWNet")
+MODELS = ("DeepLabV3Plus", "UNet", "SegNet", "YOLOSeg", "SegFormerLite", "HRNetWater", "WaterNet", "MSWNet")
 LOW_PRECISION = ("UNet", "SegNet")          # the others run in fp32 only
 HWIO, TRANSPOSED = (3, 2, 0, 1), (2, 3, 0, 1)       # physical -> logical permutes; the second is its own inverse, the first's is (2, 3, 1, 0)
 
@@ -68,4 +68,4 @@ def test_layout_rule_follows_the_owning_module(net):
         assert out.shape == p.shape and out.stride() == p.stride(), (name, tuple(out.shape), tuple(p.shape))
         assert torch.equal(out, g.permute(TRANSPOSED if t else HWIO)), name
     assert seen[False] > 0
-    assert (seen[True] > 0) == (type(net).__name__ in ("UNet", "YOLOSeg", "WaterNet", "MSWNet"))
+    assert (seen[True] > 0) == (type(net).__name__ in ("DeepLabV3Plus", "UNet", "YOLOSeg", "WaterNet", "MSWNet"))

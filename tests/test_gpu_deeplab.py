@@ -235,21 +235,22 @@ def test_deeplab_gradients_under_the_hip_decisions(pkg, n, size, seed, monkeypat
     model.load_state_dict(st)
     model = model.to(DEV).train()
     x, y = pkg.synthetic_batch(n, size, seed=seed)
+    B = importlib.import_module("eusipco-2026-robust-unet_amd.blocks")
     got = {}
-    real = dmod.dl_backward
+    real = dmod.deeplab_backward
 
     def spy(net_, C, dprob):
-        def mask(t):
-            return (t.detach() > 0).permute(0, 3, 1, 2).cpu()
+        def mask(c):        # the ReLU mask from the saved BatchNorm input and coefficients with bn_apply's own arithmetic
+            return (B.bn_apply(c["t"], c["s"], c["h"], None, relu=True) > 0).permute(0, 3, 1, 2).cpu()
         idx, h1, w1 = C["pool"]
-        dec = [mask(C["conv1"]["act"]), DS.pool_flat_3s2(idx.permute(0, 3, 1, 2).cpu().long(), w1)]
-        dec += [mask(C[k]["act"]) for k in ("conv2", "conv3", "conv4")]
-        dec.append(mask(C["aspp"]["aa"]))
-        dec += [mask(C[f"dec{i}"]["act"]) for i in range(4)]
+        dec = [mask(C["conv1"]), DS.pool_flat_3s2(idx.permute(0, 3, 1, 2).cpu().long(), w1)]
+        dec += [mask(C[k]) for k in ("conv2", "conv3", "conv4")]
+        dec.append(mask(C["aspp"]))
+        dec += [mask(C[f"dec{i}"]) for i in range(4)]
         got["dec"] = dec
         return real(net_, C, dprob)
 
-    monkeypatch.setattr(dmod, "dl_backward", spy)
+    monkeypatch.setattr(dmod, "deeplab_backward", spy)
     prob = model(x.to(DEV))
     pkg.bce_loss(prob, y.to(DEV)).backward()
     torch.cuda.synchronize()
