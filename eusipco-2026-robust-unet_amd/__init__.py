@@ -22,6 +22,8 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   DeviceCoastalDataset, DeviceLoader, Augment, prepare_device_dataset, resize_pil_device, resample_tables, nearest_table, rotation_words
   (device_data.py: the dataset built once and kept on the device as bytes, PIL-exact resampling there, batches assembled on the device with
   the augmentation of train_water_segmentation.py:313-321)
+  distance_transform_sq, distance_transform_sq_host, coastline_deviation, boundary_scores, evaluate_coastline (boundary.py: the exact
+  Euclidean distance transform on the device and the coastline-accuracy scores on top of it)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
 Sub-modules are imported lazily so that host-only pieces (data, portable_rng) stay usable
@@ -59,6 +61,8 @@ _LAZY = {
     "analysis_report": "report", "create_coastsat_style_visualization": "report", "error_overlays": "report", "generate_error_maps": "report",
     "DeviceCoastalDataset": "device_data", "DeviceLoader": "device_data", "Augment": "device_data", "prepare_device_dataset": "device_data",
     "resize_pil_device": "device_data", "resample_tables": "device_data", "nearest_table": "device_data", "rotation_words": "device_data",
+    "distance_transform_sq": "boundary", "distance_transform_sq_host": "boundary", "coastline_deviation": "boundary",
+    "boundary_scores": "boundary", "evaluate_coastline": "boundary",
 }
 
 

@@ -97,9 +97,15 @@ class ModelEvaluator:
                       f"IoU: {history['val_iou'][-1]:.4f}, F1: {history['val_f1'][-1]:.4f}")
         return {"best_iou": best_iou, "history": history}
 
-    def evaluate_model(self, model, test_loader):
+    def evaluate_model(self, model, test_loader, boundary_tolerance=None):
+        """boundary_tolerance: None (the reference's metrics and nothing else), or a whole number of pixels: the result gains mean_boundary_iou
+        and mean_bf1, the per-image means of boundary.boundary_scores on `outputs > 0.5` and the masks, one batched call per batch on the
+        tensors where they are (outside the timed span)."""
+        from . import boundary
+        if boundary_tolerance is not None:
+            boundary._check_tolerance(boundary_tolerance)
         model.eval()
-        all_metrics, inference_times = [], []
+        all_metrics, inference_times, edge_scores = [], [], []
         with torch.no_grad():
             for images, masks in test_loader:
                 images, masks = images.to(self.device), masks.to(self.device)
@@ -109,6 +115,10 @@ class ModelEvaluator:
                 torch.cuda.synchronize()
                 inference_times.append((time.time() - t0) / images.shape[0])
                 all_metrics += self.batch_metrics(outputs, masks)
+                if boundary_tolerance is not None:
+                    n, (h, w) = outputs.shape[0], outputs.shape[-2:]
+                    edge_scores += boundary.boundary_scores((outputs > 0.5).reshape(n, h, w), (masks > 0.5).reshape(n, h, w), boundary_tolerance,
+                                                            device=outputs.device)
         results = {}
         for key in all_metrics[0].keys():
             vals = [m[key] for m in all_metrics]
@@ -116,4 +126,7 @@ class ModelEvaluator:
             results[f"std_{key}"] = np.std(vals)
         results["avg_inference_time"] = np.mean(inference_times)
         results["total_samples"] = len(all_metrics)
+        if boundary_tolerance is not None:
+            results["mean_boundary_iou"] = np.mean([m["boundary_iou"] for m in edge_scores])
+            results["mean_bf1"] = np.mean([m["bf1"] for m in edge_scores])
         return results

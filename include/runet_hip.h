@@ -1112,6 +1112,45 @@ int runet_error_overlays(const float* images, const float* prob, const float* ma
                          float mean1, float mean2, float std0, float std1, float std2, const double* colours, float* vis, double* overlay,
                          float* err, long* counts, double* sums, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- exact Euclidean distance transform and the statistics of a distance map (csrc/edt.hip, boundary.py): the primitive behind the
+ *      coastline-accuracy scores (mean / RMS / worst deviation, share within t pixels, boundary F-score, Boundary IoU).  The reference has
+ *      region scores only (Main_Final.py:527-547 per image, train_water_segmentation.py:355 for the empty union); nothing there measures a
+ *      coastline.  The squared distance between two pixels is an integer, so every result below is defined exactly: no ties, no tolerance
+ *      (tests/edt_ref.py restates the rules in numpy).  All arithmetic of the transform is integer, 64-bit where parabola intersections
+ *      are formed; the one floating-point sum has a fixed order; integer atomics only.  All validation happens on the host before any
+ *      device work; no call synchronises the host.  1 <= h, w <= 32768, so that (h - 1)^2 + (w - 1)^2 < RUNET_EDT_NONE.
+ * runet_edt_workspace_bytes: host only; the BYTES either call below needs for n images of h x w (2 per pixel, at least 8 per 1024 pixels);
+ *   -1: bad shape, or a batch whose grid would not fit.
+ * runet_edt_sq_u8: mask uint8, image i's pixel (y, x) at mask[i * image_stride + y * row_stride + x] (row_stride >= w; image_stride >= an
+ *   image's extent where n > 1), any byte address.  A feature pixel is a non-zero byte (invert == 0) or a zero byte (invert != 0).
+ *   d2, dense int32 [n][h][w]:  d2[i][y][x] = min over the feature pixels (y', x') of image i of (x - x')^2 + (y - y')^2, so 0 on a feature
+ *   pixel itself, and RUNET_EDT_NONE everywhere in an image without a feature pixel.  Only pixels inside the image are features: the frame
+ *   around it is neither water nor land.
+ *   Two launches.  Pass 1, a wave per row: g = |x - x'| to the nearest feature of the same row, -1 where the row has none (a state of its
+ *   own: such a row never enters the arithmetic of pass 2).  Pass 2, a thread per column, 64 adjacent columns per wave: the lower envelope
+ *   of the parabolas (y - y')^2 + g(y')^2 over the rows y' with g >= 0, first a stack of (row, g, first row owned) built top to bottom, then
+ *   the column filled bottom to top.  It runs in place: a column of d2 holds g, then the stack, then the result; the workspace holds the
+ *   first-row-owned values, uint16 [n][h][w].  Every loop is bounded by h or w.  Two runs give the same bytes.
+ *   1 mask byte read per pixel; d2 written twice and read once in pass 1, read once and written once in pass 2 plus the stack traffic
+ *   (at most 6 bytes written and 6 read per stack entry).
+ * runet_edt_stats: one pass over d2 (dense int32 [n][h][w]).  select: dense uint8 [n][h][w], non-zero = the pixel takes part; NULL = every
+ *   pixel does.  tol_sq: HOST array of n_tol squared tolerances (each >= 0), 0 <= n_tol <= 8, read during the call; may be NULL when
+ *   n_tol == 0.  counts, device 64-bit [n][4 + n_tol], cleared by the call:
+ *     [0] selected pixels;  [1] selected pixels with d2 == RUNET_EDT_NONE, which count in nothing below;  [2] max d2;  [3] sum of d2;
+ *     [4 + t] pixels with d2 <= tol_sq[t].
+ *   sums, device float64 [n] = S, the sum of e = sqrt((double)d2) (correctly rounded, np.sqrt) over the same pixels, in this fixed order:
+ *     pixels are cut into chunks of 1024, chunk b = [1024 b, 1024 (b + 1)); e is 0.0 for a pixel that is not selected, is RUNET_EDT_NONE
+ *     or lies beyond h * w.  In a chunk, t = 0..255: d[t] = ((e[t] + e[t + 256]) + e[t + 512]) + e[t + 768]; the 256 d fall into four
+ *     groups of 64 consecutive t, each folded by a[t] += a[t + o] for o = 32, 16, 8, 4, 2, 1 to a[0]; chunk sum = ((a0 + a1) + a2) + a3.
+ *     Then lane l = 0..63 adds the chunk sums l, l + 64, l + 128, ... in that order from 0.0, and the 64 lanes fold the same way.
+ *   workspace: the chunk sums, 8-byte aligned.  4 bytes (+ 1 with select) read per pixel; nothing written but counts, sums and chunk sums. */
+#define RUNET_EDT_NONE 2147483647
+long runet_edt_workspace_bytes(int n, int h, int w);
+int runet_edt_sq_u8(const unsigned char* mask, int n, int h, int w, long row_stride, long image_stride, int invert, int* d2, void* workspace,
+                    long workspace_bytes, void* stream);
+int runet_edt_stats(const int* d2, const unsigned char* select, int n, int h, int w, const int* tol_sq, int n_tol, long* counts, double* sums,
+                    void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
