@@ -24,6 +24,8 @@ Public surface (mirrors /root/reference/Main_Final.py for the hot path):
   the augmentation of train_water_segmentation.py:313-321)
   distance_transform_sq, distance_transform_sq_host, coastline_deviation, boundary_scores, evaluate_coastline (boundary.py: the exact
   Euclidean distance transform on the device and the coastline-accuracy scores on top of it)
+  label_components, label_components_host, dense_labels, water_bodies, clean_water_mask (components.py: connected-component labelling on
+  the device, the table of water bodies and the area filter that cleans a water mask in front of the coastline)
 plus the MI355X additions: FusedAdam, sigmoid-free fused BCE loss, GradAllReducer (RCCL).
 
 Sub-modules are imported lazily so that host-only pieces (data, portable_rng) stay usable
@@ -63,6 +65,8 @@ _LAZY = {
     "resize_pil_device": "device_data", "resample_tables": "device_data", "nearest_table": "device_data", "rotation_words": "device_data",
     "distance_transform_sq": "boundary", "distance_transform_sq_host": "boundary", "coastline_deviation": "boundary",
     "boundary_scores": "boundary", "evaluate_coastline": "boundary",
+    "label_components": "components", "label_components_host": "components", "dense_labels": "components", "water_bodies": "components",
+    "clean_water_mask": "components",
 }
 
 

@@ -556,6 +556,8 @@ def save_extraction_result(result, output_dir, report=False):
     doc = {"image_path": result["image_path"], "image_size": result["image_size"], "coastlines": result["coastlines"],
            "coastline_count": result["coastline_count"], "dilation_size": result.get("dilation_size", 5),
            "extraction_time": result["extraction_time"]}
+    if "cleanup" in result:
+        doc["cleanup"] = result["cleanup"]
     with open(os.path.join(output_dir, f"{base}_coastlines.json"), "w", encoding="utf-8") as fh:
         json.dump(doc, fh, indent=2, ensure_ascii=False)
     if report:
@@ -563,6 +565,25 @@ def save_extraction_result(result, output_dir, report=False):
         if "report" not in result:
             result["report"] = _report.analysis_report(result)
         _report.create_coastsat_style_visualization(result, output_dir, report=result["report"])
+
+
+def _check_cleanup(min_water_area, min_land_area, connectivity):
+    """-> (min_water, min_land, connectivity) as clean_water_mask takes them; ValueError otherwise"""
+    from . import components as _cc
+    return (_cc._check_area(min_water_area, "min_water_area"), _cc._check_area(min_land_area, "min_land_area"),
+            _cc._check_connectivity(connectivity))
+
+
+def _clean_in_place(water, min_water, min_land, connectivity, counts):
+    """water: dense device uint8 [h, w], cleaned where it lies (components.clean_water_mask's two steps, frame components exempt);
+    counts: device int64 [1, 4], the four figures of its info.  Nothing is read back on the device route."""
+    from . import components as _cc
+    if _cc._host_route():
+        out, c = _cc._clean_host(water.cpu().numpy()[None], min_water, min_land, connectivity, True)
+        water.copy_(torch.from_numpy(out[0]))
+        counts.copy_(torch.from_numpy(c))
+    else:
+        _cc._clean_device(water[None], min_water, min_land, connectivity, True, counts)
 
 
 def _raise_nonfinite(count):
@@ -697,9 +718,15 @@ class CoastlineExtractor:
         return (mask, soft) if return_prob else mask
 
     # -- reference surface -----------------------------------------------------------------------
-    def extract_coastline_contours(self, water_mask, dilation_kernel_size=5):
-        """-> (coastlines, coastline_mask) as predict_coastline.py:583-618; water_mask: numpy array or device tensor, uint8."""
+    def extract_coastline_contours(self, water_mask, dilation_kernel_size=5, min_water_area=0, min_land_area=0, connectivity=8):
+        """-> (coastlines, coastline_mask) as predict_coastline.py:583-618; water_mask: numpy array or device tensor, uint8.
+        min_water_area / min_land_area > 0: a copy of the mask is cleaned first (components.clean_water_mask), on the device."""
+        min_water, min_land, connectivity = _check_cleanup(min_water_area, min_land_area, connectivity)
         mask = _dev_u8(water_mask, self.device)
+        if min_water or min_land:
+            if isinstance(water_mask, torch.Tensor) and mask.data_ptr() == water_mask.data_ptr():
+                mask = mask.clone()
+            _clean_in_place(mask, min_water, min_land, connectivity, torch.empty((1, 4), device=mask.device, dtype=torch.int64))
         coast, _, _ = dilate_diff(mask, dilation_kernel_size)
         rule = self.simplify_rule
         if rule == "exact":
@@ -715,14 +742,20 @@ class CoastlineExtractor:
         return _finish_contours(contours, simplified, 10, 0.002, rule), host[head:].reshape(coast.shape).copy()
 
     def extract_coastline_from_image(self, image=None, output_dir=None, dilation_size=5, tiled=False, tile=512, halo=64, batch=8, bands=None,
-                                     mode="water", report=False):
+                                     mode="water", report=False, min_water_area=0, min_land_area=0, connectivity=8):
         """predict_coastline.py:366-423.  `image`: a path, a PIL image or a uint8 [H, W, 3] array as before, or a band raster (_as_bands),
         which is enhanced on the device (scene.py, `mode`): tiled, the enhanced scene feeds the tiles directly; resized, it is downloaded
         once for the PIL bilinear resize, the reference's order.
         report=True: the result gains "report" (report.analysis_report's arrays), computed from the masks and the scene while they are on
         the device, before the download; a raster's background is its "display"-mode image, its histograms are NDWI from four bands on.
-        With output_dir the analysis PNG is written too (matplotlib)."""
+        With output_dir the analysis PNG is written too (matplotlib).
+        min_water_area / min_land_area > 0: the predicted water mask is cleaned on the device before the band is made
+        (components.clean_water_mask with `connectivity`; components that touch the image frame stay), so that water_mask, water_pixels,
+        the band, the contours and the report all describe the cleaned mask; the result gains "cleanup", the filter's four counts and
+        the three parameters.  The counts ride in the one download.  With both at 0 (the default) nothing is launched or added."""
         ellipse_spans(dilation_size)
+        min_water, min_land, connectivity = _check_cleanup(min_water_area, min_land_area, connectivity)
+        cleanup = bool(min_water or min_land)
         rule = self.simplify_rule
         if tiled:
             self._check_size(tile, "tile")
@@ -743,8 +776,10 @@ class CoastlineExtractor:
         if rule == "exact":
             _check_exact_shape(h, w)
         # one device buffer for everything that goes back: water mask | coastline mask | the two counts -> one download
+        # (with a cleanup: | its four 64-bit counts)
         seg = (h * w + 15) // 16 * 16
-        buf = torch.empty(2 * seg + 16, device=self.device, dtype=torch.uint8)
+        tail = 2 * seg + 16 + (32 if cleanup else 0)
+        buf = torch.empty(tail, device=self.device, dtype=torch.uint8)
         water, coast = buf[:h * w].view(h, w), buf[seg:seg + h * w].view(h, w)
         counts = buf[2 * seg:2 * seg + 8].view(torch.int32)
         if scene is not None:
@@ -754,6 +789,8 @@ class CoastlineExtractor:
             self._predict_tiled(_dev_u8(np.array(pil, dtype=np.uint8), self.device), tile, halo, batch, out=water)
         else:
             self._predict_resized(pil, out=water)
+        if cleanup:
+            _clean_in_place(water, min_water, min_land, connectivity, buf[2 * seg + 16:tail].view(torch.int64).view(1, 4))
         dilate_diff(water, dilation_size, coast=coast, counts=counts)
         on_device = coast.is_cuda and DEVICE_CONTOURS
         packed, simplified = _coastlines_packed(coast, 10, 0.002, rule) if on_device else (None, False)
@@ -775,13 +812,17 @@ class CoastlineExtractor:
         coast_np = host[seg:seg + h * w].reshape(h, w).copy()
         n_water, n_coast = (int(v) for v in host[2 * seg:2 * seg + 8].view(np.int32))
         if on_device:
-            contours = [] if packed is None else _unpack_contours(host[2 * seg + 16:].view(np.int32))
+            contours = [] if packed is None else _unpack_contours(host[tail:].view(np.int32))
             coastlines = _finish_contours(contours, simplified, 10, 0.002, rule)
         else:
             coastlines = coastlines_from_mask(coast_np, rule=rule)
         result = {"image_path": path if path is not None else "image", "image_size": (w, h), "water_mask": water_np,
                   "coastline_mask": coast_np, "coastlines": coastlines, "coastline_count": len(coastlines), "dilation_size": int(dilation_size),
                   "extraction_time": str(datetime.now()), "water_pixels": n_water, "coastline_pixels": n_coast}
+        if cleanup:
+            from .components import INFO_KEYS
+            result["cleanup"] = dict(zip(INFO_KEYS, (int(v) for v in host[2 * seg + 16:tail].view(np.int64))), min_water_area=min_water,
+                                     min_land_area=min_land, connectivity=connectivity)
         if arrays is not None:
             result["report"] = _report._with_statistics(arrays, h * w, n_water, n_coast, coastlines)
         if output_dir:

@@ -1151,6 +1151,50 @@ int runet_edt_sq_u8(const unsigned char* mask, int n, int h, int w, long row_str
 int runet_edt_stats(const int* d2, const unsigned char* select, int n, int h, int w, const int* tol_sq, int n_tol, long* counts, double* sums,
                     void* workspace, long workspace_bytes, void* stream);
 
+/* ---- connected components of a byte mask, their areas, and the area filter in front of the coastline (csrc/ccl.hip, components.py).  The
+ *      reference traces coastlines on `dilated - water` with cv2.findContours(RETR_EXTERNAL) and keeps every contour of more than 10 points
+ *      (predict_coastline.py:583-618) from a mask thresholded at Main_Final.py:521: every speck of water inland and every hole of land at
+ *      sea becomes a coastline.  These calls stand in front of that step.  Everything is an integer with an exact definition
+ *      (tests/ccl_ref.py restates the rules with a flood fill): there is no tolerance.
+ *      Determinism: every merge is an integer minimum (atomicMin on a parent), every count an integer sum, every box an integer minimum or
+ *      maximum, so the result is independent of scheduling by construction: two runs give the same bytes.  32-bit integer atomics on vector
+ *      memory only; no cooperative launch, no grid-wide barrier, no loop that waits on another workgroup: parents only decrease, so every
+ *      loop descends and ends.  All validation (null pointers, connectivity, shapes, workspace size, alignment) happens on the host before
+ *      any device work and returns non-zero with a runet_last_error() text; every call is asynchronous on `stream`; none synchronises the
+ *      host.  1 <= h, w <= 32768, so h * w <= 2^30 and index + 1 fits int32.  Pixel (y, x) of an image has the linear index y * w + x;
+ *      indices and labels are per image, and the images of a batch are independent.
+ * Definitions.  A feature pixel is a non-zero byte (invert == 0) or a zero byte (invert != 0).  Two feature pixels of one image are
+ *   neighbours when |dx| + |dy| == 1 (connectivity 4) or max(|dx|, |dy|) == 1 (connectivity 8); only pixels inside the image exist, so a
+ *   row's last pixel and the next row's first are not neighbours.  A component is a class of the transitive closure of "neighbour".  Its
+ *   root is its pixel of smallest linear index, its label is root index + 1.
+ * runet_ccl_workspace_bytes: host only; the BYTES runet_ccl_label_u8 and runet_ccl_table need for n images of h x w (4 per pixel + 4 per
+ *   1024 pixels, rounded up to 8); -1: bad shape, or a batch that one call cannot take (n * h * w > 2^40 or a grid that would not fit).
+ * runet_ccl_label_u8: mask uint8, image i's pixel (y, x) at mask[i * image_stride + y * row_stride + x] (row_stride >= w; image_stride >= an
+ *   image's extent where n > 1), any byte address: the stride contract of runet_edt_sq_u8, so a crop of a larger mask is read in place.
+ *   connectivity: 4 or 8.  labels, dense int32 [n][h][w]: 0 on a non-feature pixel, otherwise the label of the pixel's component.
+ *   Three launches: a block labels a 64 x 64 tile in LDS and writes every pixel's tile-local root as a global index; a thread per pixel of
+ *   the tile border rows and columns unites it with its neighbours across the border (the diagonal pairs at tile corners included); every
+ *   pixel walks to its root.  1 mask byte read per pixel; labels written once, read once and written again where the root changed.
+ * runet_ccl_areas: labels as written above.  areas, dense int32 [n][h][w], and frame, dense uint8 [n][h][w], are written whole by the call:
+ *   at a component's root pixel (linear index label - 1) areas holds the component's pixel count and frame its contact with the image's
+ *   edge, bit 0 = a pixel with y == 0, bit 1 = y == h - 1, bit 2 = x == 0, bit 3 = x == w - 1; every other pixel holds 0 in both.
+ * runet_ccl_filter_u8: a component is SELECTED when area < min_area (strictly) and, with keep_frame != 0, frame == 0.  Every pixel of a
+ *   selected component gets the byte `value` (0..255) in mask_out, dense uint8 [n][h][w]; no other byte of mask_out is touched.  counts,
+ *   64-bit [n][2], written whole by the call: {selected components, their pixels}.  min_area >= 0; 0 selects nothing.
+ * runet_ccl_table: n_components, 64-bit [n] = the number of components of each image, exact even beyond capacity.  table, dense int32
+ *   [n][capacity][8]: row k < min(capacity, n_components[i]) of image i describes the component of k-th smallest label as
+ *   {label, area, x0, y0, x1, y1, frame, 0}, [x0, x1] x [y0, y1] the inclusive bounding box.  Rows from n_components[i] on, and everything
+ *   past `capacity` rows, are not written.  capacity >= 0; with capacity == 0 only the count is made and table may be NULL.
+ *   workspace: the roots before each chunk of 1024 pixels and every root's rank, 8-byte aligned. */
+long runet_ccl_workspace_bytes(int n, int h, int w);
+int runet_ccl_label_u8(const unsigned char* mask, int n, int h, int w, long row_stride, long image_stride, int invert, int connectivity, int* labels,
+                       void* workspace, long workspace_bytes, void* stream);
+int runet_ccl_areas(const int* labels, int n, int h, int w, int* areas, unsigned char* frame, void* stream);
+int runet_ccl_filter_u8(const int* labels, const int* areas, const unsigned char* frame, int n, int h, int w, int min_area, int keep_frame,
+                        int value, unsigned char* mask_out, long* counts, void* stream);
+int runet_ccl_table(const int* labels, const int* areas, const unsigned char* frame, int n, int h, int w, int capacity, long* n_components,
+                    int* table, void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
