@@ -254,6 +254,21 @@ def _edge(part):
     return FUSED_RB_EDGES and part in RB_EDGE_PARTS
 
 
+# The 64 -> 1 output head folded into the tail of the ResidualBlock in front of it (exact, as the edges above; both need them):
+#   fwd  rb_out forms the logit and the probability from the values it stores: no outc_fwd launch, no re-read of `out` (runet_rb_out_head)
+#   bwd  outc_bwd leaves dl [P] instead of dx [P][C] (runet_outc_bwd_dl); rb_bwd1 forms w[c] * dl[p] in its load (runet_rb_bwd1_rank1)
+# RUNET_NO_FUSED_HEAD=1 restores the separate runet_outc_fwd / runet_outc_bwd launches.  Read at call time.
+FUSED_HEAD = os.environ.get("RUNET_NO_FUSED_HEAD", "0") != "1"
+HEAD_PARTS = frozenset(("fwd", "bwd"))                  # narrowed to time one part alone, as RB_EDGE_PARTS
+
+
+def fuses_head(part, c):
+    """part "fwd": rb_forward(head=...) takes the head along; "bwd": rb_backward(head_grad=...) takes outc_backward_dl's pair"""
+    if not (FUSED_HEAD and part in HEAD_PARTS and lib.runet_rb_out_head_supported(c)):      # C = 64; any other width keeps the separate launches
+        return False
+    return _edge("out") if part == "fwd" else _edge("bwd1")
+
+
 def chan_sum(x, out):
     """Per-channel sum over all pixels (bias gradients).  Nothing in the backward chain waits for a bias gradient, so inside the backward
     pass (ops.wgrad_side_stream active) the two launches go to the weight-gradient stream like the weight gradients themselves."""
@@ -323,9 +338,11 @@ class RBParams:
         self.cin_w = w1.shape[2]
 
 
-def rb_forward(x, p: RBParams, training, mask=None, save=True, stats_hook=None, pool=False):
+def rb_forward(x, p: RBParams, training, mask=None, save=True, stats_hook=None, pool=False, head=None):
     """x: [N,H,W,Cx] with Cx >= cin_w (stem: RGB zero-padded to 4).  -> (out [N,H,W,C], ctx or None)
-    pool: the block feeds MaxPool2d(2) -> (out, ctx, pooled [N,H/2,W/2,C], winner bytes); ctx keeps the bytes as "pool_idx"."""
+    pool: the block feeds MaxPool2d(2) -> (out, ctx, pooled [N,H/2,W/2,C], winner bytes); ctx keeps the bytes as "pool_idx".
+    head: dict(w=, b=, want_logit=) of the 64 -> 1 output head behind the block (the caller asked fuses_head("fwd", C)): receives "prob" and
+    "logit" (or None), what outc_forward(out, w, b, want_logit) returns."""
     n, h, w, _ = x.shape
     c = p.w1.shape[3]
     cr = p.w0p.shape[3]
@@ -395,9 +412,17 @@ def rb_forward(x, p: RBParams, training, mask=None, save=True, stats_hook=None, 
         if pool:
             pooled = ops.empty_nhwc(n, h // 2, w // 2, c, x)
             pool_idx = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.uint8)
-    check(lib.runet_rb_out_ex(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r), _ptr(ss), _ptr(hs),
-                              out.data_ptr(), ops.ld(out), _ptr(relu_bits), _ptr(pooled), ops.ld(pooled) if pooled is not None else 0, _ptr(pool_idx),
-                              n, h, w, c, st))
+    if head is not None:
+        assert not pool and fuses_head("fwd", c)
+        head["prob"] = torch.empty((n, 1, h, w), device=x.device, dtype=torch.float32)
+        head["logit"] = torch.empty((n, 1, h, w), device=x.device, dtype=torch.float32) if head["want_logit"] else None
+        check(lib.runet_rb_out_head(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r), _ptr(ss), _ptr(hs),
+                                    out.data_ptr(), ops.ld(out), _ptr(relu_bits), head["w"].data_ptr(), head["b"].data_ptr(), _ptr(head["logit"]),
+                                    head["prob"].data_ptr(), n, h, w, c, st))
+    else:
+        check(lib.runet_rb_out_ex(t2.data_ptr(), ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), r.data_ptr(), ops.ld(r), _ptr(ss), _ptr(hs),
+                                  out.data_ptr(), ops.ld(out), _ptr(relu_bits), _ptr(pooled), ops.ld(pooled) if pooled is not None else 0,
+                                  _ptr(pool_idx), n, h, w, c, st))
     if pool and pooled is None:
         pooled, pool_idx = maxpool_forward(out)
     if not save:
@@ -416,10 +441,11 @@ def rb_a1(ctx):
     return bn_apply(ctx["t1"], ctx["s1"], ctx["h1"], ctx["mask"], relu=True)
 
 
-def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None):
+def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None, head_grad=None):
     """Parameter gradients go to `sink` (names prefixed with `pre`).  -> dx or None
     dpool, pool_idx: the gradient of the block's pooled output and the pool's winner bytes; the block's incoming gradient is then
-    dout + maxpool_backward(dpool, pool_idx).  dout is left unmodified unless the edges are unfused (it is then accumulated into)."""
+    dout + maxpool_backward(dpool, pool_idx).  dout is left unmodified unless the edges are unfused (it is then accumulated into).
+    head_grad: (dl [P], w [C]) of outc_backward_dl in place of dout (None): the incoming gradient is w[c] * dl[p], formed in rb_bwd1's load."""
     p: RBParams = ctx["p"]
     x, r, t1, a1, t2, out = ctx["x"], ctx["r"], ctx["t1"], ctx["a1"], ctx["t2"], ctx["out"]
     n, h, w, c = out.shape
@@ -434,9 +460,14 @@ def rb_backward(ctx, dout, sink, pre="", need_dx=True, dpool=None, pool_idx=None
     relu_bits = ctx.get("relu_bits") if _edge("bwd1") else None
     if dpool is not None and not _edge("bwd1"):
         dout, dpool = maxpool_backward(dpool, pool_idx, dx=dout), None
-    check(lib.runet_rb_bwd1_ex(dout.data_ptr(), ops.ld(dout), _ptr(dpool), ops.ld(dpool) if dpool is not None else 0,
-                               pool_idx.data_ptr() if dpool is not None else None, out.data_ptr(), ops.ld(out), _ptr(relu_bits), t2.data_ptr(),
-                               ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), n, h, w, c, st))
+    if head_grad is not None:
+        assert dout is None and dpool is None and relu_bits is not None
+        check(lib.runet_rb_bwd1_rank1(head_grad[0].data_ptr(), head_grad[1].data_ptr(), relu_bits.data_ptr(), t2.data_ptr(), ops.ld(t2), A.data_ptr(),
+                                      B.data_ptr(), sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), n, h, w, c, st))
+    else:
+        check(lib.runet_rb_bwd1_ex(dout.data_ptr(), ops.ld(dout), _ptr(dpool), ops.ld(dpool) if dpool is not None else 0,
+                                   pool_idx.data_ptr() if dpool is not None else None, out.data_ptr(), ops.ld(out), _ptr(relu_bits), t2.data_ptr(),
+                                   ops.ld(t2), A.data_ptr(), B.data_ptr(), sa.data_ptr(), dv.data_ptr(), ops.ld(dv), dq.data_ptr(), n, h, w, c, st))
     dsm = torch.empty((P, 2), device=dev, dtype=torch.float32)
     dwsa = sink.buf(pre, [("sa.conv1.weight", (7, 7, 2, 1))])
     ws = scratch(lib.runet_sa_conv7_bwd_workspace_floats(n, h, w), dev)
@@ -973,6 +1004,17 @@ def outc_backward(dprob, prob, x, w, sink, pre=""):
     check(lib.runet_outc_bwd(dprob.data_ptr(), prob.data_ptr(), x.data_ptr(), ops.ld(x), w.data_ptr(), dx.data_ptr(), ops.ld(dx), ws.data_ptr(),
                              dw_db.data_ptr(), n * h * wd, c, ops.stream()))
     return dx
+
+
+def outc_backward_dl(dprob, prob, x, sink, pre=""):
+    """outc_backward without the data gradient: the parameter gradients, and -> dl [P], the logit's gradient, for rb_backward(head_grad=(dl, w))"""
+    n, h, wd, c = x.shape
+    dl = torch.empty(n * h * wd, device=x.device, dtype=torch.float32)
+    dw_db = sink.buf(pre, [("weight", (1, 1, c, 1)), ("bias", (1,))])
+    ws = _ws(n, h * wd, c, x.device)
+    check(lib.runet_outc_bwd_dl(dprob.data_ptr(), prob.data_ptr(), x.data_ptr(), ops.ld(x), dl.data_ptr(), ws.data_ptr(), dw_db.data_ptr(), n * h * wd, c,
+                                ops.stream()))
+    return dl
 
 
 # =============================================================================== HRNet-Water head and fusion branches (csrc/hrnet.hip)

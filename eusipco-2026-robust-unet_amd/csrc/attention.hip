@@ -171,12 +171,22 @@ __global__ __launch_bounds__(256) void sa_conv7_kernel(const float* __restrict__
 __device__ __forceinline__ unsigned int relu_bits4(const f32x4 o) {
     return (o[0] > 0.f ? 1u : 0u) | (o[1] > 0.f ? 2u : 0u) | (o[2] > 0.f ? 4u : 0u) | (o[3] > 0.f ? 8u : 0u);
 }
+// A lane's four terms of the 64 -> 1 head: four rounded products, summed left to right.  Contraction is off because outc_fwd_kernel and the
+// head inside rb_out must round alike whatever stands around the expression (as written, one compiled to packed multiplies and adds, the
+// other to a chain of FMAs: logits one ulp apart).
+__device__ __forceinline__ float head_dot4(const f32x4 v, const f32x4 k) {
+#pragma clang fp contract(off)
+    return v[0] * k[0] + v[1] * k[1] + v[2] * k[2] + v[3] * k[3];
+}
 // The edge kernels stay at the 8 waves per SIMD of the kernels they extend (64 VGPRs; unconstrained they come out at 65-71, one occupancy step lower).
 #define RB_EDGE_WAVES __attribute__((amdgpu_waves_per_eu(8, 8)))
-template <bool BITS>
+// HEAD (C = 64 only: the 16 lanes of a pixel are the 16 lanes of outc_fwd_kernel): the 64 -> 1 output convolution and its sigmoid on the
+// values just stored - outc_fwd_kernel's expressions in its order, without its read of `out`.
+template <bool BITS, bool HEAD = false>
 __device__ __forceinline__ void rb_out_body(const float* t2, int ld, const float* A, const float* B, const float* sa, const float* r, int ldr,
                                             const float* rs, const float* rh, float* out, int ldo, unsigned char* bits, int HW, int C,
-                                            int pix_per_chunk) {
+                                            int pix_per_chunk, const float* hw = nullptr, const float* hb = nullptr, float* logit = nullptr,
+                                            float* prob = nullptr) {
     const int cvec = C / 4, rows = TPB / cvec, tid = threadIdx.x;
     const int col = tid % cvec, row = tid / cvec;
     if (row >= rows) return;
@@ -187,6 +197,8 @@ __device__ __forceinline__ void rb_out_body(const float* t2, int ld, const float
     f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, h4 = {0.f, 0.f, 0.f, 0.f};
     if (rs) { s4 = *reinterpret_cast<const f32x4*>(rs + c); h4 = *reinterpret_cast<const f32x4*>(rh + c); }
     const long ib = (long)n * HW;
+    f32x4 k = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (HEAD) k = *reinterpret_cast<const f32x4*>(hw + c);
     for (int p = p0 + row; p < p1; p += rows) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(t2 + (ib + p) * ld + c);
         const f32x4 res = *reinterpret_cast<const f32x4*>(r + (ib + p) * ldr + c) * s4 + h4;
@@ -196,6 +208,16 @@ __device__ __forceinline__ void rb_out_body(const float* t2, int ld, const float
         for (int q = 0; q < 4; ++q) o[q] = fmaxf(o[q], 0.f);
         *reinterpret_cast<f32x4*>(out + (ib + p) * ldo + c) = o;
         if constexpr (BITS) bits[(ib + p) * cvec + col] = (unsigned char)relu_bits4(o);
+        if constexpr (HEAD) {
+            float acc = 0.f;
+            acc += head_dot4(o, k);
+            acc = grp_sum16(acc);                    // the pixel's 16 lanes share p: all of them are here
+            if (col == 0) {
+                const float l = acc + hb[0];
+                if (logit) logit[ib + p] = l;
+                prob[ib + p] = sigmoidf_(l);
+            }
+        }
     }
 }
 __global__ __launch_bounds__(TPB) void rb_out_kernel(const float* __restrict__ t2, int ld, const float* __restrict__ A,
@@ -211,6 +233,17 @@ __global__ __launch_bounds__(TPB) void rb_out_bits_kernel(const float* __restric
                                                           const float* __restrict__ rh, float* __restrict__ out, int ldo,
                                                           unsigned char* __restrict__ bits, int HW, int C, int pix_per_chunk) {
     rb_out_body<true>(t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, bits, HW, C, pix_per_chunk);
+}
+// rb_out of the block in front of the 64 -> 1 head, C = 64: an instance of its own, the other blocks' launches keep their kernels
+template <bool BITS>
+__global__ __launch_bounds__(TPB) void rb_out_head_kernel(const float* __restrict__ t2, int ld, const float* __restrict__ A,
+                                                          const float* __restrict__ B, const float* __restrict__ sa,
+                                                          const float* __restrict__ r, int ldr, const float* __restrict__ rs,
+                                                          const float* __restrict__ rh, float* __restrict__ out, int ldo,
+                                                          unsigned char* __restrict__ bits, int HW, int pix_per_chunk,
+                                                          const float* __restrict__ hw, const float* __restrict__ hb,
+                                                          float* __restrict__ logit, float* __restrict__ prob) {
+    rb_out_body<BITS, true>(t2, ld, A, B, sa, r, ldr, rs, rh, out, ldo, bits, HW, 64, pix_per_chunk, hw, hb, logit, prob);
 }
 // rb_out of an encoder block whose output feeds MaxPool2d(2): the thread walks the POOLED pixels of its chunk, computes the four outputs of
 // each 2x2 window with the expression above, stores them to `out`, and stores their maximum (pixel stride ldp) and the winner bytes (dense, C
@@ -275,14 +308,16 @@ __global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_out_pool_kernel(const fl
 // g = dout, and the block edges ride along.  POOL: g = dout + the pooled gradient's term, rebuilt from (dpool, pidx) by pooled_grad4 - the one
 // addition runet_maxpool2_bwd(accumulate=1) performs on dout, which is left unmodified.  BITS: the ReLU mask comes from rb_out's relu_bits (a
 // byte per 4 channels) instead of a read of `out`; else from `out` (NULL: no ReLU behind the attention - standalone SpatialAttention).
-// W: full-resolution width (POOL only).
-template <bool POOL, bool BITS>
+// W: full-resolution width (POOL only).  RANK1: g[p][c] = hw[c] * dl[p], the 64 -> 1 head's data gradient as outc_bwd_partial forms it
+// (the same fp32 product), never stored; dout is not read.
+template <bool POOL, bool BITS, bool RANK1 = false>
 __global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_bwd1_ex_kernel(const float* __restrict__ dout, int lddo, const float* __restrict__ dpool, int ldp,
                                                          const unsigned char* __restrict__ pidx, const float* __restrict__ out, int ldo,
                                                          const unsigned char* __restrict__ bits, const float* __restrict__ t2, int ld,
                                                          const float* __restrict__ A, const float* __restrict__ B,
                                                          const float* __restrict__ sa, float* __restrict__ dv, int lddv,
-                                                         float* __restrict__ dq, int HW, int W, int C) {
+                                                         float* __restrict__ dq, int HW, int W, int C, const float* __restrict__ dl = nullptr,
+                                                         const float* __restrict__ hw = nullptr) {
     const int sub = threadIdx.x & (LPP - 1);
     const int cvec = C / 4;
     const int n = blockIdx.y;            // grid (pixel groups, images): the pixel's place in its image without a 64-bit division
@@ -297,7 +332,9 @@ __global__ __launch_bounds__(TPB) RB_EDGE_WAVES void rb_bwd1_ex_kernel(const flo
         }
         float s = 0.f;
         for (int c = sub * 4; c < C; c += LPP * 4) {
-            f32x4 g = *reinterpret_cast<const f32x4*>(dout + p * lddo + c);
+            f32x4 g;
+            if constexpr (RANK1) g = *reinterpret_cast<const f32x4*>(hw + c) * dl[p];
+            else g = *reinterpret_cast<const f32x4*>(dout + p * lddo + c);
             if constexpr (POOL) g += pooled_grad4_at(dpool, ldp, pidx, C, pq, pk, c);
             f32x4 o = {1.f, 1.f, 1.f, 1.f};
             unsigned int m = 0xfu;
@@ -793,7 +830,7 @@ __global__ __launch_bounds__(TPB) void outc_fwd_kernel(const float* __restrict__
         for (int c = sub * 4; c < C; c += LPP * 4) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + p * ld + c);
             const f32x4 k = *reinterpret_cast<const f32x4*>(w + c);
-            acc += v[0] * k[0] + v[1] * k[1] + v[2] * k[2] + v[3] * k[3];
+            acc += head_dot4(v, k);
         }
         acc = grp_sum16(acc);
         if (sub == 0) {
@@ -805,10 +842,12 @@ __global__ __launch_bounds__(TPB) void outc_fwd_kernel(const float* __restrict__
 }
 // dx[p][c] = dl*w[c];  partial dw[c] = sum dl*x[p][c], db = sum dl;  dl = dprob*prob*(1-prob), or dprob itself when prob is NULL (the caller
 // hands the logit's gradient: Fast-SCNN's head, whose sigmoid sits behind an upsampling)
+// DX false: dx is not written; the pixel's dl goes to dlout [P] instead (runet_rb_bwd1_rank1 rebuilds dx's values from it)
+template <bool DX>
 __global__ __launch_bounds__(TPB) void outc_bwd_partial(const float* __restrict__ dprob, const float* __restrict__ prob,
                                                         const float* __restrict__ x, int ld, const float* __restrict__ w,
                                                         float* __restrict__ dx, int lddx, long P, int C, long pix_per_chunk,
-                                                        float* __restrict__ part) {
+                                                        float* __restrict__ part, float* __restrict__ dlout = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int cvec = C / 4, rows = TPB / cvec, tid = threadIdx.x;
     const int col = tid % cvec, row = tid / cvec;
@@ -816,7 +855,8 @@ __global__ __launch_bounds__(TPB) void outc_bwd_partial(const float* __restrict_
     const long p1 = p0 + pix_per_chunk < P ? p0 + pix_per_chunk : P;
     float sw[4] = {0, 0, 0, 0}, sb = 0.f;
     if (row < rows) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col * 4);
+        f32x4 wv = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (DX) wv = *reinterpret_cast<const f32x4*>(w + col * 4);
         for (long p = p0 + row; p < p1; p += rows) {
             float dl = dprob[p];
             if (prob) {
@@ -827,7 +867,8 @@ __global__ __launch_bounds__(TPB) void outc_bwd_partial(const float* __restrict_
 #pragma unroll
             for (int q = 0; q < 4; ++q) sw[q] += dl * v[q];
             if (col == 0) sb += dl;
-            *reinterpret_cast<f32x4*>(dx + p * lddx + col * 4) = wv * dl;
+            if constexpr (DX) *reinterpret_cast<f32x4*>(dx + p * lddx + col * 4) = wv * dl;
+            else if (col == 0) dlout[p] = dl;
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) sm[row * (C + 1) + col * 4 + q] = sw[q];
@@ -908,7 +949,7 @@ void launch_rb_bwd1(const float* dout, int lddo, const float* dpool, int ldp, co
     auto kernel = dpool ? (relu_bits ? rb_bwd1_ex_kernel<true, true> : rb_bwd1_ex_kernel<true, false>)
                         : (relu_bits ? rb_bwd1_ex_kernel<false, true> : rb_bwd1_ex_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(gx, n_img), dim3(TPB), 0, (hipStream_t)stream, dout, lddo, dpool, ldp, pool_idx, out, ldo, relu_bits, t2, ld, A, B, sa,
-                       dv, lddv, dq, hw, w, c);
+                       dv, lddv, dq, hw, w, c, nullptr, nullptr);
 }
 
 // BN: 4 values per (image, chunk, channel) instead of 2, and the final pass of the shortcut BatchNorm's sums
@@ -1033,6 +1074,39 @@ extern "C" int runet_rb_bwd1_ex(const float* dout, int lddo, const float* dpool,
     RUNET_REQUIRE((dpool == nullptr) == (pool_idx == nullptr), "dpool and pool_idx come together");
     RUNET_REQUIRE(!dpool || (h % 2 == 0 && w % 2 == 0 && ldp >= c && ldp % 4 == 0), "pooled gradient: h and w must be even, stride a multiple of 4");
     launch_rb_bwd1(dout, lddo, dpool, ldp, pool_idx, out, ldo, relu_bits, t2, ld, A, B, sa, dv, lddv, dq, n_img, h * w, w, c, stream);
+    RUNET_CHECK_LAUNCH();
+}
+
+// runet_rb_out_ex (no pool) of the block in front of the 64 -> 1 head, with runet_outc_fwd(out, hw, hb) taken from the values it stores:
+// logit (or NULL) and prob [n_img*h*w], bit for bit what the two launches give.  c must be 64 (runet_rb_out_head_supported).
+extern "C" int runet_rb_out_head_supported(int c) { return c == 4 * LPP ? 1 : 0; }
+
+extern "C" int runet_rb_out_head(const float* t2, int ld, const float* A, const float* B, const float* sa, const float* r, int ldr,
+                                 const float* rs, const float* rh, float* out, int ldo, unsigned char* relu_bits, const float* hw, const float* hb,
+                                 float* logit, float* prob, int n_img, int h, int w, int c, void* stream) {
+    RUNET_REQUIRE(t2 && A && B && sa && r && out && hw && hb && prob, "null pointer");
+    RUNET_REQUIRE(runet_rb_out_head_supported(c), "the fused head needs c == 64 (runet_rb_out_head_supported)");
+    RUNET_REQUIRE(n_img >= 1 && h >= 1 && w >= 1, "bad shape");
+    RUNET_REQUIRE((long)h * w < (1L << 31), "image too large");
+    int ppc;
+    const int chunks = stream_chunks(h * w, h * w, c, ppc);
+    hipLaunchKernelGGL(relu_bits ? rb_out_head_kernel<true> : rb_out_head_kernel<false>, dim3(chunks, n_img), dim3(TPB), 0, (hipStream_t)stream, t2, ld, A,
+                       B, sa, r, ldr, rs, rh, out, ldo, relu_bits, h * w, ppc, hw, hb, logit, prob);
+    RUNET_CHECK_LAUNCH();
+}
+
+// runet_rb_bwd1_ex (no pool, mask from relu_bits) whose incoming gradient is the head's rank-1 dx[p][c] = hw[c] * dl[p]
+// (dl from runet_outc_bwd_dl): the tensor runet_outc_bwd would have written is neither stored nor read.
+extern "C" int runet_rb_bwd1_rank1(const float* dl, const float* hw, const unsigned char* relu_bits, const float* t2, int ld, const float* A,
+                                   const float* B, const float* sa, float* dv, int lddv, float* dq, int n_img, int h, int w, int c, void* stream) {
+    RUNET_REQUIRE(dl && hw && relu_bits && t2 && A && B && sa && dv && dq, "null pointer");
+    REQ_C4(c);
+    RUNET_REQUIRE(n_img >= 1 && h >= 1 && w >= 1 && (long)h * w < (1L << 31), "bad shape");
+    const int hwp = h * w;
+    int gx = px_grid(hwp);                                  // launch_rb_bwd1's grid
+    if (gx > 8192 / n_img) gx = 8192 / n_img > 0 ? 8192 / n_img : 1;
+    hipLaunchKernelGGL((rb_bwd1_ex_kernel<false, true, true>), dim3(gx, n_img), dim3(TPB), 0, (hipStream_t)stream, nullptr, 0, nullptr, 0, nullptr, nullptr,
+                       0, relu_bits, t2, ld, A, B, sa, dv, lddv, dq, hwp, w, c, dl, hw);
     RUNET_CHECK_LAUNCH();
 }
 
@@ -1196,7 +1270,23 @@ extern "C" int runet_outc_bwd(const float* dprob, const float* prob, const float
     hipStream_t st = (hipStream_t)stream;
     long chunks, ppc;
     chunking(pixels, c, chunks, ppc);
-    hipLaunchKernelGGL(outc_bwd_partial, dim3((int)chunks), dim3(TPB), part_lds(c, c + 1), st, dprob, prob, x, ld, w, dx, lddx, pixels, c, ppc, workspace);
+    hipLaunchKernelGGL(outc_bwd_partial<true>, dim3((int)chunks), dim3(TPB), part_lds(c, c + 1), st, dprob, prob, x, ld, w, dx, lddx, pixels, c, ppc, workspace,
+                       nullptr);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(c + 1), dim3(256), 0, st, workspace, chunks, c + 1, dw_db);
+    RUNET_CHECK_LAUNCH();
+}
+
+// runet_outc_bwd without dx: dw_db as there (same chunk plan, same sums), and dl [pixels] = dprob*prob*(1-prob) (prob NULL: dprob) left behind
+// for runet_rb_bwd1_rank1, which forms dx[p][c] = w[c]*dl[p] in its load instead of reading it back.
+extern "C" int runet_outc_bwd_dl(const float* dprob, const float* prob, const float* x, int ld, float* dl, float* workspace, float* dw_db,
+                                 long pixels, int c, void* stream) {
+    RUNET_REQUIRE(dprob && x && dl && workspace && dw_db, "null pointer");
+    REQ_C4(c);
+    hipStream_t st = (hipStream_t)stream;
+    long chunks, ppc;
+    chunking(pixels, c, chunks, ppc);
+    hipLaunchKernelGGL(outc_bwd_partial<false>, dim3((int)chunks), dim3(TPB), part_lds(c, c + 1), st, dprob, prob, x, ld, nullptr, nullptr, 0, pixels, c, ppc,
+                       workspace, dl);
     hipLaunchKernelGGL(reduce_rows_kernel, dim3(c + 1), dim3(256), 0, st, workspace, chunks, c + 1, dw_db);
     RUNET_CHECK_LAUNCH();
 }

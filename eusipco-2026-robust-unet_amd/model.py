@@ -524,12 +524,14 @@ def _net_forward(net: RobustUNet, x, save, want_logit=False):
         skips.append(cur)
     xd, C["bottleneck.1"] = B.dilated_forward(pooled, net.bottleneck[1].handles(), tr, save, hook)
     y, C["bottleneck.2"] = B.rb_forward(xd, rbs["bottleneck.2"].handles(), tr, masks["bottleneck.2"], save, hook)
+    w, b = ops.hwio(net.outc[0].weight), net.outc[0].bias
     for lvl in (4, 3, 2, 1):
         att, up = getattr(net, f"att{lvl}"), getattr(net, f"up{lvl}")
         cat, C[f"upgate{lvl}"] = B.upgate_forward(y, skips[lvl - 1], att.handles(up), tr, save, hook)
-        y, C[f"dec{lvl}"] = B.rb_forward(cat, rbs[f"dec{lvl}"].handles(), tr, masks[f"dec{lvl}"], save, hook)
-    w, b = ops.hwio(net.outc[0].weight), net.outc[0].bias
-    prob, logit = B.outc_forward(y, w, b, want_logit)
+        # the last block takes the 64 -> 1 head along in its tail kernel (blocks.FUSED_HEAD)
+        head = dict(w=w, b=b, want_logit=want_logit) if (lvl == 1 and B.fuses_head("fwd", rbs["dec1"].out_channels)) else None
+        y, C[f"dec{lvl}"] = B.rb_forward(cat, rbs[f"dec{lvl}"].handles(), tr, masks[f"dec{lvl}"], save, hook, head=head)
+    prob, logit = (head["prob"], head["logit"]) if head is not None else B.outc_forward(y, w, b, want_logit)
     if save:
         C["head"] = (y, w, prob)
         C["precision"] = net.precision
@@ -598,11 +600,14 @@ def net_backward(C, dprob, sink, done=lambda blk: None):
 
 def _net_backward(C, dprob, sink, done):
     y, w, prob = C["head"]
-    dy = B.outc_backward(dprob, prob, y, w, sink, pre="outc.0.")
+    # the head's data gradient is rank 1: with the block's fused edges it travels as (dl [P], w [C]) and dec1's rb_bwd1 forms it in its load
+    rank1 = B.fuses_head("bwd", y.shape[3]) and C["dec1"].get("relu_bits") is not None
+    head_grad = (B.outc_backward_dl(dprob, prob, y, sink, pre="outc.0."), w) if rank1 else None
+    dy = None if rank1 else B.outc_backward(dprob, prob, y, w, sink, pre="outc.0.")
     done("outc.0")
     dskip = {}
     for lvl in (1, 2, 3, 4):
-        dcat = B.rb_backward(C[f"dec{lvl}"], dy, sink, pre=f"dec{lvl}.")
+        dcat = B.rb_backward(C[f"dec{lvl}"], dy, sink, pre=f"dec{lvl}.", head_grad=head_grad if lvl == 1 else None)
         done(f"dec{lvl}")
         dy, dskip[lvl] = B.upgate_backward(C[f"upgate{lvl}"], dcat, sink, f"att{lvl}.", f"up{lvl}.")
         done(f"up{lvl}")

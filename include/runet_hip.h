@@ -170,6 +170,17 @@ int runet_rb_out_ex(const float* t2, int ld, const float* A, const float* B, con
 int runet_rb_bwd1_ex(const float* dout, int lddo, const float* dpool, int ldp, const unsigned char* pool_idx, const float* out, int ldo,
                      const unsigned char* relu_bits, const float* t2, int ld, const float* A, const float* B, const float* sa, float* dv,
                      int lddv, float* dq, int n_img, int h, int w, int c, void* stream);
+/* The 64 -> 1 head (outc below) folded into the tail of the block in front of it; bit for bit what the separate launches give.
+ * runet_rb_out_head = runet_rb_out_ex(no pool) + runet_outc_fwd(out, hw [c], hb [1], logit (or NULL), prob) taken from the values it
+ *   stores, without the re-read of `out` (which is still written).  c == 64 only: runet_rb_out_head_supported.
+ * runet_rb_bwd1_rank1 = runet_rb_bwd1_ex(no pool, mask from relu_bits) on dout[p][c] = hw[c] * dl[p], the head's data gradient, formed in
+ *   the load from dl [pixels] (runet_outc_bwd_dl) instead of being written and read back as a tensor. */
+int runet_rb_out_head_supported(int c);
+int runet_rb_out_head(const float* t2, int ld, const float* A, const float* B, const float* sa, const float* r, int ldr, const float* rs,
+                      const float* rh, float* out, int ldo, unsigned char* relu_bits, const float* hw, const float* hb, float* logit,
+                      float* prob, int n_img, int h, int w, int c, void* stream);
+int runet_rb_bwd1_rank1(const float* dl, const float* hw, const unsigned char* relu_bits, const float* t2, int ld, const float* A,
+                        const float* B, const float* sa, float* dv, int lddv, float* dq, int n_img, int h, int w, int c, void* stream);
 long runet_sa_conv7_bwd_workspace_floats(int n_img, int h, int w);
 int runet_sa_conv7_bwd(const float* smap, const float* dq, const float* wp, float* dsm, float* dwp, float* workspace, int n_img, int h,
                        int w, void* stream);
@@ -220,6 +231,9 @@ int runet_ag_bwd2_bn(const float* ds, const float* g1, int ldg, const float* x1,
 int runet_outc_fwd(const float* x, int ld, const float* w, const float* b, float* logit, float* prob, long pixels, int c, void* stream);
 int runet_outc_bwd(const float* dprob, const float* prob, const float* x, int ld, const float* w, float* dx, int lddx, float* workspace,
                    float* dw_db, long pixels, int c, void* stream);
+/* runet_outc_bwd without dx: the same dw_db, and dl [pixels] = dprob*prob*(1-prob) (prob NULL: dprob) for runet_rb_bwd1_rank1 */
+int runet_outc_bwd_dl(const float* dprob, const float* prob, const float* x, int ld, float* dl, float* workspace, float* dw_db,
+                      long pixels, int c, void* stream);
 
 /* ---- MaxPool2d(2) (Main_Final.py:235,239,243,249); idx: one byte per output element ---- */
 int runet_maxpool2_fwd(const float* x, int ldx, float* y, int ldy, unsigned char* idx, int n_img, int h, int w, int c, void* stream);

@@ -569,6 +569,66 @@ GEMM_LAYER_CASES = [
 ]
 
 
+def stem_conv(n, h, w, cin_w, cout, shortcut):
+    """runet_stem_conv_stats (csrc/conv_stem.hip): both outputs and their BatchNorm partials, one per 8 x 32 tile at the tile's index whichever
+    block of the persistent grid computes it"""
+    x, w3, w1 = rnd(n, h, w, 4), rnd(3, 3, cin_w, cout), rnd(1, 1, cin_w, cout) if shortcut else None
+    parts = lib.runet_stem_conv_stats_parts(n, h, w)
+    y3, s3 = out(n, h, w, cout), out(parts, cout, 3)
+    y1, s1 = (out(n, h, w, cout), out(parts, cout, 3)) if shortcut else (None, None)
+    check(lib.runet_stem_conv_stats(p(x), 4, p(w3), p(w1) if shortcut else None, p(y3), cout, p(y1) if shortcut else None, cout if shortcut else 0, n, h, w,
+                                    cin_w, cout, p(s3), p(s1) if shortcut else None, ops.stream()))
+    return [y3, s3] + ([y1, s1] if shortcut else [])
+
+
+def fused_equal(name, fused, unfused):
+    for i, (a, b) in enumerate(zip(fused, unfused)):
+        assert a.dtype == b.dtype and torch.equal(a.view(torch.uint8), b.view(torch.uint8)), f"{name}: output {i} differs from the unfused composition"
+
+
+def att_head_fwd(n, h, w, c):
+    """runet_rb_out_ex + runet_outc_fwd: the fingerprint; runet_rb_out_head (where the build has it) must give the same bytes"""
+    t2, A, B, sa = tail_inputs(n, h, w, c)
+    r, rs, rh, wt, b = rnd(n, h, w, c), rnd(c), rnd(c), rnd(c), rnd(1)
+    P = n * h * w
+    head = (p(t2), c, p(A), p(B), p(sa), p(r), c, p(rs), p(rh))
+    res = [out(n, h, w, c), torch.zeros((P, c // 4), dtype=torch.uint8, device=DEV), out(P), out(P)]
+    check(lib.runet_rb_out_ex(*head, p(res[0]), c, p(res[1]), None, 0, None, n, h, w, c, ops.stream()))
+    check(lib.runet_outc_fwd(p(res[0]), c, p(wt), p(b), p(res[2]), p(res[3]), P, c, ops.stream()))
+    if hasattr(lib, "runet_rb_out_head"):
+        f = [torch.zeros_like(t) for t in res]
+        check(lib.runet_rb_out_head(*head, p(f[0]), c, p(f[1]), p(wt), p(b), p(f[2]), p(f[3]), n, h, w, c, ops.stream()))
+        fused_equal("runet_rb_out_head", f, res)
+    return res
+
+
+def att_head_bwd(n, h, w, c):
+    """runet_outc_bwd + runet_rb_bwd1_ex on its dx: the fingerprint; runet_outc_bwd_dl + runet_rb_bwd1_rank1 must give the same bytes"""
+    t2, A, B, sa = tail_inputs(n, h, w, c)
+    P = n * h * w
+    x, wt, dprob, prob, rb = torch.relu(rnd(n, h, w, c)), rnd(c), rnd(P), torch.sigmoid(rnd(P)), ri(16, P, c // 4, dtype=torch.uint8)
+    k = ws(lib.runet_reduce_workspace_floats(1, P, c))
+    dx, res = out(n, h, w, c), [out(c + 1), out(n, h, w, c), out(P)]
+    tail = (p(t2), c, p(A), p(B), p(sa))
+    check(lib.runet_outc_bwd(p(dprob), p(prob), p(x), c, p(wt), p(dx), c, p(k), p(res[0]), P, c, ops.stream()))
+    check(lib.runet_rb_bwd1_ex(p(dx), c, None, 0, None, None, c, p(rb), *tail, p(res[1]), c, p(res[2]), n, h, w, c, ops.stream()))
+    if hasattr(lib, "runet_rb_bwd1_rank1"):
+        dl, f = out(P), [torch.zeros_like(t) for t in res]
+        check(lib.runet_outc_bwd_dl(p(dprob), p(prob), p(x), c, p(dl), p(k), p(f[0]), P, c, ops.stream()))
+        check(lib.runet_rb_bwd1_rank1(p(dl), p(wt), p(rb), *tail, p(f[1]), c, p(f[2]), n, h, w, c, ops.stream()))
+        fused_equal("runet_rb_bwd1_rank1", f, res)
+    return res
+
+
+# the stem: one tile | ragged tile rows and columns | 27 tiles | the one- and two-column-tile instances.  The head folded into the last
+# block's tail (C = 64): the unfused composition is the fingerprint, the fused entry points are held to it in the same run
+STEM_HEAD_CASES = [
+    (stem_conv, (1, 8, 32, 3, 64, 1)), (stem_conv, (2, 10, 40, 3, 64, 0)), (stem_conv, (3, 24, 96, 3, 64, 1)), (stem_conv, (2, 10, 40, 1, 32, 0)),
+    (stem_conv, (2, 10, 40, 3, 32, 1)),
+    *[(fn, s) for s in ((2, 6, 10, 64), (1, 16, 16, 64)) for fn in (att_head_fwd, att_head_bwd)],
+]
+
+
 # (entry point, arguments).  Partial rows each reducing case yields, from its file's chunk rule, against the 16 (hrnet, multiscale,
 # water_index) or 8 (fastscnn, dwsep, dwconv) part-lanes of the final pass:
 CASES = [
@@ -595,6 +655,7 @@ CASES = [
     *ATTENTION_CASES,
     *WINO2_CASES,
     *GEMM_LAYER_CASES,
+    *STEM_HEAD_CASES,
 ]
 
 
